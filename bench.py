@@ -7,7 +7,9 @@ BatchNorm + dropout 0.5, sorted segment-sum scatter, TF-1 non-lazy Adam over eve
 synthetic pre-hashed batch already resident in HBM.  Optimizer semantics are the reference's
 (`adam_mode=tf1_dense`): nothing is skipped inside the timed region.
 
-Prints ONE JSON line (rank 0).  Extra objects:
+Prints ONE JSON line (rank 0).  A plain run sets up, warms up, times EXACTLY --steps steps (one timed region), writes the
+outputs of the last step if --dump-outputs DIR is given, and prints the line.  Extra objects, measured only with --full (and
+config.launches_per_step; --full also times the headline region 5 times and reports the median, unless --repeats says otherwise):
   roofline     -- the kernel that moves the bytes: the TF-faithful dense Adam sweep.  With optimizer windows (the
                   default: include/rsx.h rsx_adam_window) that is adam_window_k, ONE pass over the optimizer state per
                   window of k steps: bytes of the pass / mean launch duration, HIP events on the launch stream;
@@ -50,7 +52,15 @@ def parse():
     p.add_argument("--host_input", action="store_true", help="measurement aid: every step's batch starts in pinned HOST "
                    "memory and crosses PCIe inside the timed region (one packed copy per step, per-step graphs); the "
                    "reported `value` of the default run never includes this")
-    p.add_argument("--repeats", type=int, default=5, help="the K-step timed region is run this many times; the median is reported")
+    p.add_argument("--repeats", type=int, default=None, help="the K-step timed region is run this many times; the median is "
+                   "reported (default: 1, so that --steps is the number of timed steps; 5 with --full)")
+    p.add_argument("--full", action="store_true", help="also measure everything beside the headline: the roofline leg, launches "
+                   "per step, the other BASELINE configs, the end-to-end config and the CPU baseline (each can be left out with "
+                   "its --no_* flag)")
+    p.add_argument("--dump-outputs", dest="dump_outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write what the timed path computed in its last step as DIR/<name>.npy (float32): "
+                        "the loss of that step and the trained variables (every dense variable, a fixed seeded sample of the rows "
+                        "of every embedding table)")
     p.add_argument("--no_cpu_baseline", action="store_true")
     p.add_argument("--cpu_seconds", type=float, default=25.0)
     p.add_argument("--n_batches", type=int, default=64)
@@ -70,7 +80,10 @@ def parse():
     p.add_argument("--config_steps", type=int, default=320, help="timed steps per entry of the `configs` list (x 3 repeats)")
     p.add_argument("--steps_per_graph", type=int, default=16, help="training steps captured per HIP graph (1: per-step "
                    "graph fed by one D2D copy of the batch)")
-    return p.parse_args()
+    a = p.parse_args()
+    if a.repeats is None:
+        a.repeats = 5 if a.full else 1
+    return a
 
 
 def cpu_baseline(batches, layout, seconds):
@@ -334,7 +347,7 @@ def time_config(a, model, batch_size, cin_bf16, dp, emu, rank, dev, steps, warmu
         dts.append(dt)
     med = sorted(range(len(dts)), key=lambda i: dts[i])[len(dts) // 2]
     dt = dts[med]
-    return {"est": est, "rank_dts": rank_dts[med] if rank_dts else None, "B": B, "dt": dt, "dts": dts, "cin": cin_ran(est, cin_bf16) if model == "xdeepfm" else False, "final_loss": float(loss), "host": host, "layout": layout, "feats": feats}
+    return {"est": est, "rank_dts": rank_dts[med] if rank_dts else None, "B": B, "dt": dt, "dts": dts, "cin": cin_ran(est, cin_bf16) if model == "xdeepfm" else False, "final_loss": float(loss), "loss": loss, "host": host, "layout": layout, "feats": feats}
 
 
 def other_configs(a, rank, dev):
@@ -575,39 +588,28 @@ def headline_step_kernels():
     return rows
 
 
-def main():
-    a = parse()
-    world = int(os.environ.get("WORLD_SIZE", "1"))
-    rank = int(os.environ.get("RANK", "0"))
-    from recsys_amd import build as _build
-    from recsys_amd import dist
-    if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
-        # `python bench.py --gpus N` on its own: become the launcher of N ranks (one per GPU; the driver's own form,
-        # `python -m torch.distributed.run ... bench.py --gpus N`, arrives here with WORLD_SIZE set and skips this)
-        _build.build(verbose=False)
-        raise SystemExit(dist.spawn_local_ranks(a.gpus, sys.argv[1:], script=os.path.abspath(__file__)))
-    if a.gpus > 1 and world != a.gpus:
-        raise SystemExit("bench.py --gpus %d inside a job of WORLD_SIZE=%d: launch N ranks for --gpus N" % (a.gpus, world))
-    dp = None
-    if world > 1 or os.environ.get("RSX_FORCE_DIST") == "1":
-        dist.init_process_group()            # nccl (= RCCL); RSX_DIST_BACKEND=gloo lets several ranks share ONE GPU (smoke runs)
-        dp = dist.DataParallel()
-    if rank == 0:
-        _build.build(verbose=False)          # no-op when the in-tree librsx.so is current
-    if dp is not None:
-        dp.barrier()                         # the other ranks load the library only after rank 0's build check
-    dev = torch.device("cuda", int(os.environ.get("LOCAL_RANK", "0")) % max(torch.cuda.device_count(), 1))
-    torch.cuda.set_device(dev)
-    emu = None
-    if a.emulate_world > 1 and dp is None:
-        from tests.dp_harness import EmulatedDataParallel          # (profiling harness, not product)
-        emu = EmulatedDataParallel(a.emulate_world)
+def dump_outputs(est, loss, out_dir, max_rows=65536):
+    """--dump-outputs: what the timed path leaves its caller after its last step, as float32 .npy files -- the loss of that step
+    and the trained variables: the whole dense arena and, per embedding table, the same seeded sample of at most `max_rows` rows
+    (sorted row indices drawn from default_rng(0)), so that two builds can be compared output for output."""
+    from recsys_amd.ops import EmbeddingArena
+    os.makedirs(out_dir, exist_ok=True)
+    store = est.store
+    out = {"loss": torch.as_tensor(loss).reshape(1), "dense": store.dense.flat}
+    for name, ar in sorted(store.embeddings.items()):
+        tab = ar.tables if isinstance(ar, EmbeddingArena) else ar.table          # (din.py: SparseTable views of one arena)
+        R = int(tab.shape[0])
+        rows = torch.from_numpy(np.sort(np.random.default_rng(0).choice(R, min(R, max_rows), replace=False))).to(tab.device)
+        out["%s.tables" % name] = tab.index_select(0, rows)
+        if getattr(ar, "w1", None) is not None:
+            out["%s.w1" % name] = ar.w1.index_select(0, rows)
+    torch.cuda.synchronize()
+    for k, v in out.items():
+        np.save(os.path.join(out_dir, k + ".npy"), v.detach().to("cpu", torch.float32).numpy())
 
-    dp_captured = dist.dp_capture(dp or emu)
-    t = time_config(a, a.model, a.batch_size, cin_mode(a.cin_bf16, a.cin_split), dp, emu, rank, dev, a.steps, a.warmup, a.repeats)
-    est, B, dt, dts, final_loss, host, layout = t["est"], t["B"], t["dt"], t["dts"], t["final_loss"], t["host"], t["layout"]
-    cin_run = t["cin"]
 
+def roofline_leg(a, est, B, dt, wk, cin_run):
+    """--full: the `roofline` object of the result line (see the module docstring), measured after the timed region."""
     # ---- roofline leg: the dominant kernel, HIP events on the launch stream (torch's current stream) -----
     store = est.store
     segs = store.adam_segments()
@@ -637,7 +639,6 @@ def main():
         adam_ms += e0.elapsed_time(e1)
     adam_ms /= reps * per
     roof = None
-    wk = est._window_len() if (not a.no_graph and not a.no_overlap) else 1      # (data-parallel runs use windows too)
 
     def pmc_traffic(kernel):
         """PMC-derived HBM bytes per launch: collected offline (scripts/pmc.sh, separate --pmc passes) and committed."""
@@ -723,10 +724,52 @@ def main():
                 roof["other_step_kernels"] = headline_step_kernels()
             except Exception as ex:
                 roof["other_step_kernels_error"] = repr(ex)[:200]
-    try:
-        n_launch = launches_per_step(est, t["feats"], wk)
-    except Exception as ex:
-        n_launch = None
+    return roof
+
+
+def main():
+    a = parse()
+    world = int(os.environ.get("WORLD_SIZE", "1"))
+    rank = int(os.environ.get("RANK", "0"))
+    from recsys_amd import build as _build
+    from recsys_amd import dist
+    if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
+        # `python bench.py --gpus N` on its own: become the launcher of N ranks (one per GPU; the driver's own form,
+        # `python -m torch.distributed.run ... bench.py --gpus N`, arrives here with WORLD_SIZE set and skips this)
+        _build.build(verbose=False)
+        raise SystemExit(dist.spawn_local_ranks(a.gpus, sys.argv[1:], script=os.path.abspath(__file__)))
+    if a.gpus > 1 and world != a.gpus:
+        raise SystemExit("bench.py --gpus %d inside a job of WORLD_SIZE=%d: launch N ranks for --gpus N" % (a.gpus, world))
+    dp = None
+    if world > 1 or os.environ.get("RSX_FORCE_DIST") == "1":
+        dist.init_process_group()            # nccl (= RCCL); RSX_DIST_BACKEND=gloo lets several ranks share ONE GPU (smoke runs)
+        dp = dist.DataParallel()
+    if rank == 0:
+        _build.build(verbose=False)          # no-op when the in-tree librsx.so is current
+    if dp is not None:
+        dp.barrier()                         # the other ranks load the library only after rank 0's build check
+    dev = torch.device("cuda", int(os.environ.get("LOCAL_RANK", "0")) % max(torch.cuda.device_count(), 1))
+    torch.cuda.set_device(dev)
+    emu = None
+    if a.emulate_world > 1 and dp is None:
+        from tests.dp_harness import EmulatedDataParallel          # (profiling harness, not product)
+        emu = EmulatedDataParallel(a.emulate_world)
+
+    dp_captured = dist.dp_capture(dp or emu)
+    t = time_config(a, a.model, a.batch_size, cin_mode(a.cin_bf16, a.cin_split), dp, emu, rank, dev, a.steps, a.warmup, a.repeats)
+    est, B, dt, dts, final_loss, host, layout = t["est"], t["B"], t["dt"], t["dts"], t["final_loss"], t["host"], t["layout"]
+    cin_run = t["cin"]
+    if a.dump_outputs and rank == 0:
+        dump_outputs(est, t["loss"], a.dump_outputs)
+
+    wk = est._window_len() if (not a.no_graph and not a.no_overlap) else 1      # (data-parallel runs use windows too)
+    roof = n_launch = None
+    if a.full:
+        roof = roofline_leg(a, est, B, dt, wk, cin_run)
+        try:
+            n_launch = launches_per_step(est, t["feats"], wk)
+        except Exception as ex:
+            n_launch = None
     world_seen = torch.distributed.get_world_size() if dp is not None else 1
     backend = torch.distributed.get_backend() if dp is not None else None
     rank_dts = t["rank_dts"]
@@ -752,19 +795,21 @@ def main():
                                       "all-gather per step), RCCL collectives %s" %
                                       ("captured into the graphs (steps_per_graph=%d)" % a.steps_per_graph if dp_captured else "eager between graph segments"))),
                       "global_batch": N * B, "parallelism": ("dp%d" % N) if emu is None else "EMULATED per-rank compute of dp%d (not a throughput claim)" % emu.world, "final_loss": round(final_loss, 5),
-                      "adam_window": wk, "launches_per_step": n_launch,
-                      **dp_exchange_info(store, B),
-                      "timed_repeats_ms_per_step": [round(x / a.steps * 1e3, 5) for x in dts], "reported": "median repeat"},
-           "roofline": roof}
-    if N == 1 and emu is None and not a.no_configs and a.model == "deepfm" and not a.host_input and a.adam_mode == "tf1_dense":
-        del t, est, store
+                      "adam_window": wk,
+                      **dp_exchange_info(est.store, B),
+                      "timed_repeats_ms_per_step": [round(x / a.steps * 1e3, 5) for x in dts], "reported": "median repeat"}}
+    if a.full:
+        out["config"]["launches_per_step"] = n_launch
+        out["roofline"] = roof
+    if a.full and N == 1 and emu is None and not a.no_configs and a.model == "deepfm" and not a.host_input and a.adam_mode == "tf1_dense":
+        del t, est
         out["configs"] = other_configs(a, rank, dev)
         if not a.no_e2e:
             try:
                 out["configs"].append(e2e_config(a, dev, out["ms_per_step"]))
             except Exception as e:                               # (must not take the headline line with it)
                 out["configs"].append({"workload": "deepfm.py end to end from TFRecord shards", "error": repr(e)[:300]})
-    if N == 1 and not a.no_cpu_baseline and a.model == "deepfm":
+    if a.full and N == 1 and not a.no_cpu_baseline and a.model == "deepfm":
         out["cpu_baseline"] = cpu_baseline(host, layout, a.cpu_seconds)
     print(json.dumps(out), flush=True)
 

@@ -1,5 +1,5 @@
 cd /root/repo
-run() { tag=$1; shift; env "$@" timeout 600 python bench.py --no_cpu_baseline --no_configs $ARGS 2>/dev/null | tail -1 | python -c "
+run() { tag=$1; shift; env "$@" timeout 600 python bench.py --full --no_cpu_baseline --no_configs $ARGS 2>/dev/null | tail -1 | python -c "
 import sys, json
 d = json.loads(sys.stdin.read()); c = d['config']
 print('$tag', 'ms_per_step', d['ms_per_step'], 'window', c['adam_window'], 'launches', c.get('launches_per_step'))"; }

@@ -14,11 +14,11 @@ try:
 except Exception as e:
     print('$1', 'NO LINE', e)"; }
 for m in ${MODELS:-deepfm fm dcn xdeepfm din}; do
-  timeout 600 python bench.py --model $m --no_cpu_baseline --no_configs "$@" 2>/dev/null | grep '"metric"' | tail -1 | line "single replica: model $m"
+  timeout 600 python bench.py --full --model $m --no_cpu_baseline --no_configs "$@" 2>/dev/null | grep '"metric"' | tail -1 | line "single replica: model $m"
   for ex in unique examples; do
     port=$((port + 1))
     RSX_DP_EXCHANGE=$ex RSX_FORCE_DIST=1 timeout 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 \
-      --master-port $port bench.py --gpus 1 --model $m --no_cpu_baseline --no_configs "$@" 2>/dev/null | grep '"metric"' | tail -1 | line "world-1 RCCL via C ABI, captured (default): model $m RSX_DP_EXCHANGE=$ex"
+      --master-port $port bench.py --full --gpus 1 --model $m --no_cpu_baseline --no_configs "$@" 2>/dev/null | grep '"metric"' | tail -1 | line "world-1 RCCL via C ABI, captured (default): model $m RSX_DP_EXCHANGE=$ex"
   done
 done
 ok=0; n=${SOAK:-50}
