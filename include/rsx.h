@@ -246,6 +246,36 @@ int rsx_adam_state_init_h(float* state_h /* host float[4]: words 0..3 of the sta
 int rsx_adam_tf1_multi(const rsx_adam_seg* segs_h, int nseg, float* state, float lr, float beta1,
                        float beta2, float eps, rsx_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Sparse optimizers (replaces tf.train.FtrlOptimizer, the default of deep&wide/deep&wide.py:146-149 and of
+ * estimator.LinearClassifier, and tf.train.AdagradOptimizer): TF 1.x training_ops ApplyFtrl / ApplyFtrlV2 /
+ * SparseApplyFtrl(V2) and ApplyAdagrad / SparseApplyAdagrad, fp32, one launch over all segments of a step.
+ *   FTRL (p = lr_power; p == -0.5 uses sqrt; shrinkage only when l2_shrinkage > 0, and never in the accumulator):
+ *     g_s = g + 2*l2_shrinkage*var; new_acc = acc + g*g; linear += g_s - (new_acc^-p - acc^-p) / lr * var;
+ *     y = new_acc^-p / lr + 2*l2; var = |linear| > l1 ? (l1*sign(linear) - linear) / y : 0; acc = new_acc
+ *   Adagrad: acc += g*g; var -= lr*g / sqrt(acc)
+ * Segments are rsx_adam_seg with m = FTRL's `linear` slot (unused by Adagrad) and v = the accumulator.  Kinds:
+ *   RSX_ADAM_DENSE       the dense form over n elements (dense gradient g, zero_grad honoured; B must be 0 / 1).
+ *   RSX_ADAM_TABLE_ROWS  the sparse form on the unique rows of the step (uniq_row / nuniq / B / stride; g = G [F*B, d],
+ *                        g_replicas 0 / 1).  d: a multiple of 4.
+ *   RSX_ADAM_VEC_SLOT    the dense form on a vector whose dense gradient is g[slot[i]] (slot[i] >= 0) and 0 elsewhere.
+ *                        A zero-gradient dense update leaves an element that has had one dense update bit for bit as it
+ *                        is (Adagrad always; FTRL while l2_shrinkage == 0), so only at the first step (state word 3 == 1)
+ *                        or with l2_shrinkage > 0 are the untouched elements written; otherwise they are skipped.
+ * Other kinds, and slot_w / a DENSE replica sum / g_replicas > 1, are rejected.  state: the RSX_ADAM_STATE_WORDS layout
+ * of rsx_adam_tf1_multi; the last workgroup advances the step (word 3); the beta-power words are left alone.  No per-step
+ * host argument: replayable from a hipGraph.  Rejected before any HIP call (RSX_EINVAL): lr <= 0, lr_power > 0, a
+ * negative l1 / l2 / l2_shrinkage, an unknown optimizer kind, nseg outside 1..RSX_ADAM_MAX_SEGS, missing pointers.
+ * ------------------------------------------------------------------------------------------- */
+#define RSX_OPT_ADAGRAD 1
+#define RSX_OPT_FTRL 2
+typedef struct {
+  int32_t kind;            /* RSX_OPT_ADAGRAD | RSX_OPT_FTRL */
+  float lr, lr_power, l1, l2, l2_shrinkage;     /* lr_power .. l2_shrinkage: FTRL only */
+} rsx_sparse_opt_hp;
+int rsx_sparse_opt_multi(const rsx_adam_seg* segs_h, int nseg, float* state, const rsx_sparse_opt_hp* hp,
+                         rsx_stream_t stream);
+
 /* Split form of the same TF-1 update, for overlapping the HBM-bound sweep with latency-bound kernels:
  * the untouched rows (*_COLD kinds) depend only on the PREVIOUS optimizer state and on which rows this step touches
  * (the slot map of rsx_field_sort), so their sweep may run -- cut into slices of workgroups -- as extra workgroups of

@@ -10,6 +10,7 @@ LIB_PATH = os.environ.get("RSX_LIB_PATH") or os.path.join(_HERE, "librsx.so")
 (RSX_ADAM_DENSE, RSX_ADAM_TABLE_TF1, RSX_ADAM_VEC_SLOT, RSX_ADAM_TABLE_ROWS, RSX_ADAM_VEC_ROWS, RSX_ADAM_TABLE_TF1_COLD,
  RSX_ADAM_VEC_COLD, RSX_ADAM_VEC_ROWS_DENSE) = range(8)
 RSX_ADAM_MAX_SEGS = 12
+RSX_OPT_ADAGRAD, RSX_OPT_FTRL = 1, 2         # include/rsx.h rsx_sparse_opt_hp.kind
 
 
 class RsxError(RuntimeError):
@@ -177,6 +178,14 @@ class SortJob(C.Structure):
 
 
 ADAM_WINDOW_MAX = 8
+
+
+class SparseOptHp(C.Structure):
+    """include/rsx.h rsx_sparse_opt_hp (FTRL / Adagrad hyper-parameters)."""
+    _fields_ = [("kind", C.c_int32), ("lr", C.c_float), ("lr_power", C.c_float), ("l1", C.c_float), ("l2", C.c_float),
+                ("l2_shrinkage", C.c_float)]
+
+
 ADAM_STATE_WORDS = 4 + 32 * 32        # include/rsx.h RSX_ADAM_STATE_WORDS
 
 
@@ -216,6 +225,7 @@ _SIGS = {
     "rsx_segsum_partials_ride": (_I, [_P] * 9 + [_U64, _I, _I, _I, _I, _I, _P, C.POINTER(ScatterRiders), _P]),
     "rsx_adam_state_init_h": (_I, [_P, _F, _F]),
     "rsx_adam_tf1_multi": (_I, [C.POINTER(AdamSeg), _I, _P, _F, _F, _F, _F, _P]),
+    "rsx_sparse_opt_multi": (_I, [C.POINTER(AdamSeg), _I, _P, C.POINTER(SparseOptHp), _P]),
     "rsx_tower_fwd_layer": (_I, [_P] * 11 + [C.c_uint32, _I, _F, _I, _I, _I, _P, _P, _P, _I, _P]),
     "rsx_gather_tower_fwd0": (_I, [_P] * 8 + [_U64, _I, _I, _P, _P, _P, _P, _I, _I, _P, _P, _P, _I, _P]),
     "rsx_gather_tower_fwd0_supported": (_I, [_I, _I, _I]),

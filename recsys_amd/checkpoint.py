@@ -1,6 +1,7 @@
 """Checkpoint / resume: what Estimator's RunConfig(save_checkpoints_steps, keep_checkpoint_max=5)
 plus model_dir auto-resume give the reference scripts (fm/fm.py:187-194,204-209).  Files are
-`model.ckpt-<global_step>.pt` holding tables, first-order weights, dense arena, Adam slots and beta powers."""
+`model.ckpt-<global_step>.pt` holding tables, first-order weights, dense arena, optimizer slots and state (Adam's beta
+powers; FTRL / Adagrad add their name and hyper-parameters, and restoring under another optimizer raises)."""
 import glob
 import os
 import re

@@ -330,6 +330,13 @@ def define_flags(p=None):
     p.add_argument("--adam_window", type=int, default=0,
                    help="steps per optimizer window (include/rsx.h rsx_adam_window; bit-identical to single steps): 0 = the "
                         "model's default (8 up to batch 1024, 4 above), 1 = every step on its own")
+    # tf.train.AdagradOptimizer / FtrlOptimizer in place of AdamOptimizer (their TF argument names and defaults)
+    p.add_argument("--optimizer", default="adam", choices=["adam", "adagrad", "ftrl"])
+    p.add_argument("--initial_accumulator_value", type=float, default=0.1)
+    p.add_argument("--learning_rate_power", type=float, default=-0.5, help="ftrl")
+    p.add_argument("--l1_regularization_strength", type=float, default=0.0, help="ftrl")
+    p.add_argument("--l2_regularization_strength", type=float, default=0.0, help="ftrl")
+    p.add_argument("--l2_shrinkage_regularization_strength", type=float, default=0.0, help="ftrl")
     p.add_argument("--feature_set", default="criteo", choices=["criteo", "uid_iid"],
                    help="criteo: the 39-field pipeline of fm.py (BASELINE configs); uid_iid: deepfm.py as committed "
                         "(int64 u_id / i_id hashed into 500000 / 100000 buckets, int64 label)")
@@ -362,8 +369,27 @@ def make_params(FLAGS, linear="indicator_all"):
     return params
 
 
+def optimizer_config(FLAGS):
+    """(optimizer, optimizer_hparams) of RunConfig from the --optimizer flags."""
+    opt = getattr(FLAGS, "optimizer", "adam")
+    if opt == "adam":
+        return opt, None
+    hp = {"initial_accumulator_value": FLAGS.initial_accumulator_value}
+    if opt == "ftrl":
+        hp.update(learning_rate_power=FLAGS.learning_rate_power, l1_regularization_strength=FLAGS.l1_regularization_strength,
+                  l2_regularization_strength=FLAGS.l2_regularization_strength,
+                  l2_shrinkage_regularization_strength=FLAGS.l2_shrinkage_regularization_strength)
+    return opt, hp
+
+
 def run_main(model_fn, FLAGS, make_params_fn):
     """The `main(_)` driver shared by the Criteo scripts (fm/fm.py:173-224, deepfm/deepfm.py:153-234, ...)."""
+    optimizer, optimizer_hparams = optimizer_config(FLAGS)
+    if optimizer != "adam" and FLAGS.mirror:
+        # data-parallel training exists for the Adam step only (VariableStore.build refuses a data-parallel store)
+        print("INFO:--optimizer %s: one replica in this process (data-parallel training supports --optimizer adam only)"
+              % optimizer, flush=True)
+        FLAGS.mirror = False
     if FLAGS.mirror:
         # MirroredStrategy() = every GPU of the host (fm/fm.py:184-186): on a multi-GPU box this process becomes the launcher
         from . import dist
@@ -376,7 +402,8 @@ def run_main(model_fn, FLAGS, make_params_fn):
     train_files, eval_files = files[:-FLAGS.eval_parts], files[-FLAGS.eval_parts:]
     params = make_params_fn(FLAGS)
     config = RunConfig(save_checkpoints_steps=FLAGS.save_checkpoints_steps, keep_checkpoint_max=5,
-                       log_step_count_steps=FLAGS.log_steps, adam_mode=FLAGS.adam_mode)
+                       log_step_count_steps=FLAGS.log_steps, adam_mode=FLAGS.adam_mode, optimizer=optimizer,
+                       optimizer_hparams=optimizer_hparams)
     est = Estimator(model_fn, FLAGS.model_dir, params, config)
     shard = None
     if FLAGS.mirror:

@@ -36,6 +36,9 @@ def _prefer_rocblas():
 
 
 def build_variables(store, params, B, P):
+    if store.optimizer != "adam":
+        # DIN's tables are SparseTable views (ops.SparseTable) that have no row-segment optimizer form
+        raise _lib.RsxError("din.py: optimizer=%r is not supported (DIN trains with optimizer='adam' only)" % store.optimizer)
     _prefer_rocblas()
     K = params["embedding_size"]
     n_item, n_cate = params.get("n_item", N_ITEM), params.get("n_cate", N_CATE)

@@ -24,7 +24,7 @@ import torch
 
 from . import _lib
 from . import metrics as _metrics
-from .ops import AdamTF1, DenseArena, EmbeddingArena
+from .ops import SPARSE_OPTIMIZERS, AdamTF1, DenseArena, EmbeddingArena
 
 
 class ModeKeys:
@@ -56,6 +56,11 @@ class RunConfig:
     device: str = "cuda"
     seed: int = 0
     adam_mode: str = "tf1_dense"    # 'tf1_dense' (reference semantics) | 'lazy_rows' (NOT TF semantics)
+    # 'adam' (tf.train.AdamOptimizer, adam_mode above) | 'adagrad' | 'ftrl' (tf.train.AdagradOptimizer / FtrlOptimizer:
+    # ops.AdagradTF1 / FtrlTF1, sparse on the tables' unique rows); optimizer_hparams: their TF argument names
+    # (initial_accumulator_value, learning_rate_power, l1_/l2_/l2_shrinkage_regularization_strength), TF's defaults
+    optimizer: str = "adam"
+    optimizer_hparams: Optional[Dict[str, float]] = None
 
 
 @dataclass
@@ -193,7 +198,9 @@ class LazyMeanLoss:
 class VariableStore:
     """The variables of one model: named embedding arenas + one flat dense arena + the optimizer."""
 
-    def __init__(self, device, seed, adam_mode):
+    def __init__(self, device, seed, adam_mode, optimizer="adam", optimizer_hparams=None):
+        if optimizer != "adam" and optimizer not in SPARSE_OPTIMIZERS:
+            raise ValueError("optimizer must be one of adam, %s; got %r" % (", ".join(sorted(SPARSE_OPTIMIZERS)), optimizer))
         self.device = torch.device(device)
         self.embeddings: Dict[str, EmbeddingArena] = {}
         self.dense: Optional[DenseArena] = None
@@ -201,7 +208,12 @@ class VariableStore:
         self.built = False
         self.gen = torch.Generator(device="cpu")
         self.gen.manual_seed(seed)
-        self.adam_mode = adam_mode
+        # The one predicate of the model code: every fused-Adam branch (the split TF-1 sweep, optimizer windows, the cold-sweep
+        # slices, the segment-sum fused with Adam) tests adam_mode == "tf1_dense".  Under another optimizer it is "off", so
+        # none of them runs and the steps end in segsum + apply_gradients (rsx_sparse_opt_multi).
+        self.optimizer = optimizer
+        self.optimizer_hparams = dict(optimizer_hparams or {})
+        self.adam_mode = adam_mode if optimizer == "adam" else "off"
         self.extra_segments = []     # model-specific optimizer segments (e.g. DIN tables)
         self.dp = None               # recsys_amd.dist.DataParallel when training data-parallel
         self.graph_safe_dp = False   # set by model code whose DP collectives run outside autograd (segmentable)
@@ -224,7 +236,21 @@ class VariableStore:
                 t = torch.empty(tuple(dense_shapes[k]))
                 fn(t, self.gen)
                 self.dense[k].copy_(t)
-        self.opt = AdamTF1(lr=lr, device=self.device)
+        if self.optimizer == "adam":
+            self.opt = AdamTF1(lr=lr, device=self.device)
+        else:
+            if self.dp is not None:
+                raise _lib.RsxError("optimizer=%r: data-parallel training supports optimizer='adam' only" % self.optimizer)
+            if self.extra_segments:
+                raise _lib.RsxError("optimizer=%r: this model's variables have no sparse-optimizer segments" % self.optimizer)
+            self.opt = SPARSE_OPTIMIZERS[self.optimizer](lr=lr, device=self.device, **self.optimizer_hparams)
+            acc0 = self.opt.initial_accumulator_value
+            with torch.no_grad():           # every accumulator slot starts at initial_accumulator_value (TF's slot init)
+                for a in embeddings.values():
+                    a.v_t.fill_(acc0)
+                    if a.with_w1:
+                        a.v_w.fill_(acc0)
+                self.dense.v.fill_(acc0)
         self.built = True
 
     def adam_segments(self):
@@ -253,18 +279,33 @@ class VariableStore:
             loss.backward()
         self.apply_gradients()
 
+    def sparse_opt_segments(self):
+        segs = []
+        for a in self.embeddings.values():
+            segs += a.sparse_opt_segments()
+        return segs + self.dense.adam_segments()
+
     def apply_gradients(self):
+        if self.optimizer != "adam":
+            self.opt.step(self.sparse_opt_segments())
+            return
         self.opt.step(self.adam_segments())
 
     # -- checkpoint -------------------------------------------------------
     def state_dict(self):
         sd = {"opt_state": self.opt.state.cpu(), "dense": {k: getattr(self.dense, k).cpu() for k in ("flat", "m", "v")}}
+        if self.optimizer != "adam":        # (no tag: Adam -- what every checkpoint written before the tag existed holds)
+            sd["optimizer"] = {"name": self.optimizer, "hparams": dict(self.opt.hparams)}
         for name, a in self.embeddings.items():
             sd["emb." + name] = {k: getattr(a, k).cpu() for k in ("tables", "m_t", "v_t", "w1", "m_w", "v_w", "table", "m", "v")
                                  if getattr(a, k, None) is not None}
         return sd
 
     def load_state_dict(self, sd):
+        tag = sd.get("optimizer") or {"name": "adam"}
+        if tag["name"] != self.optimizer:
+            raise _lib.RsxError("checkpoint was written by optimizer=%r (%s); this run uses optimizer=%r -- the slots do not carry "
+                                "over" % (tag["name"], tag.get("hparams", {}), self.optimizer))
         with torch.no_grad():
             self.opt.state[:4].copy_(sd["opt_state"][:4])      # (beta powers, ticket, step; the arrival counters stay zero)
             for k in ("flat", "m", "v"):
@@ -293,7 +334,11 @@ class Estimator:
         self.model_dir = model_dir
         self.params = dict(params or {})
         self.config = config or RunConfig()
-        self.store = VariableStore(self.config.device, self.config.seed, self.config.adam_mode)
+        self.store = VariableStore(self.config.device, self.config.seed, self.config.adam_mode, self.config.optimizer,
+                                   self.config.optimizer_hparams)
+        if self.config.optimizer != "adam" and int(self.params.get("adam_window", 0) or 0) > 1:
+            raise _lib.RsxError("adam_window=%d: optimizer windows exist for optimizer='adam' only (got optimizer=%r)"
+                                % (int(self.params["adam_window"]), self.config.optimizer))
         self._graphs = {}
         self._ring = {}        # pinned staging buffers for host batches (see _h2d)
         # captured instances of a streaming window that take turns (_train_window_packed): window w + 1 is staged into the

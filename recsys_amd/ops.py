@@ -530,6 +530,17 @@ class EmbeddingArena:
                                  g=self.gw1, slot=slot))
         return segs
 
+    def sparse_opt_segments(self):
+        """rsx_sparse_opt_multi segments (FtrlTF1 / AdagradTF1): the tables' IndexedSlices gradient -> the sparse form on the
+        step's unique rows; the first-order vector's gradient is DENSE in TF (one-hot matmul kernel) -> the dense form over
+        the vector (VEC_SLOT).  m = FTRL's `linear` slot, v = the accumulator."""
+        segs = [dict(kind=_lib.RSX_ADAM_TABLE_ROWS, d=self.D, n=self.F * self.last_B, var=self.tables, m=self.m_t,
+                     v=self.v_t, g=self.G, uniq_row=self.uniq_row, nuniq=self.nuniq, B=self.last_B, stride=self.stride)]
+        if self.with_w1:
+            segs.append(dict(kind=_lib.RSX_ADAM_VEC_SLOT, n=self.R, var=self.w1, m=self.m_w, v=self.v_w, g=self.gw1,
+                             slot=self.slot))
+        return segs
+
 
 class GatherFM(torch.autograd.Function):
     """Autograd node of the fused gather (+first-order +FM2).  backward = sorted segment-sum into the
@@ -730,6 +741,84 @@ class AdamTF1:
     @property
     def global_step(self):
         return int(self.state.view(torch.int32)[3].item()) - 1
+
+
+class _SparseOptTF1:
+    """Common part of FtrlTF1 / AdagradTF1: one rsx_sparse_opt_multi launch per step over every segment (include/rsx.h).
+    Segments are AdamTF1's dicts with m = FTRL's `linear` slot and v = the accumulator; the state has AdamTF1's layout
+    (word 3 = the step, advanced on the device; the beta-power words are unused)."""
+    name = None
+    KIND = None
+
+    def __init__(self, lr, initial_accumulator_value, device, lr_power=-0.5, l1=0.0, l2=0.0, l2_shrinkage=0.0):
+        self.hparams = self._check(lr, initial_accumulator_value, lr_power, l1, l2, l2_shrinkage)
+        dev = _require_cuda(device)
+        self.initial_accumulator_value = float(initial_accumulator_value)
+        self.hp = _lib.SparseOptHp(self.KIND, float(lr), float(lr_power), float(l1), float(l2), float(l2_shrinkage))
+        st = np.zeros(_lib.ADAM_STATE_WORDS, np.float32)
+        st.view(np.uint32)[3] = 1                  # the step counter of rsx_adam_state_init_h
+        self.state = torch.from_numpy(st).to(dev)
+
+    @staticmethod
+    def _check(lr, acc0, lr_power, l1, l2, l2_shrinkage):
+        raise NotImplementedError
+
+    def step(self, segments):
+        arr, n = AdamTF1._seg_array(segments)
+        check(lib().rsx_sparse_opt_multi(arr, n, _ptr(self.state), C.byref(self.hp), _stream()), "rsx_sparse_opt_multi")
+
+    @property
+    def global_step(self):
+        return int(self.state.view(torch.int32)[3].item()) - 1
+
+
+class AdagradTF1(_SparseOptTF1):
+    """tf.train.AdagradOptimizer(lr, initial_accumulator_value=0.1): ApplyAdagrad on dense gradients, SparseApplyAdagrad on
+    the unique rows of an IndexedSlices gradient: acc += g*g; var -= lr*g / sqrt(acc)."""
+    name = "adagrad"
+    KIND = _lib.RSX_OPT_ADAGRAD
+
+    def __init__(self, lr=1e-3, initial_accumulator_value=0.1, device="cuda"):
+        super().__init__(lr, initial_accumulator_value, device)
+
+    @staticmethod
+    def _check(lr, acc0, lr_power, l1, l2, l2_shrinkage):
+        if not float(lr) > 0.0:
+            raise ValueError("AdagradOptimizer: learning_rate must be > 0, got %r" % (lr,))
+        if not float(acc0) > 0.0:
+            raise ValueError("AdagradOptimizer: initial_accumulator_value must be > 0, got %r" % (acc0,))
+        return {"learning_rate": float(lr), "initial_accumulator_value": float(acc0)}
+
+
+class FtrlTF1(_SparseOptTF1):
+    """tf.train.FtrlOptimizer (deep&wide/deep&wide.py:146-149): ApplyFtrl / SparseApplyFtrl, and the ApplyFtrlV2 forms when
+    l2_shrinkage > 0 (include/rsx.h rsx_sparse_opt_multi for the formula).  The `linear` slot starts at 0."""
+    name = "ftrl"
+    KIND = _lib.RSX_OPT_FTRL
+
+    def __init__(self, lr=1e-3, learning_rate_power=-0.5, initial_accumulator_value=0.1, l1_regularization_strength=0.0,
+                 l2_regularization_strength=0.0, l2_shrinkage_regularization_strength=0.0, device="cuda"):
+        super().__init__(lr, initial_accumulator_value, device, learning_rate_power, l1_regularization_strength,
+                         l2_regularization_strength, l2_shrinkage_regularization_strength)
+
+    @staticmethod
+    def _check(lr, acc0, lr_power, l1, l2, l2_shrinkage):
+        if not float(lr) > 0.0:
+            raise ValueError("FtrlOptimizer: learning_rate must be > 0, got %r" % (lr,))
+        if not float(lr_power) <= 0.0:
+            raise ValueError("FtrlOptimizer: learning_rate_power must be <= 0, got %r" % (lr_power,))
+        if not float(acc0) >= 0.0:
+            raise ValueError("FtrlOptimizer: initial_accumulator_value must be >= 0, got %r" % (acc0,))
+        for k, v in (("l1_regularization_strength", l1), ("l2_regularization_strength", l2),
+                     ("l2_shrinkage_regularization_strength", l2_shrinkage)):
+            if not float(v) >= 0.0:
+                raise ValueError("FtrlOptimizer: %s must be >= 0, got %r" % (k, v))
+        return {"learning_rate": float(lr), "learning_rate_power": float(lr_power), "initial_accumulator_value": float(acc0),
+                "l1_regularization_strength": float(l1), "l2_regularization_strength": float(l2),
+                "l2_shrinkage_regularization_strength": float(l2_shrinkage)}
+
+
+SPARSE_OPTIMIZERS = {"adagrad": AdagradTF1, "ftrl": FtrlTF1}
 
 
 class FusedTower:
