@@ -150,7 +150,7 @@ class DinFused:
         arena.null_last = True
         arena._bind_partials()
         if self.dp is not None:
-            from .deepfm import dp_unique_wanted
+            from .fused_step import dp_unique_wanted
             if dp_unique_wanted(store, {}) and EmbeddingArena.unique_exchange_ok(arena.row_off_np, self.dp.world):
                 # round 5: every rank de-duplicates and sums ITS entries (the single replica's sort + scatter), the ranks exchange
                 # unique (row, sum) lists: send block [dense | G [capT, K] | bias sums [capT]], capT = min(entries, item rows + 1)

@@ -5,16 +5,16 @@ logits = dense([relu(first_order), fm_second_order], 1).  The whole model is the
 (gather + first-order + FM forward, sorted segment-sum backward) plus a 2->1 dense head.
 """
 import ctypes as C
-import os
 
 import torch
 
 from . import _lib
+from . import fused_step
 from . import layers as L
 from .deepfm import build_variables as _build
-from .deepfm import define_flags, dp_unique_wanted, input_fn, make_params, run_main  # noqa: F401
+from .deepfm import define_flags, input_fn, make_params, run_main  # noqa: F401
 from .estimator import EstimatorSpec, ModeKeys, get_variable_store
-from .ops import EmbeddingArena, _ptr, _stream, gather_fm
+from .ops import _ptr, _stream, gather_fm
 
 
 def model_fn(features, labels, mode, params):
@@ -24,28 +24,12 @@ def model_fn(features, labels, mode, params):
     if not store.built:
         cap = max(int(params.get("max_batch_size", 0)), ids.shape[0])
         _build(store, params, capacity=cap, with_dnn=False)
-        a0 = store.embeddings["input_layer"]
-        want_ux = store.dp is not None and params.get("fused", True) and dp_unique_wanted(store, params) and \
-            EmbeddingArena.unique_exchange_ok(a0.row_off_np, store.dp.world)
-        if store.adam_mode == "tf1_dense" and params.get("fused", True):
-            gcap = cap * (store.dp.world if store.dp is not None else 1)
-            if (cap if want_ux else gcap) <= 16384:      # (unique-list exchange: the window's sorts are the ranks' local ones)
-                store.window_k = _lib.default_adam_window(gcap, want_ux)     # optimizer windows (include/rsx.h rsx_adam_window)
-                store.window_dp = True
         store.dp_block = False
-        store.dp_unique = False
-        if store.dp is not None and params.get("fused", True):
-            # data-parallel: the dense gradient arena + the rank's block of the sparse exchange in one persistent send block --
-            # [G [capT, D] | gw1 [capT]] (unique-row lists, round 5: deepfm.py) or, RSX_DP_EXCHANGE=examples, [S | gy2 | gy1] of
-            # the local batch
-            if want_ux:
-                ux = a0.enable_unique_exchange(store.dp.world, cap)
-                store.dp.make_send_block(store.dense, ux.capT, [a0.D, 1])
-                store.dp_unique = True
-            else:
-                store.dp.make_send_block(store.dense, cap, [a0.D, 1, 1])
-            store.dp_block = True
-            store.graph_safe_dp = True       # the fused step issues its collectives outside autograd
+        if params.get("fused", True):
+            # data-parallel send block: [S | gy2 | gy1] per example, or [G | gw1] per packed unique row
+            a0 = store.embeddings["input_layer"]
+            fused_step.configure(store, params, [a0], cap * (store.dp.world if store.dp is not None else 1), [a0.D, 1, 1],
+                                 [a0.D, 1], windows=store.adam_mode == "tf1_dense", send_block=True)
     arena, P = store.embeddings["input_layer"], store.dense
     training = mode == ModeKeys.TRAIN
     if training and store.adam_mode == "tf1_dense" and params.get("fused", True) and (store.dp is None or store.dp_block):
@@ -85,46 +69,21 @@ def model_fn(features, labels, mode, params):
 def _train_fused(store, arena, ids, labels):
     """TRAIN step as 4 launches, no autograd: dedup sort -> gather (+ first order + FM) -> FM head with its backward,
     carrying most of the untouched-row Adam sweep as extra workgroups -> segment-sum fused with the touched-row and dense
-    Adam (+ the rest of the sweep).  Same exact split of the TF-1 update as deepfm.py."""
+    Adam (+ the rest of the sweep).  The exact split of the TF-1 update and the scheduling around these launches:
+    fused_step.py."""
     P, dp = store.dense, store.dp
     B = ids.shape[0]
     dev = ids.device
     with torch.no_grad():
-        # data-parallel: the optimizer sees the GLOBAL batch -- dedup sort over the all-gathered ids, per-example gradient
-        # block [S | gy2 | gy1] + dense arena exchanged by ONE all-gather straight from the send block (see deepfm.py)
-        # optimizer window (deepfm.py, include/rsx.h rsx_adam_window): position 0 sorts the ids of all wk batches and sweeps the
-        # untouched rows ONCE for the whole window (a launch of its own); the other positions run neither
-        wk, wpos, wfeat = store.window_of_step()
-        arena.select(wpos)
-        sweep = sweep2 = None
-        ux = dp is not None and store.dp_unique
-        if ux:
-            # ids phase of the unique-list exchange (deepfm._train_fused): local sorts -> key blocks -> one all-gather -> merge
-            if wpos == 0:
-                idl = [f["ids"] for f in wfeat] if wk > 1 else [ids]
-                arena.ux_merge(dp.all_gather_keys(arena.ux_sort_pack(idl), arena, idl), wk)
-            arena.select(wpos)
-            arena.last_B = arena.ux.max_unique
-            if wk > 1:
-                if wpos == 0:
-                    cold, _ = arena.adam_split_segments(window_k=wk)
-                    store.opt.window_sweep(cold[::-1])
-            else:
-                cold, hot = arena.adam_split_segments()
-                sweep, sweep2 = store.opt.cold_slices(cold[::-1], [0.7, 0.3])
-        elif wk > 1:
-            if wpos == 0:
-                from .dist import window_global_ids
-                arena.sort_window(window_global_ids(dp, wfeat))    # data-parallel: one all-gather for all wk batches' ids
-                cold, _ = arena.adam_split_segments(window_k=wk)
-                store.opt.window_sweep(cold[::-1])
-            arena.last_B = B * (dp.world if dp is not None else 1)
-        else:
-            arena.field_sort(dp.all_gather_id_list([ids], prefetchable=True)[0] if dp is not None else ids)
-            cold, hot = arena.adam_split_segments()
-            # 70 % of the untouched-row sweep rides in the head launch, 30 % (table blocks only: the first-order vector goes
-            # first) in the scatter + touched-row Adam launch (measured: 76.4 -> 72.2 us per step)
-            sweep, sweep2 = store.opt.cold_slices(cold[::-1], [0.7, 0.3])
+        # (this path is the split TF-1 update by construction: model_fn takes it under adam_mode tf1_dense only)
+        plan = fused_step.begin(store, [arena], ids, split=True)
+        fused_step.sort_ids(plan)
+        fused_step.sort_now(plan)
+        # 70 % of the untouched-row sweep rides in the head launch, 30 % (table blocks only: the first-order vector goes
+        # first) in the scatter + touched-row Adam launch (measured: 76.4 -> 72.2 us per step)
+        fused_step.split_update(plan, [0.7, 0.3], 1)
+        ux = plan.ux
+        sweep = plan.sweeps[0] if plan.sweeps is not None else None
         Sv, gy2v, gy1v = dp.send_views(B) if (dp is not None and not ux) else (None,) * 3
         prob = torch.empty(B, device=dev)
         gy1, gy2 = (gy1v, gy2v) if (dp is not None and not ux) else (torch.empty(B, device=dev) for _ in range(2))
@@ -161,29 +120,16 @@ def _train_fused(store, arena, ids, labels):
                 stride if terms is not None else 0, P.n, P.offsets["b1"], P.offsets["out.W"], P.offsets["out.b"],
                 1.0 / (B * world), B, None if sweep is None else C.byref(sweep), _stream()), "rsx_fm_head_terms")
 
-        if ux:      # the rank's own sorted segment-sum, written as its block of the send buffer (deepfm._train_fused)
-            Gv, gw1v = dp.send_views(arena.ux.capT)
-            arena.ux_segsum_local(B, S, None, gy1, gy2, Gv, gw1v, wpos)
+        grads = [(S, None, gy1, gy2)]
+        fused_step.local_sums(plan, grads)
 
     def train_op():
         with torch.no_grad():
-            if ux:
-                (G0, gw10), blocks, dense_segs = dp.gather_send_block(arena.ux.capT, fold_dense=True)
-                arena.select(wpos)
-                arena.ux_merged_adam(G0, gw10, blocks[1], store.opt, dense_segs or store.dense.adam_segments(), sweep2,
-                                     window=(wk, wpos))
-            elif dp is not None:
-                (Sg, gy2g, gy1g), blocks, dense_segs = dp.gather_send_block(B, fold_dense=True)
-                arena.select(wpos)
-                arena.segsum_adam(B * world, Sg, None, gy1g, gy2g, store.opt, dense_segs or store.dense.adam_segments(), sweep2,
-                                  blocks=blocks, window=(wk, wpos))
-            else:
-                arena.select(wpos)
-                dense_segs = store.dense.adam_segments()
-                if terms is not None:       # the head's dense gradients: the examples' rows, summed in example order by the launch
-                    dense_segs = [dict(kind=_lib.RSX_ADAM_DENSE, n=P.n, var=P.flat, m=P.m, v=P.v, g=terms, B=terms.shape[0],
-                                       stride=terms.shape[1], zero_grad=0)]
-                arena.segsum_adam(B, S, None, gy1, gy2, store.opt, dense_segs, sweep2, window=(wk, wpos))
+            dense_segs = None
+            if terms is not None:       # the head's dense gradients: the examples' rows, summed in example order by the launch
+                dense_segs = [dict(kind=_lib.RSX_ADAM_DENSE, n=P.n, var=P.flat, m=P.m, v=P.v, g=terms, B=terms.shape[0],
+                                   stride=terms.shape[1], zero_grad=0)]
+            fused_step.finish(plan, grads, dense_segs=dense_segs)
 
     return EstimatorSpec(ModeKeys.TRAIN, predictions={"prob": prob}, loss=loss if terms is not None else loss[0],
                          train_op=train_op)
