@@ -659,6 +659,51 @@ typedef struct {
 int rsx_mlp_nobn_reduce_job(const rsx_mlp_step* step_h, rsx_mlp_reduce_job* job_out);
 
 /* ---------------------------------------------------------------------------------------------
+ * Serving forward of an exported fm.py / deepfm.py model as ONE launch: ids [B, F] -> prob [B].
+ * Replaces, in PREDICT mode, deepfm/deepfm.py:85-113 (input_layer lookup, first-order one-hot matmul + bias + relu, FM term,
+ * 'dnn' = L x [tf.layers.dense(relu) -> batch_normalization -> dropout], the 1-unit layer, the logits layer, sigmoid) and
+ * fm/fm.py:117-134 (L = 0: no tower, wo has two entries).  Inference form: the reference never updates the moving statistics,
+ * so BN(x) = (gamma / sqrt(1 + bn_eps)) * x + beta, and dropout is the identity; no quantity crosses the rows of a batch.
+ *   y1 = sum over the fields f of w1_field_mask of w1[row_off[f] + ids[b, f]];  y2 = 0.5 * sum_d ((sum_f e)^2 - sum_f e^2)
+ *   x_0 = the F gathered rows side by side [F * 16];  x_{l+1} = BN_l(relu(x_l . W_l + b_l)), l < L;  u = x_L . wd + bd
+ *   z = wo[0] * relu(y1 + c0) + wo[1] * y2 (+ wo[2] * relu(u) when L > 0) + bo;  prob = 1 / (1 + exp(-z))
+ * A workgroup owns 16 examples from the ids to the probability (rows gathered into LDS as the first MFMA A operand, fp32 MFMA,
+ * activations in LDS, weights streamed from L2).  Only prob [0, B) is written: no E / S / statistics / gradient-side outputs and
+ * no workspace.  Deterministic: no atomics, and a row's bits depend on its own ids and the model only -- not on B, on its
+ * position, or on the other rows.  B need not be a multiple of 16: no id past ids[B * F) is read.
+ * Nullable: w1 (y1 = 0), c0 (no bias), gamma[l] / beta[l] together (layer l without batch-norm); wd / bd / W / b / gamma / beta /
+ * widths are not read beyond L.  tables must be 16-byte aligned (RSX_EINVAL otherwise, like NULL required pointers or B <= 0;
+ * all refusals happen before any HIP call).
+ * Envelope (rsx_predict_fm_tower_supported; RSX_EUNSUPPORTED outside, where the caller serves through the TRAIN kernels'
+ * inference form): D == 16, 1 <= F <= 64, 0 <= L <= 3, widths as ops.FusedTower.supports takes them (inner widths multiples
+ * of 4, the last at most 256), B * F < 2^31, and the tile's LDS -- the gathered rows 16 * (16 F + 4), two activation tiles
+ * 32 * (max width rounded up to 16, + 4) and the layers' partial tiles (at most 8 192 floats up to 512 columns) -- within
+ * 160 KB: every FusedTower width up to 256 at F = 64, inner widths up to ~600 at F = 39.  A layer whose width is no multiple
+ * of 4 or whose W is not 16-byte aligned is read with 4-byte loads (slower, same results).
+ * ------------------------------------------------------------------------------------------- */
+#define RSX_PREDICT_MAX_LAYERS 3
+typedef struct {
+  const float* tables;                          /* [R, D] */
+  const float* w1;                              /* nullable [R] */
+  const int32_t* row_off;                       /* [F] first row of every field (device) */
+  const float* W[RSX_PREDICT_MAX_LAYERS];       /* [K_l, widths[l]], K_0 = F * D */
+  const float* b[RSX_PREDICT_MAX_LAYERS];       /* [widths[l]] */
+  const float* gamma[RSX_PREDICT_MAX_LAYERS];   /* nullable (with beta) [widths[l]] */
+  const float* beta[RSX_PREDICT_MAX_LAYERS];
+  const float* wd;                              /* [widths[L-1]]  (dnn.Wout) */
+  const float* bd;                              /* [1] */
+  const float* c0;                              /* nullable [1]   (b1) */
+  const float* wo;                              /* [3], or [2] when L == 0  (out.W) */
+  const float* bo;                              /* [1] */
+  uint64_t w1_field_mask;
+  float bn_eps;
+  int32_t F, D, L;
+  int32_t widths[RSX_PREDICT_MAX_LAYERS];
+} rsx_predict_model;
+int rsx_predict_fm_tower_supported(int B, int F, int D, int L, const int32_t* widths);
+int rsx_predict_fm_tower(const rsx_predict_model* model_h, const int32_t* ids, float* prob, int B, rsx_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
  * DCN cross layers, dcn/dcn.py:132-142: x_{l+1} = (x_l . w_l) * x0 + x_l + b_l, all L
  * layers fused per example.  dim % 4 == 0, dim <= 1024, L <= 8.
  * ------------------------------------------------------------------------------------------- */

@@ -186,6 +186,18 @@ class SparseOptHp(C.Structure):
                 ("l2_shrinkage", C.c_float)]
 
 
+PREDICT_MAX_LAYERS = 3
+
+
+class PredictModel(C.Structure):
+    """include/rsx.h rsx_predict_model (the serving forward of an exported fm.py / deepfm.py model)."""
+    _fields_ = [("tables", C.c_void_p), ("w1", C.c_void_p), ("row_off", C.c_void_p), ("W", C.c_void_p * PREDICT_MAX_LAYERS),
+                ("b", C.c_void_p * PREDICT_MAX_LAYERS), ("gamma", C.c_void_p * PREDICT_MAX_LAYERS),
+                ("beta", C.c_void_p * PREDICT_MAX_LAYERS), ("wd", C.c_void_p), ("bd", C.c_void_p), ("c0", C.c_void_p),
+                ("wo", C.c_void_p), ("bo", C.c_void_p), ("w1_field_mask", C.c_uint64), ("bn_eps", C.c_float), ("F", C.c_int32),
+                ("D", C.c_int32), ("L", C.c_int32), ("widths", C.c_int32 * PREDICT_MAX_LAYERS)]
+
+
 ADAM_STATE_WORDS = 4 + 32 * 32        # include/rsx.h RSX_ADAM_STATE_WORDS
 
 
@@ -338,6 +350,8 @@ _SIGS = {
     "rsx_mlp_nobn_train_step": (_I, [C.POINTER(MlpStep), _P]),
     "rsx_mlp_nobn_reduce": (_I, [C.POINTER(MlpStep), _P]),
     "rsx_mlp_nobn_reduce_job": (_I, [C.POINTER(MlpStep), C.POINTER(MlpReduceJob)]),
+    "rsx_predict_fm_tower_supported": (_I, [_I, _I, _I, _I, _P]),
+    "rsx_predict_fm_tower": (_I, [C.POINTER(PredictModel), _P, _P, _I, _P]),
     "rsx_eval_metrics_state_words": (_I, [_I]),
     "rsx_eval_metrics_update": (_I, [_P, _P, _P, _I, _P, _P, _I, _P]),
 }

@@ -184,7 +184,9 @@ def define_flags(p=None):
     p.add_argument("--embedding_size", type=int, default=16)
     p.add_argument("--learning_rate", type=float, default=0.001)
     p.add_argument("--dropout", type=float, default=0.5)
-    p.add_argument("--task_type", default="train", help="{train, infer, eval}")
+    p.add_argument("--task_type", default="train", help="{train, infer, eval, export}")
+    p.add_argument("--export_path", default="./export/",
+                   help="--task_type export: the latest checkpoint of --model_dir goes to <export_path>/<unix seconds>/")
     p.add_argument("--num_epochs", type=int, default=10)
     p.add_argument("--deep_layers", default="100,100")
     p.add_argument("--train_path", default="/home/wangrc/criteo_data/train/")
@@ -253,7 +255,10 @@ def optimizer_config(FLAGS):
 
 
 def run_main(model_fn, FLAGS, make_params_fn):
-    """The `main(_)` driver shared by the Criteo scripts (fm/fm.py:173-224, deepfm/deepfm.py:153-234, ...)."""
+    """The `main(_)` driver shared by the Criteo scripts (fm/fm.py:173-224, deepfm/deepfm.py:153-234, ...).
+    --task_type export writes the serving bundle of the latest checkpoint (Estimator.export_savedmodel) and returns its
+    directory.  The reference's deepfm.py exports after EVERY task because its `main` falls through to the export lines
+    (deepfm/deepfm.py:220-234); here a model is exported only when asked."""
     optimizer, optimizer_hparams = optimizer_config(FLAGS)
     if optimizer != "adam" and FLAGS.mirror:
         # data-parallel training exists for the Adam step only (VariableStore.build refuses a data-parallel store)
@@ -300,6 +305,8 @@ def run_main(model_fn, FLAGS, make_params_fn):
             if i >= 9:
                 break
         return out
+    if FLAGS.task_type == "export":
+        return est.export_savedmodel(FLAGS.export_path)
     raise SystemExit("unknown --task_type %r" % FLAGS.task_type)
 
 

@@ -571,7 +571,9 @@ def define_flags():
     p.add_argument("--embedding_size", type=int, default=32)
     p.add_argument("--learning_rate", type=float, default=0.001)
     p.add_argument("--dropout", type=float, default=0.5)
-    p.add_argument("--task_type", default="train")
+    p.add_argument("--task_type", default="train", help="{train, infer, eval, export}")
+    p.add_argument("--export_path", default="./export/",
+                   help="--task_type export: the latest checkpoint of --model_dir goes to <export_path>/<unix seconds>/")
     p.add_argument("--num_epochs", type=int, default=5)
     p.add_argument("--deep_layers", default="100,100")        # accepted, ignored like the reference (:19,85-86)
     p.add_argument("--din_layers", default="80,40")
@@ -619,6 +621,8 @@ def main(argv=None):
         return train_and_evaluate(est, tr, ev)
     if FLAGS.task_type == "eval":
         return est.evaluate(lambda: input_fn(eval_files, FLAGS.batch_size, 1, False, FLAGS.hist_len, shard, True), steps=FLAGS.eval_steps)
+    if FLAGS.task_type == "export":     # (only when asked: the reference's deepfm.py exports after every task, its main falls through)
+        return est.export_savedmodel(FLAGS.export_path)
     return list(zip(range(10), est.predict(lambda: input_fn(eval_files, FLAGS.batch_size, 1, False, FLAGS.hist_len))))
 
 

@@ -987,6 +987,15 @@ class Estimator:
         return {"prob": np.concatenate(out) if out else np.zeros(0, np.float32)}
 
 
+    def export_savedmodel(self, export_dir_base):
+        """Estimator.export_savedmodel (deepfm/deepfm.py:220-234): the latest checkpoint of model_dir as a serving bundle
+        `<export_dir_base>/<unix seconds>/` = model.json + variables.npz (recsys_amd.serving: the variables in fp32, no
+        optimizer slots or state), written under a temporary name and renamed when complete.  -> the directory (the chief's
+        under data parallelism; None on the other ranks).  serving.Predictor.load() serves it."""
+        from . import serving
+        return serving.export_estimator(self, export_dir_base)
+
+
 class _LaunchThread:
     """Issues the staged windows of Estimator.train (ONE graph replay each) in order, on a thread of its own (opt-in,
     RSX_LAUNCH_THREAD=1): torch releases the GIL inside replay(), so the training thread fetches and stages window w + 1

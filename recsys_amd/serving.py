@@ -1,0 +1,464 @@
+"""From a trained model to a served prediction: the export bundle and its `Predictor`.
+
+The reference exports a SavedModel whose serving signature parses serialized `tf.train.Example`s and returns
+`{"prob": ...}` (deepfm/deepfm.py:220-234); deepfm/grpc_client.py sends it 200 serialized Examples per request.  Here:
+
+  bundle      `<export_dir_base>/<unix seconds>/` = `model.json` (settings only: the script, the columns, the layer sizes, the
+              batch-norm epsilon, name / shape / dtype of every tensor) + `variables.npz` (the variables in fp32: tables,
+              first-order weights, the dense arena's named tensors; no optimizer slots, no optimizer state), written under a
+              temporary name and renamed when complete (`Estimator.export_savedmodel`, `--task_type export`).
+  Predictor   loads a bundle and answers `predict_examples(list of serialized Examples)` / `predict(features)`.
+              path == "fused":  fm.py / deepfm.py bundles inside the kernel's envelope -- the variables live on the device once
+                                and a batch is ONE launch of rsx_predict_fm_tower (csrc/predict.hip), captured per request size
+                                into a HIP graph over static input buffers.
+              path == "layers": dcn.py / xdeepfm.py / din.py bundles, and fm / deepfm shapes outside the envelope -- the
+                                script's Estimator rebuilt from the manifest (model_dir=None) with the bundle's variables,
+                                answering through Estimator._infer_step (the TRAIN kernels' inference form).
+"""
+import ctypes as C
+import importlib
+import json
+import os
+import re
+import shutil
+import time
+
+import numpy as np
+
+from . import _lib
+from .feature_columns import Column, CriteoLayout
+from .layers import BN_EPS
+
+FORMAT_VERSION = 1
+SCRIPTS = ("fm", "deepfm", "xdeepfm", "dcn", "din")
+MANIFEST, VARIABLES = "model.json", "variables.npz"
+# model_fn parameters that shape the network (what a Predictor needs to rebuild it without the training flags)
+_NETWORK_PARAMS = ("embedding_size", "deep_layers", "cross_layers", "cin_bf16", "cin_split", "hist_len", "n_item", "n_cate",
+                   "tower", "force_generic")
+SIGNATURE = {"serving_default": {"inputs": "examples", "outputs": ["prob"]}}
+
+
+# ---- manifest ------------------------------------------------------------------------------------------------------------
+def _column_json(c):
+    return {"name": c.name, "key": c.key, "kind": c.kind, "rows": int(c.rows), "dimension": int(c.dimension),
+            "boundaries": None if c.boundaries is None else [float(x) for x in c.boundaries], "log_shift": float(c.log_shift)}
+
+
+def _column_from_json(d):
+    return Column(d["name"], d["key"], d["kind"], int(d["rows"]), int(d["dimension"]), d["boundaries"], float(d["log_shift"]))
+
+
+def linear_mode(linear_columns):
+    """build_feature_columns' `linear` argument that yields these linear columns ('custom' for hand-made ones)."""
+    kinds = {c.kind for c in linear_columns}
+    if kinds <= {"bucketized_indicator", "hash_indicator"}:
+        return "indicator_all"
+    if kinds == {"numeric", "hash_indicator"}:
+        return "numeric+indicator"
+    if kinds == {"numeric"}:
+        return "numeric"
+    return "custom"
+
+
+def make_manifest(script, params, global_step, tensors):
+    """The settings of one exported model.  tensors: {name: numpy array} -- only names, shapes and dtypes go in here."""
+    if script not in SCRIPTS:
+        raise _lib.RsxError("export: unknown script %r (known: %s)" % (script, ", ".join(SCRIPTS)))
+    emb = params.get("embedding_feature_columns")
+    lin = params.get("linear_feature_columns") or []
+    if script == "din":
+        feature_set = "din"
+    else:
+        if emb is None:
+            raise _lib.RsxError("export: the params of %s.py hold no embedding_feature_columns" % script)
+        feature_set = "uid_iid" if {c.key for c in emb} <= {"u_id", "i_id"} else "criteo"
+    m = {"format_version": FORMAT_VERSION, "script": script, "global_step": int(global_step), "feature_set": feature_set,
+         "linear_mode": linear_mode(lin) if script != "din" else None, "batch_norm_epsilon": BN_EPS,
+         "params": {k: params[k] for k in _NETWORK_PARAMS if k in params},
+         "embedding_columns": [_column_json(c) for c in (emb or [])],
+         "linear_columns": [_column_json(c) for c in lin],
+         "signature": SIGNATURE,
+         "tensors": [{"name": k, "shape": [int(d) for d in v.shape], "dtype": str(v.dtype)} for k, v in tensors.items()]}
+    return m
+
+
+def layout_from_manifest(manifest):
+    """The CriteoLayout (slot order, row offsets, host transform) of a bundle's embedding columns."""
+    return CriteoLayout.from_columns([_column_from_json(d) for d in manifest["embedding_columns"]])
+
+
+def params_from_manifest(manifest, max_batch_size):
+    """model_fn params that rebuild the bundle's network for inference."""
+    p = dict(manifest["params"])
+    p.update(learning_rate=0.0, dropout=0.0, max_batch_size=int(max_batch_size))
+    if manifest["script"] != "din":
+        p["embedding_feature_columns"] = [_column_from_json(d) for d in manifest["embedding_columns"]]
+        p["linear_feature_columns"] = [_column_from_json(d) for d in manifest["linear_columns"]]
+    return p
+
+
+# ---- bundle writer / reader ----------------------------------------------------------------------------------------------
+def write_bundle(export_dir_base, manifest, tensors):
+    """-> `<export_dir_base>/<unix seconds>`, holding model.json and variables.npz.  The bundle is assembled in a temporary
+    directory of the same parent and renamed when complete: a reader never sees half a bundle.  (A second export within the
+    same second takes the next free second, as tf.estimator's export does.)"""
+    base = os.path.abspath(export_dir_base)
+    os.makedirs(base, exist_ok=True)
+    for k, v in tensors.items():
+        if not isinstance(v, np.ndarray) or v.dtype.hasobject:
+            raise _lib.RsxError("export: tensor %r is not a plain numpy array" % k)
+    tmp = os.path.join(base, "temp-%d-%d" % (os.getpid(), time.monotonic_ns()))
+    os.makedirs(tmp)
+    try:
+        with open(os.path.join(tmp, VARIABLES), "wb") as f:
+            np.savez(f, **tensors)
+        with open(os.path.join(tmp, MANIFEST), "w") as f:
+            json.dump(manifest, f, indent=1, sort_keys=True)
+            f.write("\n")
+        ts = int(time.time())
+        while True:
+            final = os.path.join(base, "%d" % ts)
+            try:
+                os.rename(tmp, final)          # (fails when `final` exists and is not empty)
+                return final
+            except OSError:
+                if not os.path.exists(final):
+                    raise
+                ts += 1
+    finally:
+        if os.path.isdir(tmp):
+            shutil.rmtree(tmp, ignore_errors=True)
+
+
+def latest_bundle(path):
+    """`path` itself when it is a bundle, else its newest `<unix seconds>` child that is one."""
+    if os.path.isfile(os.path.join(path, MANIFEST)):
+        return path
+    best = None
+    if os.path.isdir(path):
+        for name in os.listdir(path):
+            if re.fullmatch(r"\d+", name) and os.path.isfile(os.path.join(path, name, MANIFEST)):
+                if best is None or int(name) > int(best):
+                    best = name
+    if best is None:
+        raise _lib.RsxError("no exported model under %r (run the script with --task_type export)" % path)
+    return os.path.join(path, best)
+
+
+def read_bundle(bundle_dir):
+    """-> (manifest, {name: numpy array}).  Refuses (RsxError naming the cause): an unknown format_version, a tensor the
+    manifest lists and the archive lacks or the reverse, a shape or dtype that disagrees with the manifest."""
+    mp = os.path.join(bundle_dir, MANIFEST)
+    try:
+        with open(mp) as f:
+            manifest = json.load(f)
+    except (OSError, ValueError) as e:
+        raise _lib.RsxError("bundle %r: cannot read %s (%s)" % (bundle_dir, MANIFEST, e)) from e
+    ver = manifest.get("format_version") if isinstance(manifest, dict) else None
+    if ver != FORMAT_VERSION:
+        raise _lib.RsxError("bundle %r: format_version %r is not supported (this reader knows %d)"
+                            % (bundle_dir, ver, FORMAT_VERSION))
+    if manifest.get("script") not in SCRIPTS:
+        raise _lib.RsxError("bundle %r: unknown script %r" % (bundle_dir, manifest.get("script")))
+    try:
+        with np.load(os.path.join(bundle_dir, VARIABLES), allow_pickle=False) as z:
+            arrays = {k: z[k] for k in z.files}
+    except (OSError, ValueError) as e:
+        raise _lib.RsxError("bundle %r: cannot read %s (%s)" % (bundle_dir, VARIABLES, e)) from e
+    listed = {t["name"]: t for t in manifest["tensors"]}
+    missing = sorted(set(listed) - set(arrays))
+    if missing:
+        raise _lib.RsxError("bundle %r: %s lacks the tensors %s listed in %s" % (bundle_dir, VARIABLES, missing, MANIFEST))
+    extra = sorted(set(arrays) - set(listed))
+    if extra:
+        raise _lib.RsxError("bundle %r: %s holds the tensors %s that %s does not list" % (bundle_dir, VARIABLES, extra, MANIFEST))
+    for k, t in listed.items():
+        if list(arrays[k].shape) != list(t["shape"]):
+            raise _lib.RsxError("bundle %r: tensor %r has shape %s, %s says %s"
+                                % (bundle_dir, k, list(arrays[k].shape), MANIFEST, list(t["shape"])))
+        if str(arrays[k].dtype) != t["dtype"]:
+            raise _lib.RsxError("bundle %r: tensor %r has dtype %s, %s says %s" % (bundle_dir, k, arrays[k].dtype, MANIFEST, t["dtype"]))
+    return manifest, arrays
+
+
+# ---- Estimator side --------------------------------------------------------------------------------------------------------
+_TABLE_ATTRS = ("tables", "w1", "table")      # what an EmbeddingArena / SparseTable holds besides optimizer slots
+
+
+def store_variables(store):
+    """{name: fp32 numpy array} of a built VariableStore: `emb.<arena>.<tables|w1|table>` and `dense.<variable>`."""
+    out = {}
+    for name, a in store.embeddings.items():
+        for attr in _TABLE_ATTRS:
+            t = getattr(a, attr, None)
+            if t is not None:
+                out["emb.%s.%s" % (name, attr)] = t.detach().float().cpu().numpy().copy()
+    for k, p in store.dense.params.items():
+        out["dense." + k] = p.detach().float().cpu().contiguous().numpy().copy()
+    return out
+
+
+def load_store_variables(store, arrays):
+    """The reverse: a bundle's tensors into a built VariableStore of the same model."""
+    import torch
+    want = set(store_variables_names(store))
+    if want != set(arrays):
+        raise _lib.RsxError("bundle and model disagree on the variables: only in the bundle %s, only in the model %s"
+                            % (sorted(set(arrays) - want), sorted(want - set(arrays))))
+    with torch.no_grad():
+        for name, a in store.embeddings.items():
+            for attr in _TABLE_ATTRS:
+                t = getattr(a, attr, None)
+                if t is not None:
+                    src = arrays["emb.%s.%s" % (name, attr)]
+                    if tuple(src.shape) != tuple(t.shape):
+                        raise _lib.RsxError("bundle tensor emb.%s.%s has shape %s, the model's is %s"
+                                            % (name, attr, tuple(src.shape), tuple(t.shape)))
+                    t.copy_(torch.from_numpy(src))
+        for k, p in store.dense.params.items():
+            src = arrays["dense." + k]
+            if tuple(src.shape) != tuple(p.shape):
+                raise _lib.RsxError("bundle tensor dense.%s has shape %s, the model's is %s" % (k, tuple(src.shape), tuple(p.shape)))
+            p.copy_(torch.from_numpy(src))
+
+
+def store_variables_names(store):
+    names = ["emb.%s.%s" % (n, attr) for n, a in store.embeddings.items() for attr in _TABLE_ATTRS
+             if getattr(a, attr, None) is not None]
+    return names + ["dense." + k for k in store.dense.params]
+
+
+def export_estimator(est, export_dir_base):
+    """Estimator.export_savedmodel's body: the latest checkpoint of est.model_dir as a bundle -> its directory."""
+    from . import checkpoint
+    script = est.model_fn.__module__.rsplit(".", 1)[-1]
+    if script not in SCRIPTS:
+        raise _lib.RsxError("export: model_fn of module %r is none of the scripts %s" % (est.model_fn.__module__, ", ".join(SCRIPTS)))
+    # With a model_dir the bundle is its latest checkpoint (restored now unless this Estimator already runs from it); an
+    # Estimator without one (model_dir=None: tests, notebooks) exports the variables it holds.
+    if est.model_dir:
+        if checkpoint.latest(est.model_dir) is None:
+            raise _lib.RsxError("export: no checkpoint in model_dir %r -- train first (--task_type train), then export"
+                                % est.model_dir)
+    elif not est.store.built:
+        raise _lib.RsxError("export: this Estimator has neither a model_dir nor variables -- nothing to export")
+    if not est.store.built:
+        _build_store(est, script)
+    est._maybe_restore()
+    est._check_consistent("export_savedmodel")
+    out = None
+    if est._is_chief():                   # replicas are bit-identical: the chief writes (the rule of _save_checkpoint)
+        tensors = store_variables(est.store)
+        out = write_bundle(export_dir_base, make_manifest(script, est.params, est.global_step, tensors), tensors)
+        print("INFO:Model exported.", flush=True)
+    if est.store.dp is not None:
+        est.store.dp.barrier()
+    return out
+
+
+def _dummy_features(script, params, layout=None):
+    """One all-zero request row: what the first model_fn call needs to create the variables."""
+    if script == "din":
+        P = int(params.get("hist_len", 100))
+        z1, zP = np.zeros(1, np.int32), np.zeros((1, P), np.int32)
+        return {"i_id": z1, "i_cate": z1.copy(), "u_iid_seq": zP, "u_icat_seq": zP.copy()}
+    f = {"ids": np.zeros((1, layout.F), np.int32)}
+    if script == "xdeepfm":
+        f["cont_log"] = np.zeros((1, 13), np.float32)
+    return f
+
+
+def _build_store(est, script):
+    """Creates the Estimator's variables (the first model_fn call does) without a batch of data."""
+    import torch
+    from .estimator import ModeKeys
+    layout = None if script == "din" else CriteoLayout.from_columns(est.params["embedding_feature_columns"])
+    with torch.no_grad():
+        est._call_model_fn(est._to_device(_dummy_features(script, est.params, layout)), None, ModeKeys.PREDICT)
+
+
+# ---- Predictor ---------------------------------------------------------------------------------------------------------------
+class Predictor:
+    """An exported model ready to answer requests.  See the module docstring for the two paths."""
+
+    MAX_GRAPHS = 32            # request sizes that get a captured graph at most (Estimator.MAX_INFER_GRAPHS' twin)
+
+    def __init__(self):
+        raise TypeError("use Predictor.load(export_dir)")
+
+    @classmethod
+    def load(cls, export_dir, device="cuda", max_batch_size=4096, use_hip_graph=True):
+        """export_dir: a bundle, or the --export_path that holds bundles (the newest is taken)."""
+        import torch
+        self = object.__new__(cls)
+        self.bundle_dir = latest_bundle(export_dir)
+        self.manifest, arrays = read_bundle(self.bundle_dir)
+        m = self.manifest
+        self.script, self.global_step = m["script"], int(m["global_step"])
+        self.signature = SIGNATURE
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise _lib.RsxError("Predictor: device %r -- there is no CPU path (the forward is HIP kernels)" % device)
+        self.max_batch_size = int(max_batch_size)
+        if self.max_batch_size < 1:
+            raise _lib.RsxError("Predictor: max_batch_size must be at least 1")
+        self.use_hip_graph = bool(use_hip_graph)
+        self.layout = None if self.script == "din" else layout_from_manifest(m)
+        self._graphs, self._n_graphs = {}, 0
+        self._est = None
+        if self.script in ("fm", "deepfm") and self._fused_setup(arrays):
+            self.path = "fused"
+        else:
+            self.path = "layers"
+            self._layers_setup(arrays)
+        return self
+
+    # -- the one-launch path ----------------------------------------------------------------------------------------------
+    def _fused_setup(self, arrays):
+        import torch
+        m, lay = self.manifest, self.layout
+        D = int(m["params"]["embedding_size"])
+        widths = [int(w) for w in str(m["params"].get("deep_layers", "")).split(",") if w] if self.script == "deepfm" else []
+        if len(widths) > _lib.PREDICT_MAX_LAYERS:
+            return False
+        wa = (C.c_int32 * _lib.PREDICT_MAX_LAYERS)(*widths)
+        if not _lib.lib().rsx_predict_fm_tower_supported(self.max_batch_size, lay.F, D, len(widths), wa):
+            return False
+        need = ["emb.input_layer.tables", "emb.input_layer.w1", "dense.b1", "dense.out.W", "dense.out.b"]
+        for l in range(len(widths)):
+            need += ["dense.dnn.%s%d" % (v, l) for v in ("W", "b", "gamma", "beta")]
+        if widths:
+            need += ["dense.dnn.Wout", "dense.dnn.bout"]
+        if set(need) != set(arrays):
+            raise _lib.RsxError("bundle %r: a %s bundle holds the tensors %s, not %s"
+                                % (self.bundle_dir, self.script, sorted(need), sorted(arrays)))
+        dev = self.device
+        # the variables, once: the tables, the first-order vector, and every dense tensor in ONE flat buffer (16-byte aligned parts)
+        self._tables = torch.from_numpy(arrays["emb.input_layer.tables"]).to(dev)
+        self._w1 = torch.from_numpy(arrays["emb.input_layer.w1"]).to(dev)
+        dense = [k for k in need if k.startswith("dense.")]
+        offs, n = {}, 0
+        for k in dense:
+            offs[k] = n
+            n = (n + arrays[k].size + 3) & ~3
+        flat = np.zeros(n, np.float32)
+        for k in dense:
+            flat[offs[k]:offs[k] + arrays[k].size] = arrays[k].reshape(-1)
+        self._dense = torch.from_numpy(flat).to(dev)
+        self._row_off = torch.from_numpy(lay.row_off[:-1].astype(np.int32)).to(dev)
+        lin_keys = {c["key"] for c in m["linear_columns"] if c["kind"].endswith("indicator")}
+        ptr = lambda k: self._dense.data_ptr() + 4 * offs[k]
+        pm = _lib.PredictModel()
+        pm.tables, pm.w1, pm.row_off = self._tables.data_ptr(), self._w1.data_ptr(), self._row_off.data_ptr()
+        for l in range(len(widths)):
+            pm.W[l], pm.b[l] = ptr("dense.dnn.W%d" % l), ptr("dense.dnn.b%d" % l)
+            pm.gamma[l], pm.beta[l] = ptr("dense.dnn.gamma%d" % l), ptr("dense.dnn.beta%d" % l)
+            pm.widths[l] = widths[l]
+        if widths:
+            pm.wd, pm.bd = ptr("dense.dnn.Wout"), ptr("dense.dnn.bout")
+        pm.c0, pm.wo, pm.bo = ptr("dense.b1"), ptr("dense.out.W"), ptr("dense.out.b")
+        pm.w1_field_mask = lay.field_mask(lin_keys)
+        pm.bn_eps = float(m["batch_norm_epsilon"])
+        pm.F, pm.D, pm.L = lay.F, D, len(widths)
+        self._model = pm
+        # request buffers: ids and prob of one chunk (the static inputs / outputs of the captured graphs are slices of them)
+        self._ids = torch.zeros(self.max_batch_size, lay.F, dtype=torch.int32, device=dev)
+        self._prob = torch.zeros(self.max_batch_size, dtype=torch.float32, device=dev)
+        return True
+
+    def _launch(self, n):
+        import torch
+        _lib.check(_lib.lib().rsx_predict_fm_tower(C.byref(self._model), self._ids.data_ptr(), self._prob.data_ptr(), int(n),
+                                                   torch.cuda.current_stream().cuda_stream), "rsx_predict_fm_tower")
+
+    def _fused_chunk(self, ids):
+        """ids: int32 [n, F] (host or device), n <= max_batch_size -> prob [n] (a view of the Predictor's output buffer,
+        valid until the next call)."""
+        import torch
+        n = int(ids.shape[0])
+        self._ids[:n].copy_(ids, non_blocking=True)
+        g = self._graphs.get(n) if self.use_hip_graph else None
+        if g is None and self.use_hip_graph and self._n_graphs < self.MAX_GRAPHS:
+            g = self._graphs[n] = {"warm": 0}
+            self._n_graphs += 1
+        if g is None:                       # graphs off, or a serving loop with ever-new request sizes: eager
+            self._launch(n)
+        elif "graph" in g:
+            g["graph"].replay()
+        elif g["warm"] < 1:                 # first request of this size: eager
+            g["warm"] += 1
+            self._launch(n)
+        else:
+            torch.cuda.synchronize()
+            graph = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(graph):
+                self._launch(n)
+            g["graph"] = graph
+            graph.replay()                  # capture executes nothing
+        return self._prob[:n]
+
+    # -- the Estimator path -----------------------------------------------------------------------------------------------
+    def _layers_setup(self, arrays):
+        import torch
+        from .estimator import Estimator, RunConfig
+        mod = importlib.import_module("recsys_amd." + self.script)
+        params = params_from_manifest(self.manifest, self.max_batch_size)
+        est = Estimator(mod.model_fn, None, params, RunConfig(use_hip_graph=self.use_hip_graph, device=str(self.device)))
+        _build_store(est, self.script)
+        load_store_variables(est.store, arrays)
+        torch.cuda.synchronize()
+        self._est = est
+
+    # -- public ------------------------------------------------------------------------------------------------------------
+    def _parse(self, serialized):
+        from . import input_pipeline as ip
+        if self.script == "din":
+            return ip.parse_din_examples(serialized, int(self.manifest["params"].get("hist_len", 100)))[0]
+        if self.manifest["feature_set"] == "uid_iid":
+            return {"ids": parse_uid_iid_examples(serialized, self.layout)}
+        return ip.parse_criteo_examples(serialized, self.layout)[0]
+
+    def predict(self, features):
+        """One parsed batch ({'ids': int32 [B, F]}, + 'cont_log' for xdeepfm.py; din.py: its four id arrays), host or device
+        -> {'prob': float32 numpy [B]}."""
+        import torch
+        from .estimator import ModeKeys
+        B = int(next(iter(features.values())).shape[0])
+        out = np.empty(B, np.float32)
+        with torch.no_grad():
+            for s in range(0, B, self.max_batch_size):
+                e = min(B, s + self.max_batch_size)
+                if self.path == "fused":
+                    ids = features["ids"][s:e]
+                    if isinstance(ids, np.ndarray):
+                        ids = torch.from_numpy(np.ascontiguousarray(ids, np.int32))
+                    prob = self._fused_chunk(ids.to(torch.int32))
+                else:
+                    part = {k: v[s:e] for k, v in features.items()}
+                    prob, _, _ = self._est._infer_step(part, None, ModeKeys.PREDICT)
+                out[s:e] = prob.reshape(-1).float().cpu().numpy()
+        return {"prob": out}
+
+    def predict_examples(self, serialized):
+        """What deepfm/grpc_client.py sends: a list of serialized tf.train.Example byte strings -> {'prob': float32 [n]}."""
+        serialized = list(serialized)
+        if not serialized:
+            return {"prob": np.zeros(0, np.float32)}
+        out = []
+        for s in range(0, len(serialized), self.max_batch_size):
+            out.append(self.predict(self._parse(serialized[s:s + self.max_batch_size]))["prob"])
+        return {"prob": np.concatenate(out)}
+
+
+def parse_uid_iid_examples(serialized, layout):
+    """deepfm/deepfm.py:28-33 AS COMMITTED applied to in-memory serialized Examples (no label needed): -> ids int32 [n, 2]."""
+    from .input_pipeline import _p, _pack_serialized
+    if not len(serialized):
+        raise ValueError("no examples")
+    buf, offs, lens = _pack_serialized(serialized)
+    n = len(serialized)
+    names = (C.c_char_p * 2)(b"u_id", b"i_id")
+    out = np.empty((2, n), np.int64)
+    _lib.check(_lib.lib().rsx_int64_features_parse_h(_p(buf), _p(offs), _p(lens), n, names, 2, _p(out), 1),
+               "rsx_int64_features_parse_h")
+    return layout.transform_int64({"u_id": out[0], "i_id": out[1]})
