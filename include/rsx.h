@@ -704,6 +704,45 @@ int rsx_predict_fm_tower_supported(int B, int F, int D, int L, const int32_t* wi
 int rsx_predict_fm_tower(const rsx_predict_model* model_h, const int32_t* ids, float* prob, int B, rsx_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Candidate ranking of an exported din.py model as ONE launch: U user histories, C candidates each -> prob [U, C].
+ * prob[u, c] is what din/din.py:83-140 gives in PREDICT mode for the example (target = (cand_item[u, c], cand_cate[u, c]),
+ * history = (hist_item[u, :], hist_cate[u, :])): the target lookups (:100-101; id 0 is an ordinary row), both `_attention`
+ * blocks with their own weights (:103-125; a position counts when its id > 0, wherever it sits; dropout off), 'mlp_layer'
+ * (:130-138), + i_item[cand_item] (:139), sigmoid.  The first attention layer is evaluated in its folded form
+ *   concat[h, q, h*q, h-q] . W0 = h . (Wh + Wm) + q . (Wq - Wm) + (h*q) . Wp,   W0 = [Wh; Wq; Wp; Wm] (K rows each)
+ * (the first term once per history position, the second once per candidate); Wh + Wm and Wq - Wm are formed inside the
+ * launch from the variables the model points at, so a reloaded model needs no further call.
+ * A workgroup owns one user and 1 .. 8 consecutive candidates; the history rows are fetched once per workgroup, positions
+ * with id <= 0 are compacted away before any matrix work.  No workspace, no atomics; only prob [0, U * C) is written.
+ * Deterministic, and a (history, candidate) pair's bits depend on its own ids and the model only: not on C, U, the
+ * candidate's position, or the other candidates and users of the call.
+ * The model points INTO the din.py store (nothing is copied): the tables of its two-field arena, the item bias as column 0
+ * of its bias_ld-wide table, the dense arena's variables; ld[l] is the stored row stride of mlp_W[l] (50 is stored as 52).
+ * RSX_EINVAL: a NULL pointer, U / C / P <= 0, K / n1 / n2 <= 0, ld[l] < widths[l], tables not 16-byte aligned.  Envelope
+ * (rsx_predict_din_rank_supported; RSX_EUNSUPPORTED outside, where the caller expands the request and serves it through the
+ * TRAIN kernels' inference form): K in {16, 32}, n1 = 80, n2 = 40, L = 3 with widths 100-50-20, 1 <= P <= 128,
+ * U * C * P < 2^31.  All refusals happen before any HIP call.
+ * ------------------------------------------------------------------------------------------- */
+typedef struct {
+  const float* item_emb;                        /* [n_item, K] */
+  const float* cate_emb;                        /* [n_cate, K] */
+  const float* item_bias;                       /* i_item[i] = item_bias[i * bias_ld] */
+  const float* att_W[2][3];                     /* [item | category history]: W0 [4 K, n1], W1 [n1, n2], W2 [n2, 1] */
+  const float* att_b[2][3];                     /* b0 [n1], b1 [n2], b2 [1] */
+  const float* mlp_W[RSX_PREDICT_MAX_LAYERS];   /* [K_l, ld[l]], K_0 = 3 K, K_l = widths[l - 1] */
+  const float* mlp_b[RSX_PREDICT_MAX_LAYERS];   /* [widths[l]] */
+  const float* mlp_wout;                        /* [widths[L - 1]] */
+  const float* mlp_bout;                        /* [1] */
+  int32_t K, n1, n2, L, bias_ld;
+  int32_t widths[RSX_PREDICT_MAX_LAYERS];
+  int32_t ld[RSX_PREDICT_MAX_LAYERS];
+} rsx_predict_din_model;
+int rsx_predict_din_rank_supported(int U, int C, int P, int K, int n1, int n2, int L, const int32_t* widths);
+int rsx_predict_din_rank(const rsx_predict_din_model* model_h, const int32_t* hist_item, const int32_t* hist_cate,
+                         const int32_t* cand_item, const int32_t* cand_cate, float* prob, int U, int C, int P,
+                         rsx_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
  * DCN cross layers, dcn/dcn.py:132-142: x_{l+1} = (x_l . w_l) * x0 + x_l + b_l, all L
  * layers fused per example.  dim % 4 == 0, dim <= 1024, L <= 8.
  * ------------------------------------------------------------------------------------------- */

@@ -198,6 +198,16 @@ class PredictModel(C.Structure):
                 ("D", C.c_int32), ("L", C.c_int32), ("widths", C.c_int32 * PREDICT_MAX_LAYERS)]
 
 
+class PredictDinModel(C.Structure):
+    """include/rsx.h rsx_predict_din_model (candidate ranking of an exported din.py model; pointers into the din.py store)."""
+    _fields_ = [("item_emb", C.c_void_p), ("cate_emb", C.c_void_p), ("item_bias", C.c_void_p),
+                ("att_W", (C.c_void_p * 3) * 2), ("att_b", (C.c_void_p * 3) * 2),
+                ("mlp_W", C.c_void_p * PREDICT_MAX_LAYERS), ("mlp_b", C.c_void_p * PREDICT_MAX_LAYERS),
+                ("mlp_wout", C.c_void_p), ("mlp_bout", C.c_void_p), ("K", C.c_int32), ("n1", C.c_int32), ("n2", C.c_int32),
+                ("L", C.c_int32), ("bias_ld", C.c_int32), ("widths", C.c_int32 * PREDICT_MAX_LAYERS),
+                ("ld", C.c_int32 * PREDICT_MAX_LAYERS)]
+
+
 ADAM_STATE_WORDS = 4 + 32 * 32        # include/rsx.h RSX_ADAM_STATE_WORDS
 
 
@@ -352,6 +362,8 @@ _SIGS = {
     "rsx_mlp_nobn_reduce_job": (_I, [C.POINTER(MlpStep), C.POINTER(MlpReduceJob)]),
     "rsx_predict_fm_tower_supported": (_I, [_I, _I, _I, _I, _P]),
     "rsx_predict_fm_tower": (_I, [C.POINTER(PredictModel), _P, _P, _I, _P]),
+    "rsx_predict_din_rank_supported": (_I, [_I] * 7 + [_P]),
+    "rsx_predict_din_rank": (_I, [C.POINTER(PredictDinModel)] + [_P] * 5 + [_I, _I, _I, _P]),
     "rsx_eval_metrics_state_words": (_I, [_I]),
     "rsx_eval_metrics_update": (_I, [_P, _P, _P, _I, _P, _P, _I, _P]),
 }

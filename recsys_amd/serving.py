@@ -14,6 +14,12 @@ The reference exports a SavedModel whose serving signature parses serialized `tf
               path == "layers": dcn.py / xdeepfm.py / din.py bundles, and fm / deepfm shapes outside the envelope -- the
                                 script's Estimator rebuilt from the manifest (model_dir=None) with the bundle's variables,
                                 answering through Estimator._infer_step (the TRAIN kernels' inference form).
+              din.py bundles also answer `rank_candidates(u_iid_seq, u_icat_seq, i_id, i_cate)`: ONE user history against C
+              candidate items (or U histories against C candidates each) -> prob [C] / [U, C].
+              rank_path == "fused":  ONE launch of rsx_predict_din_rank (csrc/predict_din.hip) over the variables where the
+                                rebuilt Estimator's store keeps them; the history is shipped and fetched once, not C times.
+              rank_path == "layers": outside that kernel's envelope -- the request expanded on the host to the training-shaped
+                                batch (`expand_rank_request`) and answered through `predict`.
 """
 import ctypes as C
 import importlib
@@ -277,6 +283,69 @@ def _build_store(est, script):
         est._call_model_fn(est._to_device(_dummy_features(script, est.params, layout)), None, ModeKeys.PREDICT)
 
 
+# ---- candidate ranking requests (din.py): pure numpy, no device ----------------------------------------------------------
+def expand_rank_request(u_iid_seq, u_icat_seq, i_id, i_cate, hist_len=None):
+    """The training-shaped batch that asks `predict` the question of `rank_candidates`: example u * C + c is (candidate c of
+    user u, user u's history).  Histories [P'] / [U, P'], candidates [C] / [U, C]; hist_len pads the histories with zeros to
+    that length.  -> {'i_id' [U * C], 'i_cate' [U * C], 'u_iid_seq' [U * C, P], 'u_icat_seq' [U * C, P]}, all int32."""
+    hi, hc = np.atleast_2d(np.asarray(u_iid_seq)), np.atleast_2d(np.asarray(u_icat_seq))
+    ci, cc = np.atleast_2d(np.asarray(i_id)), np.atleast_2d(np.asarray(i_cate))
+    U, C = ci.shape
+    if hi.shape != hc.shape or ci.shape != cc.shape or hi.shape[0] != U:
+        raise _lib.RsxError("expand_rank_request: histories %s / %s and candidates %s / %s do not describe U users"
+                            % (hi.shape, hc.shape, ci.shape, cc.shape))
+    P = hi.shape[1] if hist_len is None else int(hist_len)
+    if hi.shape[1] > P:
+        raise _lib.RsxError("expand_rank_request: a history of length %d does not fit hist_len %d" % (hi.shape[1], P))
+    out = {"i_id": ci.reshape(-1).astype(np.int32), "i_cate": cc.reshape(-1).astype(np.int32)}
+    for k, h in (("u_iid_seq", hi), ("u_icat_seq", hc)):
+        e = np.zeros((U, C, P), np.int32)
+        e[:, :, :h.shape[1]] = h[:, None, :]
+        out[k] = e.reshape(U * C, P)
+    return out
+
+
+def _is_int_array(x):
+    dt = getattr(x, "dtype", None)
+    if dt is None:
+        return False
+    if isinstance(x, np.ndarray):
+        return np.issubdtype(dt, np.integer)
+    return (not dt.is_floating_point) and (not dt.is_complex) and str(dt) != "torch.bool"
+
+
+def check_rank_request(u_iid_seq, u_icat_seq, i_id, i_cate, hist_len, n_item, n_cate):
+    """Argument checking of `Predictor.rank_candidates` (no device needed).  Accepts numpy arrays or torch tensors of any
+    integer dtype (lists become numpy).  -> (U, C, P', single): `single` when the request was one user's 1-D arrays.
+    Refuses (RsxError): non-integer inputs, shapes that are not [P'] + [C] or [U, P'] + [U, C], an empty request, a history
+    longer than the bundle's hist_len (both lengths named), and -- for HOST inputs only, device inputs are trusted as in
+    `predict` -- ids outside [0, n_item) / [0, n_cate)."""
+    arrs = []
+    for name, x in (("u_iid_seq", u_iid_seq), ("u_icat_seq", u_icat_seq), ("i_id", i_id), ("i_cate", i_cate)):
+        if not hasattr(x, "shape") or not hasattr(x, "dtype"):
+            x = np.asarray(x)
+        if not _is_int_array(x):
+            raise _lib.RsxError("rank_candidates: %s must hold integers, not %s" % (name, x.dtype))
+        arrs.append(x)
+    hi, hc, ci, cc = arrs
+    nd = len(ci.shape)
+    if nd not in (1, 2) or len(hi.shape) != nd or tuple(hi.shape) != tuple(hc.shape) or tuple(ci.shape) != tuple(cc.shape):
+        raise _lib.RsxError("rank_candidates: expected histories [P] with candidates [C], or [U, P] with [U, C]; got u_iid_seq %s, "
+                            "u_icat_seq %s, i_id %s, i_cate %s" % (tuple(hi.shape), tuple(hc.shape), tuple(ci.shape), tuple(cc.shape)))
+    U = 1 if nd == 1 else int(ci.shape[0])
+    C, Pq = int(ci.shape[-1]), int(hi.shape[-1])
+    if nd == 2 and int(hi.shape[0]) != U:
+        raise _lib.RsxError("rank_candidates: %d histories for %d rows of candidates" % (int(hi.shape[0]), U))
+    if U < 1 or C < 1:
+        raise _lib.RsxError("rank_candidates: an empty request (U = %d users, C = %d candidates)" % (U, C))
+    if Pq > int(hist_len):
+        raise _lib.RsxError("rank_candidates: a history of length %d does not fit this bundle's hist_len %d" % (Pq, int(hist_len)))
+    for name, x, hi_ in (("u_iid_seq", hi, n_item), ("u_icat_seq", hc, n_cate), ("i_id", ci, n_item), ("i_cate", cc, n_cate)):
+        if not getattr(x, "is_cuda", False) and int(np.prod(tuple(x.shape))) and (int(x.min()) < 0 or int(x.max()) >= int(hi_)):
+            raise _lib.RsxError("rank_candidates: %s holds ids outside [0, %d) (min %d, max %d)" % (name, int(hi_), int(x.min()), int(x.max())))
+    return U, C, Pq, nd == 1
+
+
 # ---- Predictor ---------------------------------------------------------------------------------------------------------------
 class Predictor:
     """An exported model ready to answer requests.  See the module docstring for the two paths."""
@@ -287,8 +356,9 @@ class Predictor:
         raise TypeError("use Predictor.load(export_dir)")
 
     @classmethod
-    def load(cls, export_dir, device="cuda", max_batch_size=4096, use_hip_graph=True):
-        """export_dir: a bundle, or the --export_path that holds bundles (the newest is taken)."""
+    def load(cls, export_dir, device="cuda", max_batch_size=4096, use_hip_graph=True, max_candidates=None):
+        """export_dir: a bundle, or the --export_path that holds bundles (the newest is taken).  max_candidates (din.py bundles;
+        default max_batch_size): the candidates per user one `rank_candidates` launch takes, longer requests are cut along C."""
         import torch
         self = object.__new__(cls)
         self.bundle_dir = latest_bundle(export_dir)
@@ -311,6 +381,13 @@ class Predictor:
         else:
             self.path = "layers"
             self._layers_setup(arrays)
+        self.max_candidates = self.max_batch_size if max_candidates is None else int(max_candidates)
+        if self.max_candidates < 1:
+            raise _lib.RsxError("Predictor: max_candidates must be at least 1")
+        self.rank_path = None
+        self._rank = None
+        if self.script == "din":
+            self.rank_path = "fused" if self._rank_supported() else "layers"
         return self
 
     # -- the one-launch path ----------------------------------------------------------------------------------------------
@@ -408,6 +485,133 @@ class Predictor:
         load_store_variables(est.store, arrays)
         torch.cuda.synchronize()
         self._est = est
+
+    # -- candidate ranking (din.py) ---------------------------------------------------------------------------------------
+    def _din_sizes(self):
+        from . import din
+        pr = self.manifest["params"]
+        return (int(pr.get("hist_len", 100)), int(pr.get("n_item", din.N_ITEM)), int(pr.get("n_cate", din.N_CATE)),
+                int(pr["embedding_size"]))
+
+    def _rank_supported(self):
+        from . import din
+        P, _, _, K = self._din_sizes()
+        wa = (C.c_int32 * _lib.PREDICT_MAX_LAYERS)(*din.MLP_LAYERS)
+        n1, n2 = din.ATTENTION_LAYERS
+        return bool(_lib.lib().rsx_predict_din_rank_supported(1, self.max_candidates, P, K, n1, n2, len(din.MLP_LAYERS), wa))
+
+    def _rank_setup(self, U):
+        """The model (pointers into the Estimator's store: nothing is copied) and the static request buffers for U users."""
+        import torch
+        from . import din
+        P, _, _, K = self._din_sizes()
+        st = self._est.store
+        r = self._rank
+        if r is None:
+            item, cate, bias = (st.embeddings[k].table for k in ("i_id", "i_cate", "i_item"))
+            pm = _lib.PredictDinModel()
+            pm.item_emb, pm.cate_emb, pm.item_bias = item.data_ptr(), cate.data_ptr(), bias.data_ptr()
+            pm.bias_ld = int(bias.stride(0))
+            for a, pre in enumerate(("att_i", "att_c")):
+                for l in range(3):
+                    pm.att_W[a][l] = st.dense["%s.W%d" % (pre, l)].data_ptr()
+                    pm.att_b[a][l] = st.dense["%s.b%d" % (pre, l)].data_ptr()
+            for l, n in enumerate(din.MLP_LAYERS):
+                pm.mlp_W[l], pm.mlp_b[l] = st.dense["mlp.W%d" % l].data_ptr(), st.dense["mlp.b%d" % l].data_ptr()
+                pm.widths[l], pm.ld[l] = n, int(st.dense.storage["mlp.W%d" % l][1])
+            pm.mlp_wout, pm.mlp_bout = st.dense["mlp.Wout"].data_ptr(), st.dense["mlp.bout"].data_ptr()
+            pm.K, pm.n1, pm.n2, pm.L = K, din.ATTENTION_LAYERS[0], din.ATTENTION_LAYERS[1], len(din.MLP_LAYERS)
+            r = self._rank = {"model": pm, "U": 0}
+        if U > r["U"]:
+            # request buffers of one chunk: the histories [U, P], the candidates and their probabilities [U, max_candidates]
+            # (a request of fewer users or candidates uses leading parts of them; graphs captured over smaller buffers go)
+            dev, i32 = self.device, torch.int32
+            for k in [k for k in self._graphs if isinstance(k, tuple) and k[0] == "rank"]:
+                del self._graphs[k]
+                self._n_graphs -= 1
+            r["hist"] = [torch.zeros(U * P, dtype=i32, device=dev) for _ in range(2)]
+            r["cand"] = [torch.zeros(U * self.max_candidates, dtype=i32, device=dev) for _ in range(2)]
+            r["prob"] = torch.zeros(U * self.max_candidates, dtype=torch.float32, device=dev)
+            r["U"] = U
+        return r
+
+    def rank_buffer_bytes(self, U=1):
+        """Bytes of the static request buffers `rank_candidates` holds for U users."""
+        P = self._din_sizes()[0]
+        return 4 * (2 * U * P + 3 * U * self.max_candidates)
+
+    def _rank_launch(self, U, n):
+        import torch
+        r, P = self._rank, self._din_sizes()[0]
+        _lib.check(_lib.lib().rsx_predict_din_rank(C.byref(r["model"]), r["hist"][0].data_ptr(), r["hist"][1].data_ptr(),
+                                                   r["cand"][0].data_ptr(), r["cand"][1].data_ptr(), r["prob"].data_ptr(),
+                                                   int(U), int(n), P, torch.cuda.current_stream().cuda_stream),
+                   "rsx_predict_din_rank")
+
+    def _rank_chunk(self, U, ci, cc):
+        """ci, cc: int32 [U, n] (host or device), n <= max_candidates; the histories are in place -> prob [U, n] (a view of
+        the output buffer, valid until the next call).  Graphs: the rule of _fused_chunk, keyed by the request shape."""
+        import torch
+        r = self._rank
+        n = int(ci.shape[1])
+        r["cand"][0][:U * n].view(U, n).copy_(ci, non_blocking=True)
+        r["cand"][1][:U * n].view(U, n).copy_(cc, non_blocking=True)
+        key = ("rank", U, n)
+        g = self._graphs.get(key) if self.use_hip_graph else None
+        if g is None and self.use_hip_graph and self._n_graphs < self.MAX_GRAPHS:
+            g = self._graphs[key] = {"warm": 0}
+            self._n_graphs += 1
+        if g is None:
+            self._rank_launch(U, n)
+        elif "graph" in g:
+            g["graph"].replay()
+        elif g["warm"] < 1:
+            g["warm"] += 1
+            self._rank_launch(U, n)
+        else:
+            torch.cuda.synchronize()
+            graph = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(graph):
+                self._rank_launch(U, n)
+            g["graph"] = graph
+            graph.replay()
+        return r["prob"][:U * n].view(U, n)
+
+    def rank_candidates(self, u_iid_seq, u_icat_seq, i_id, i_cate):
+        """din.py bundles: score C candidate items against ONE user's behaviour history -- histories [P'], candidates [C] ->
+        {'prob': float32 numpy [C]} -- or U users with C candidates each: histories [U, P'], candidates [U, C] -> prob [U, C].
+        P' <= the bundle's hist_len (shorter histories are zero padded).  numpy or torch, host or device, any integer dtype."""
+        import torch
+        if getattr(self, "script", None) != "din":
+            raise _lib.RsxError("rank_candidates: only din.py bundles rank candidates against a history; this bundle is %s.py"
+                                % getattr(self, "script", None))
+        P, n_item, n_cate, _ = self._din_sizes()
+        U, Cn, Pq, single = check_rank_request(u_iid_seq, u_icat_seq, i_id, i_cate, P, n_item, n_cate)
+        shape = (Cn,) if single else (U, Cn)
+        if self.rank_path != "fused":
+            host = [x.detach().cpu().numpy() if isinstance(x, torch.Tensor) else np.asarray(x)
+                    for x in (u_iid_seq, u_icat_seq, i_id, i_cate)]
+            return {"prob": self.predict(expand_rank_request(*host, hist_len=P))["prob"].reshape(shape)}
+
+        def dev32(x, rows):
+            if isinstance(x, torch.Tensor):
+                return x.reshape(rows, -1).to(torch.int32)
+            return torch.from_numpy(np.ascontiguousarray(np.asarray(x).reshape(rows, -1), np.int32))
+
+        out = np.empty((U, Cn), np.float32)
+        with torch.no_grad():
+            r = self._rank_setup(U)
+            for buf, x in zip(r["hist"], (u_iid_seq, u_icat_seq)):
+                hv = buf[:U * P].view(U, P)
+                if Pq:
+                    hv[:, :Pq].copy_(dev32(x, U), non_blocking=True)
+                if Pq < P:
+                    hv[:, Pq:].zero_()
+            ci, cc = dev32(i_id, U), dev32(i_cate, U)
+            for s in range(0, Cn, self.max_candidates):
+                e = min(Cn, s + self.max_candidates)
+                out[:, s:e] = self._rank_chunk(U, ci[:, s:e], cc[:, s:e]).cpu().numpy()
+        return {"prob": out.reshape(shape)}
 
     # -- public ------------------------------------------------------------------------------------------------------------
     def _parse(self, serialized):

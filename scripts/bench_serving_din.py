@@ -1,0 +1,211 @@
+"""Time per candidate-ranking request of an exported din.py model at the reference's sizes (K = 32, hist_len = 100, 63 002
+items, 802 categories, histories of synthetic.din_batch): ONE user history against C candidates, on the two ways the package
+can answer it, in ONE process, their timed regions alternating, `--repeats` rounds per C; medians and the spread are reported.
+
+  A  what a caller had before `rank_candidates`: serving.expand_rank_request on the host (the history copied C times) and
+     Predictor.predict on the `layers` path with HIP graphs on -- five row lookups, attention and pooling forward twice
+     each, the concat, three tower-forward launches and the head, captured as one graph per request size.
+  B  Predictor.rank_candidates: the captured graph of ONE rsx_predict_din_rank launch (csrc/predict_din.hip).
+
+    python scripts/bench_serving_din.py [--sizes 1,16,200,1000,4096] [--replays 2000] [--repeats 3]
+        device time per request: hipEvents around graph replays over resident inputs (every C of both contenders warmed up
+        and captured before any timing; the replay count is cut for the slow sizes so that a timed region stays ~0.5 s);
+        wall time per request: host arrays in, host probabilities out (A: expansion + copies + graph; B: copies + graph),
+        around a synchronise.
+    rocprofv3 --kernel-trace --stats --output-format csv -d DIR -o NAME -- python scripts/bench_serving_din.py --profile-run 200
+        eager requests of both paths for a kernel trace of its own (no timing printed);
+    python scripts/bench_serving_din.py --kernel-stats DIR/.../NAME_kernel_stats.csv --profile-run 200
+        the kernel's time against the sum of A's kernels per request (every other kernel the trace holds at least once per
+        request, the runtime's buffer copies left out), and its achieved FLOP/s against the fp32 MFMA peak.
+
+FLOPs of a request, from shapes: 2 x C x valid positions x (K x 80 + 80 x 40 + 40) per attention (the folded first layer), both
+attentions; the user-side and candidate-side terms and the tower are not counted."""
+import argparse
+import csv
+import json
+import os
+import sys
+import tempfile
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+B_KERNEL = "predict_din_rank_k"
+K, P = 32, 100
+PEAK_F32_MFMA = 157.3e12                         # 256 CUs x 4 SIMDs x 64 FLOP/clk x 2.4 GHz (v_mfma_f32_16x16x4_f32)
+
+
+def build(dev, max_c, export_dir):
+    """-> Predictor of a din.py bundle at the reference's sizes (both contenders answer from its variables)."""
+    import torch
+    from recsys_amd import din, serving
+    from recsys_amd.estimator import Estimator, ModeKeys, RunConfig
+    params = {"embedding_size": K, "learning_rate": 1e-3, "dropout": 0.5, "max_batch_size": 64, "hist_len": P}
+    est = Estimator(din.model_fn, None, params, RunConfig(device=str(dev), seed=1234))
+    z1, zP = torch.zeros(1, dtype=torch.int32, device=dev), torch.zeros(1, P, dtype=torch.int32, device=dev)
+    with torch.no_grad():
+        est._call_model_fn({"i_id": z1, "i_cate": z1.clone(), "u_iid_seq": zP, "u_icat_seq": zP.clone()}, None, ModeKeys.PREDICT)
+        g = torch.Generator(device="cpu").manual_seed(7)          # a served model is a trained one: no all-zero biases
+        for k, p in est.store.dense.params.items():
+            if k.split(".")[-1][0] == "b":
+                p.add_((torch.rand(p.shape, generator=g) * 0.2 - 0.1).to(dev))
+        est.store.embeddings["i_item"].table[:, 0].add_((torch.randn(din.N_ITEM, generator=g) * 0.3).to(dev))
+    d = est.export_savedmodel(export_dir)
+    del est
+    pred = serving.Predictor.load(d, device=str(dev), max_batch_size=max_c, max_candidates=max_c)
+    assert pred.path == "layers" and pred.rank_path == "fused", (pred.path, pred.rank_path)
+    torch.cuda.synchronize()
+    return pred
+
+
+def request(C, seed):
+    """One user's history (synthetic.din_batch: ragged, zero padded to P) and C candidates."""
+    from recsys_amd import synthetic
+    rng = np.random.default_rng(seed)
+    h = synthetic.din_batch(rng, 1, P)
+    c = synthetic.din_batch(rng, C, 1)
+    return (h["u_iid_seq"][0].astype(np.int32), h["u_icat_seq"][0].astype(np.int32), c["i_id"].astype(np.int32),
+            c["i_cate"].astype(np.int32))
+
+
+def answer_a(pred, req):
+    from recsys_amd import serving
+    return pred.predict(serving.expand_rank_request(*req, hist_len=P))["prob"]
+
+
+def answer_b(pred, req):
+    return pred.rank_candidates(*req)["prob"]
+
+
+def capture_both(pred, req):
+    """Warm up and capture the request size on both paths -> (A's graph, B's graph, max |A - B|)."""
+    C = len(req[2])
+    for _ in range(3):                           # eager warm-up, capture + replay, replay
+        pa, pb = answer_a(pred, req), answer_b(pred, req)
+    err = float(np.abs(pa - pb).max())
+    assert err <= 2e-5, (C, err)                 # (faster and different is not faster)
+    ga = [g for k, g in pred._est._graphs.items() if k[0] == "infer" and "graph" in g
+          and g["static"].views()[0]["i_id"].shape[0] == C]
+    assert len(ga) == 1 and "graph" in pred._graphs[("rank", 1, C)]
+    return ga[0]["graph"], pred._graphs[("rank", 1, C)]["graph"], err
+
+
+def time_replays(graph, n):
+    import torch
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    torch.cuda.synchronize()
+    e0.record()
+    for _ in range(n):
+        graph.replay()
+    e1.record()
+    e1.synchronize()
+    return e0.elapsed_time(e1) * 1e3 / n          # us per request
+
+
+def time_wall(fn, pred, req, n):
+    import torch
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for _ in range(n):
+        fn(pred, req)                             # (ends in a device-to-host copy of prob: synchronises)
+    torch.cuda.synchronize()
+    return (time.perf_counter() - t0) / n * 1e6
+
+
+def flops(C, valid):
+    return 2 * 2 * C * valid * (K * 80 + 80 * 40 + 40)
+
+
+def kernel_stats(path):
+    rows = {}
+    with open(path) as f:
+        for row in csv.DictReader(f):
+            rows[row["Name"]] = (int(row["Calls"]), float(row["TotalDurationNs"]), float(row["AverageNs"]))
+    return rows
+
+
+def main():
+    import torch
+    p = argparse.ArgumentParser()
+    p.add_argument("--sizes", default="1,16,200,1000,4096")
+    p.add_argument("--replays", type=int, default=2000)
+    p.add_argument("--repeats", type=int, default=3)
+    p.add_argument("--wall_calls", type=int, default=200)
+    p.add_argument("--profile-run", dest="profile_run", type=int, default=0, help="C of a rocprofv3 run")
+    p.add_argument("--profile-requests", dest="profile_requests", type=int, default=200)
+    p.add_argument("--kernel-stats", dest="kernel_stats", default=None)
+    a = p.parse_args()
+    if a.kernel_stats:                            # no GPU needed: the trace's own numbers
+        C, n = a.profile_run, a.profile_requests
+        st = kernel_stats(a.kernel_stats)
+        b = [(c, t, avg) for name, (c, t, avg) in st.items() if B_KERNEL in name]
+        # A's kernels: everything else the trace holds at least once per request (the Estimator's and the Predictor's variable
+        # set-up add one or two calls each: per request = calls // requests, at the kernel's average time); the runtime's
+        # buffer copies serve both contenders and are left out
+        a_k = {name: (c // n, c // n * avg) for name, (c, t, avg) in st.items()
+               if B_KERNEL not in name and "copyBuffer" not in name and c >= n}
+        req = request(C, 100 + C)
+        valid = int((req[0] > 0).sum())
+        fl = flops(C, valid)
+        rec = {"candidates": C, "A_kernels_per_request": sum(c for c, _ in a_k.values()),
+               "A_kernel_us_per_request": round(sum(t for _, t in a_k.values()) / 1e3, 3),
+               "B_kernel_us_per_request": round(b[0][2] / 1e3, 3), "B_calls": b[0][0], "valid_positions": valid,
+               "request_flops": fl, "B_achieved_TFLOPs": round(fl / b[0][2] / 1e3, 3),
+               "B_share_of_fp32_mfma_peak": round(fl / (b[0][2] * 1e-9) / PEAK_F32_MFMA, 4),
+               "A_kernels": {name[:48]: c for name, (c, _) in sorted(a_k.items())}}
+        print(json.dumps(rec), flush=True)
+        return rec
+    from recsys_amd import build as _b
+    _b.build(verbose=False)
+    dev = torch.device("cuda")
+    sizes = [int(s) for s in a.sizes.split(",")] if not a.profile_run else [a.profile_run]
+    with tempfile.TemporaryDirectory() as tmp:
+        pred = build(dev, max(sizes), os.path.join(tmp, "export"))
+    if a.profile_run:
+        pred.use_hip_graph = pred._est.config.use_hip_graph = False     # eager: every launch appears in the trace under its name
+        req = request(a.profile_run, 100 + a.profile_run)
+        for _ in range(a.profile_requests):
+            answer_a(pred, req)
+        for _ in range(a.profile_requests):
+            answer_b(pred, req)
+        torch.cuda.synchronize()
+        return None
+    out = []
+    reqs = {C: request(C, 100 + C) for C in sizes}
+    graphs = {C: capture_both(pred, reqs[C]) for C in sizes}            # every size, before any timing
+    for C in sizes:
+        ga, gb, err = graphs[C]
+        na = max(20, min(a.replays, int(5e5 / max(time_replays(ga, 20), 1.0))))
+        nb = max(20, min(a.replays, int(5e5 / max(time_replays(gb, 20), 1.0))))
+        ta, tb, wa, wb = [], [], [], []
+        for _ in range(a.repeats):                 # the contenders alternate within every round
+            ta.append(time_replays(ga, na))
+            tb.append(time_replays(gb, nb))
+        nw = max(10, min(a.wall_calls, na))
+        for fn in (answer_a, answer_b):
+            time_wall(fn, pred, reqs[C], 5)
+        for _ in range(a.repeats):
+            wa.append(time_wall(answer_a, pred, reqs[C], nw))
+            wb.append(time_wall(answer_b, pred, reqs[C], nw))
+        med = lambda x: float(np.median(x))
+        spread = lambda x: max(x) - min(x)
+        valid = int((reqs[C][0] > 0).sum())
+        rec = {"candidates": C, "valid_positions": valid,
+               "A_device_us": round(med(ta), 3), "B_device_us": round(med(tb), 3), "device_B_over_A": round(med(tb) / med(ta), 4),
+               "A_device_repeats_us": [round(x, 3) for x in ta], "B_device_repeats_us": [round(x, 3) for x in tb],
+               "device_accepted": bool(med(ta) - med(tb) > max(spread(ta), spread(tb))),
+               "A_wall_us": round(med(wa), 1), "B_wall_us": round(med(wb), 1), "wall_B_over_A": round(med(wb) / med(wa), 4),
+               "A_wall_repeats_us": [round(x, 1) for x in wa], "B_wall_repeats_us": [round(x, 1) for x in wb],
+               "wall_accepted": bool(med(wa) - med(wb) > max(spread(wa), spread(wb))),
+               "max_abs_prob_diff": err, "replays": [na, nb], "wall_calls": nw, "request_flops": flops(C, valid),
+               "B_TFLOPs_at_device_time": round(flops(C, valid) / med(tb) / 1e6, 3)}
+        out.append(rec)
+        print(json.dumps(rec), flush=True)
+    return out
+
+
+if __name__ == "__main__":
+    main()
