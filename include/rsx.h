@@ -704,6 +704,46 @@ int rsx_predict_fm_tower_supported(int B, int F, int D, int L, const int32_t* wi
 int rsx_predict_fm_tower(const rsx_predict_model* model_h, const int32_t* ids, float* prob, int B, rsx_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Serving forward of an exported dcn.py model as ONE launch: ids [B, F] -> prob [B].
+ * Replaces, in PREDICT mode, dcn/dcn.py:123-153: the input_layer lookup x_0 [F * 16]; Lc cross layers
+ *   x_{l+1} = (x_l . cross_W[l]) * x_0 + x_l + cross_b[l];
+ * the tower over x_0, h_{l+1} = BN_l(relu(h_l . W_l + b_l)), l < L, in the inference form of rsx_predict_fm_tower (no 1-unit
+ * layer on top);  z = h_L . wo[0 : widths[L-1]] + x_Lc . wo[widths[L-1] : widths[L-1] + 16 F] + bo;  prob = 1 / (1 + exp(-z)).
+ * dcn.py has no first-order term and no FM term.
+ * A workgroup owns 16 examples from the ids to the probability, as in rsx_predict_fm_tower; the cross layers run on the
+ * registers of the gather threads (the 32 threads of an example sum their partial dot products with a fixed butterfly).
+ * Only prob [0, B) is written: no workspace, no atomics, no allocation, no sync.  Deterministic, and a row's bits depend on its
+ * own ids and the model only -- not on B, on its position, or on the other rows.  B need not be a multiple of 16: no id past
+ * ids[B * F) is read.
+ * Nullable: gamma[l] / beta[l] together (layer l without batch-norm); W / b / gamma / beta / widths are not read beyond L.
+ * RSX_EINVAL (before any HIP call): a NULL model / ids / prob / tables / row_off / cross_W / cross_b / wo / bo / W[l] / b[l],
+ * B <= 0, gamma[l] without beta[l] or the reverse, a bn_eps that is negative or not finite, tables / cross_W / cross_b not
+ * 16-byte aligned (they are read as float4).  wo needs 4-byte alignment only: its cross part starts at widths[L-1] floats and is
+ * read with 4-byte loads when that address is not 16-byte aligned.
+ * Envelope (rsx_predict_dcn_supported; RSX_EUNSUPPORTED outside, where the caller serves through the TRAIN kernels' inference
+ * form): D == 16, 1 <= F <= 64, 1 <= L <= RSX_PREDICT_MAX_LAYERS with the width rules of rsx_predict_fm_tower (inner widths
+ * multiples of 4, the last at most 256), 1 <= Lc <= 8 (the cross kernels' limit), B * F < 2^31, and the LDS budget of
+ * rsx_predict_fm_tower: 16 * (16 F + 4) + 32 * (max width rounded up to 16, + 4) + the partial tiles + 32 floats within 160 KB.
+ * ------------------------------------------------------------------------------------------- */
+typedef struct {
+  const float* tables;                          /* [R, D] */
+  const int32_t* row_off;                       /* [F] first row of every field (device) */
+  const float* cross_W;                         /* [Lc, 16 F] */
+  const float* cross_b;                         /* [Lc, 16 F] */
+  const float* W[RSX_PREDICT_MAX_LAYERS];       /* [K_l, widths[l]], K_0 = F * D */
+  const float* b[RSX_PREDICT_MAX_LAYERS];       /* [widths[l]] */
+  const float* gamma[RSX_PREDICT_MAX_LAYERS];   /* nullable (with beta) [widths[l]] */
+  const float* beta[RSX_PREDICT_MAX_LAYERS];
+  const float* wo;                              /* [widths[L-1] + 16 F]: the tower's part first  (out.W) */
+  const float* bo;                              /* [1] */
+  float bn_eps;
+  int32_t F, D, L, Lc;
+  int32_t widths[RSX_PREDICT_MAX_LAYERS];
+} rsx_predict_dcn_model;
+int rsx_predict_dcn_supported(int B, int F, int D, int L, const int32_t* widths, int Lc);
+int rsx_predict_dcn(const rsx_predict_dcn_model* model_h, const int32_t* ids, float* prob, int B, rsx_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Candidate ranking of an exported din.py model as ONE launch: U user histories, C candidates each -> prob [U, C].
  * prob[u, c] is what din/din.py:83-140 gives in PREDICT mode for the example (target = (cand_item[u, c], cand_cate[u, c]),
  * history = (hist_item[u, :], hist_cate[u, :])): the target lookups (:100-101; id 0 is an ordinary row), both `_attention`

@@ -198,6 +198,15 @@ class PredictModel(C.Structure):
                 ("D", C.c_int32), ("L", C.c_int32), ("widths", C.c_int32 * PREDICT_MAX_LAYERS)]
 
 
+class PredictDcnModel(C.Structure):
+    """include/rsx.h rsx_predict_dcn_model (the serving forward of an exported dcn.py model)."""
+    _fields_ = [("tables", C.c_void_p), ("row_off", C.c_void_p), ("cross_W", C.c_void_p), ("cross_b", C.c_void_p),
+                ("W", C.c_void_p * PREDICT_MAX_LAYERS), ("b", C.c_void_p * PREDICT_MAX_LAYERS),
+                ("gamma", C.c_void_p * PREDICT_MAX_LAYERS), ("beta", C.c_void_p * PREDICT_MAX_LAYERS),
+                ("wo", C.c_void_p), ("bo", C.c_void_p), ("bn_eps", C.c_float), ("F", C.c_int32), ("D", C.c_int32),
+                ("L", C.c_int32), ("Lc", C.c_int32), ("widths", C.c_int32 * PREDICT_MAX_LAYERS)]
+
+
 class PredictDinModel(C.Structure):
     """include/rsx.h rsx_predict_din_model (candidate ranking of an exported din.py model; pointers into the din.py store)."""
     _fields_ = [("item_emb", C.c_void_p), ("cate_emb", C.c_void_p), ("item_bias", C.c_void_p),
@@ -362,6 +371,8 @@ _SIGS = {
     "rsx_mlp_nobn_reduce_job": (_I, [C.POINTER(MlpStep), C.POINTER(MlpReduceJob)]),
     "rsx_predict_fm_tower_supported": (_I, [_I, _I, _I, _I, _P]),
     "rsx_predict_fm_tower": (_I, [C.POINTER(PredictModel), _P, _P, _I, _P]),
+    "rsx_predict_dcn_supported": (_I, [_I, _I, _I, _I, _P, _I]),
+    "rsx_predict_dcn": (_I, [C.POINTER(PredictDcnModel), _P, _P, _I, _P]),
     "rsx_predict_din_rank_supported": (_I, [_I] * 7 + [_P]),
     "rsx_predict_din_rank": (_I, [C.POINTER(PredictDinModel)] + [_P] * 5 + [_I, _I, _I, _P]),
     "rsx_eval_metrics_state_words": (_I, [_I]),

@@ -21,130 +21,9 @@
 // of lane i, k = 16 ks + 4 kq + t over the four MFMAs t of k-step ks (tower.hip's convention); the accumulator holds rows
 // 4 kq + r.  The 4 tiles of a group are 4 independent chains (a dependent 16x16x4 fp32 MFMA waits ~32 cycles).
 #include "rsx_common.h"
+#include "predict_device.h"
 
 namespace {
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ f32x4 mfma16(float a, float b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
-
-constexpr int PR_T = 512, PR_NW = PR_T / 64;   // threads / waves per workgroup
-constexpr int PR_ROWS = 16;                    // examples per workgroup
-constexpr int PR_GF = 8;                       // fields per gather thread: 64 fields / 8 field lanes
-constexpr int PR_MAX_LDS = 160 * 1024;
-
-struct PredictArgs {
-  const float* tables; const float* w1; const int32_t* row_off; const int32_t* ids;
-  const float* W[RSX_PREDICT_MAX_LAYERS]; const float* b[RSX_PREDICT_MAX_LAYERS];
-  const float* gamma[RSX_PREDICT_MAX_LAYERS]; const float* beta[RSX_PREDICT_MAX_LAYERS];
-  const float* wd; const float* bd; const float* c0; const float* wo; const float* bo;
-  float* prob;
-  uint64_t w1_mask;
-  float bn_rstd;                               // 1 / sqrt(1 + eps)
-  int B, F, L;
-  int N[RSX_PREDICT_MAX_LAYERS];
-  int ksplit[RSX_PREDICT_MAX_LAYERS];          // K-splits of a layer: its column groups x ksplit work units go round the 8 waves
-  int ldx, lda;                                // row strides of the gathered tile and of the activation tiles (floats, == 4 mod 8)
-  int oA0, oA1, oP, oY;                        // LDS offsets (floats): activation tiles, partial tiles, y1 | y2 [2][16]
-};
-
-// B operands of one k-step for a column group: b[t] = W[16 ks + 4 kq + t][c0 .. c0 + 3].  Rows past K are clamped to K - 1 (the A
-// operand is zero there), columns past N to a valid address (their outputs are dropped).  VEC: N % 4 == 0 and W 16-byte aligned.
-template <bool VEC>
-__device__ __forceinline__ void load_b(f32x4 (&b)[4], const float* __restrict__ W, const int ks, const int K, const uint32_t N,
-                                       const int kq, const uint32_t c0) {
-#pragma unroll
-  for (int t = 0; t < 4; ++t) {
-    const int k = 16 * ks + 4 * kq + t;
-    const uint32_t o = (uint32_t)(k < K ? k : K - 1) * N;
-    if (VEC) {
-      b[t] = *reinterpret_cast<const f32x4*>(W + (o + c0));
-    } else {
-#pragma unroll
-      for (int c = 0; c < 4; ++c) b[t][c] = W[o + (c0 + c < N ? c0 + c : N - 1)];
-    }
-  }
-}
-
-__device__ __forceinline__ void mfma_step(f32x4 (&acc)[4], const float4 a, const f32x4 (&b)[4]) {
-#pragma unroll
-  for (int t = 0; t < 4; ++t) acc[t] = mfma16(a.x, b[0][t], acc[t]);
-#pragma unroll
-  for (int t = 0; t < 4; ++t) acc[t] = mfma16(a.y, b[1][t], acc[t]);
-#pragma unroll
-  for (int t = 0; t < 4; ++t) acc[t] = mfma16(a.z, b[2][t], acc[t]);
-#pragma unroll
-  for (int t = 0; t < 4; ++t) acc[t] = mfma16(a.w, b[3][t], acc[t]);
-}
-
-// part [ksplit][16][PW] <- the partial products in [16][ldi] . W [K][N] of this wave's (column group, K-split) units.  The B
-// operands run one k-step ahead of the MFMAs (deeper prefetch and loading a layer's first operands ahead of the work that
-// produces its input were measured and changed nothing or lost 1-2 us to their extra instructions: DESIGN.md).
-template <bool VEC>
-__device__ __forceinline__ void layer_mfma(const float* __restrict__ in, const int ldi, const int K, const float* __restrict__ W,
-                                           const int N, const int ksplit, float* __restrict__ part, const int w, const int lane) {
-  const int i = lane & 15, kq = lane >> 4;
-  const int nks = (K + 15) >> 4, ng = (N + 63) >> 6, PW = ng * 64;
-  const float* arow = in + i * ldi + 4 * kq;
-  for (int u = w; u < ng * ksplit; u += PR_NW) {          // (wave-uniform)
-    const int g = u % ng, sp = u / ng;
-    const int ks_lo = sp * nks / ksplit, ks_hi = (sp + 1) * nks / ksplit;
-    const uint32_t col = (uint32_t)(g * 64 + 4 * i);
-    const uint32_t c0 = col < (uint32_t)N ? col : 0u;
-    f32x4 acc[4];
-#pragma unroll
-    for (int t = 0; t < 4; ++t) acc[t] = f32x4{0.f, 0.f, 0.f, 0.f};
-    f32x4 bc[4], bn[4];
-    if (ks_lo < ks_hi) load_b<VEC>(bc, W, ks_lo, K, (uint32_t)N, kq, c0);
-    for (int ks = ks_lo; ks < ks_hi; ++ks) {
-      const bool more = ks + 1 < ks_hi;
-      if (more) load_b<VEC>(bn, W, ks + 1, K, (uint32_t)N, kq, c0);      // (in flight under this k-step's 16 MFMAs)
-      const float4 a = *reinterpret_cast<const float4*>(arow + 16 * ks);
-      mfma_step(acc, a, bc);
-      if (more) {
-#pragma unroll
-        for (int t = 0; t < 4; ++t) bc[t] = bn[t];
-      }
-    }
-    float* pr = part + (sp * 16 + 4 * kq) * PW + g * 64 + 4 * i;
-#pragma unroll
-    for (int r = 0; r < 4; ++r) *reinterpret_cast<f32x4*>(pr + r * PW) = f32x4{acc[0][r], acc[1][r], acc[2][r], acc[3][r]};
-  }
-}
-
-// out [16][ldo] = gamma' * relu(sum of the partial tiles in split order + bias) + beta; the columns N .. up16(N) become zeros
-// (the next layer's last k-step reads them).  Thread = (row, float4 column).
-__device__ __forceinline__ void layer_epilogue(const float* __restrict__ part, const int ksplit, const int N,
-                                               const float* __restrict__ bias, const float* __restrict__ gamma,
-                                               const float* __restrict__ beta, const float rstd, float* __restrict__ out,
-                                               const int ldo, const int tid) {
-  const int PW = ((N + 63) >> 6) * 64, NP = (N + 15) & ~15;
-  const int row = tid >> 5;
-  for (int c = 4 * (tid & 31); c < NP; c += 128) {
-    f32x4 v = *reinterpret_cast<const f32x4*>(part + row * PW + c);
-    for (int sp = 1; sp < ksplit; ++sp) v += *reinterpret_cast<const f32x4*>(part + (sp * 16 + row) * PW + c);
-    f32x4 o;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      const int col = c + e, cc = col < N ? col : N - 1;
-      const float a = fmaxf(v[e] + bias[cc], 0.f);
-      const float inv = gamma != nullptr ? rstd * gamma[cc] : 1.f;     // oracle / TF order: (rstd * gamma) * x + beta
-      const float sh = beta != nullptr ? beta[cc] : 0.f;
-      o[e] = col < N ? a * inv + sh : 0.f;
-    }
-    *reinterpret_cast<f32x4*>(out + row * ldo + c) = o;
-  }
-}
-
-__device__ __forceinline__ void dense_bn_layer(const float* in, const int ldi, const int K, const float* W, const float* bias,
-                                               const float* gamma, const float* beta, const float rstd, const int N,
-                                               const int ksplit, float* part, float* out, const int ldo, const int tid) {
-  const int w = tid >> 6, lane = tid & 63;
-  if ((N & 3) == 0 && (reinterpret_cast<uintptr_t>(W) & 15u) == 0) layer_mfma<true>(in, ldi, K, W, N, ksplit, part, w, lane);
-  else layer_mfma<false>(in, ldi, K, W, N, ksplit, part, w, lane);
-  __syncthreads();
-  layer_epilogue(part, ksplit, N, bias, gamma, beta, rstd, out, ldo, tid);
-  __syncthreads();
-}
-
 __global__ __launch_bounds__(PR_T) void predict_fm_tower_k(const PredictArgs p) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
   const int tid = threadIdx.x;
@@ -235,47 +114,6 @@ __global__ __launch_bounds__(PR_T) void predict_fm_tower_k(const PredictArgs p) 
     if (d == 0 && row0 + r < p.B) p.prob[row0 + r] = 1.f / (1.f + expf(-z));
   }
 }
-
-inline int up16(int x) { return (x + 15) & ~15; }
-
-// LDS floats of a launch, or -1 outside the envelope.
-long long predict_lds_floats(int B, int F, int D, int L, const int32_t* widths, PredictArgs* p) {
-  if (D != 16 || F < 1 || F > 64 || L < 0 || L > RSX_PREDICT_MAX_LAYERS || B < 1) return -1;
-  if ((long long)B * F >= (1ll << 31)) return -1;
-  if (L > 0 && widths == nullptr) return -1;
-  int wmax = 0;
-  for (int l = 0; l < L; ++l) {
-    const int n = widths[l];
-    if (n < 1 || n > (1 << 20)) return -1;
-    if (l + 1 < L && (n & 3)) return -1;                 // FusedTower.supports: the inner widths are multiples of 4,
-    if (l + 1 == L && n > 256) return -1;                // the last one at most 256
-    wmax = n > wmax ? n : wmax;
-  }
-  const int ldx = 16 * F + 4, lda = L > 0 ? up16(wmax) + 4 : 0;
-  // partial tiles: [ksplit][16][64 * groups] of the layer that needs most; ksplit = the waves its column groups leave free
-  int pmax = 0, K = 16 * F;
-  for (int l = 0; l < L; ++l) {
-    const int ng = (widths[l] + 63) / 64, nks = (K + 15) / 16;
-    int ksp = ng >= PR_NW ? 1 : PR_NW / ng;
-    ksp = ksp > nks ? nks : ksp;
-    if (p) p->ksplit[l] = ksp;
-    pmax = ksp * 16 * 64 * ng > pmax ? ksp * 16 * 64 * ng : pmax;
-    K = widths[l];
-  }
-  const long long fl = 16ll * ldx + 2ll * 16 * lda + pmax + 32;
-  if (fl * (long long)sizeof(float) > PR_MAX_LDS) return -1;
-  if (p) {
-    p->ldx = ldx;
-    p->lda = lda;
-    p->oA0 = 16 * ldx;
-    p->oA1 = p->oA0 + 16 * lda;
-    p->oP = p->oA1 + 16 * lda;
-    p->oY = p->oP + pmax;
-  }
-  return fl;
-}
-
-inline bool al16(const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15u) == 0; }
 
 }  // namespace
 

@@ -11,9 +11,13 @@ The reference exports a SavedModel whose serving signature parses serialized `tf
               path == "fused":  fm.py / deepfm.py bundles inside the kernel's envelope -- the variables live on the device once
                                 and a batch is ONE launch of rsx_predict_fm_tower (csrc/predict.hip), captured per request size
                                 into a HIP graph over static input buffers.
-              path == "layers": dcn.py / xdeepfm.py / din.py bundles, and fm / deepfm shapes outside the envelope -- the
-                                script's Estimator rebuilt from the manifest (model_dir=None) with the bundle's variables,
-                                answering through Estimator._infer_step (the TRAIN kernels' inference form).
+                                dcn.py bundles loaded with `Predictor.load(..., one_launch=True)` inside rsx_predict_dcn's
+                                envelope (csrc/predict_dcn.hip) -- the same buffers, graphs and chunking, ONE launch of that
+                                kernel per batch.  Opt-in: it agrees with the Estimator to 2e-5, not bit for bit.
+              path == "layers": dcn.py (the default) / xdeepfm.py / din.py bundles, and fm / deepfm / dcn shapes outside the
+                                envelope -- the script's Estimator rebuilt from the manifest (model_dir=None) with the
+                                bundle's variables, answering through Estimator._infer_step (the TRAIN kernels' inference
+                                form), bit-identical to the Estimator the bundle came from.
               din.py bundles also answer `rank_candidates(u_iid_seq, u_icat_seq, i_id, i_cate)`: ONE user history against C
               candidate items (or U histories against C candidates each) -> prob [C] / [U, C].
               rank_path == "fused":  ONE launch of rsx_predict_din_rank (csrc/predict_din.hip) over the variables where the
@@ -356,9 +360,12 @@ class Predictor:
         raise TypeError("use Predictor.load(export_dir)")
 
     @classmethod
-    def load(cls, export_dir, device="cuda", max_batch_size=4096, use_hip_graph=True, max_candidates=None):
+    def load(cls, export_dir, device="cuda", max_batch_size=4096, use_hip_graph=True, max_candidates=None, one_launch=False):
         """export_dir: a bundle, or the --export_path that holds bundles (the newest is taken).  max_candidates (din.py bundles;
-        default max_batch_size): the candidates per user one `rank_candidates` launch takes, longer requests are cut along C."""
+        default max_batch_size): the candidates per user one `rank_candidates` launch takes, longer requests are cut along C.
+        one_launch (dcn.py bundles; the other scripts ignore it): answer through rsx_predict_dcn, path == "fused", instead of
+        the rebuilt Estimator.  Off by default: the one-launch forward sums in another order than the Estimator's kernels, so
+        it agrees with them to 2e-5, not bit for bit."""
         import torch
         self = object.__new__(cls)
         self.bundle_dir = latest_bundle(export_dir)
@@ -376,7 +383,10 @@ class Predictor:
         self.layout = None if self.script == "din" else layout_from_manifest(m)
         self._graphs, self._n_graphs = {}, 0
         self._est = None
+        self.one_launch = bool(one_launch)
         if self.script in ("fm", "deepfm") and self._fused_setup(arrays):
+            self.path = "fused"
+        elif self.script == "dcn" and self.one_launch and self._fused_dcn_setup(arrays):
             self.path = "fused"
         else:
             self.path = "layers"
@@ -391,6 +401,30 @@ class Predictor:
         return self
 
     # -- the one-launch path ----------------------------------------------------------------------------------------------
+    def _fused_variables(self, arrays, need):
+        """The variables of a one-launch model on the device, once: the tables and every dense tensor of `need` in ONE flat
+        buffer (16-byte aligned parts), the row offsets, and the request buffers -> the dense tensors' address by name."""
+        import torch
+        if set(need) != set(arrays):
+            raise _lib.RsxError("bundle %r: a %s bundle holds the tensors %s, not %s"
+                                % (self.bundle_dir, self.script, sorted(need), sorted(arrays)))
+        dev, lay = self.device, self.layout
+        self._tables = torch.from_numpy(arrays["emb.input_layer.tables"]).to(dev)
+        dense = [k for k in need if k.startswith("dense.")]
+        offs, n = {}, 0
+        for k in dense:
+            offs[k] = n
+            n = (n + arrays[k].size + 3) & ~3
+        flat = np.zeros(n, np.float32)
+        for k in dense:
+            flat[offs[k]:offs[k] + arrays[k].size] = arrays[k].reshape(-1)
+        self._dense = torch.from_numpy(flat).to(dev)
+        self._row_off = torch.from_numpy(lay.row_off[:-1].astype(np.int32)).to(dev)
+        # request buffers: ids and prob of one chunk (the static inputs / outputs of the captured graphs are slices of them)
+        self._ids = torch.zeros(self.max_batch_size, lay.F, dtype=torch.int32, device=dev)
+        self._prob = torch.zeros(self.max_batch_size, dtype=torch.float32, device=dev)
+        return lambda k: self._dense.data_ptr() + 4 * offs[k]
+
     def _fused_setup(self, arrays):
         import torch
         m, lay = self.manifest, self.layout
@@ -406,25 +440,9 @@ class Predictor:
             need += ["dense.dnn.%s%d" % (v, l) for v in ("W", "b", "gamma", "beta")]
         if widths:
             need += ["dense.dnn.Wout", "dense.dnn.bout"]
-        if set(need) != set(arrays):
-            raise _lib.RsxError("bundle %r: a %s bundle holds the tensors %s, not %s"
-                                % (self.bundle_dir, self.script, sorted(need), sorted(arrays)))
-        dev = self.device
-        # the variables, once: the tables, the first-order vector, and every dense tensor in ONE flat buffer (16-byte aligned parts)
-        self._tables = torch.from_numpy(arrays["emb.input_layer.tables"]).to(dev)
-        self._w1 = torch.from_numpy(arrays["emb.input_layer.w1"]).to(dev)
-        dense = [k for k in need if k.startswith("dense.")]
-        offs, n = {}, 0
-        for k in dense:
-            offs[k] = n
-            n = (n + arrays[k].size + 3) & ~3
-        flat = np.zeros(n, np.float32)
-        for k in dense:
-            flat[offs[k]:offs[k] + arrays[k].size] = arrays[k].reshape(-1)
-        self._dense = torch.from_numpy(flat).to(dev)
-        self._row_off = torch.from_numpy(lay.row_off[:-1].astype(np.int32)).to(dev)
+        ptr = self._fused_variables(arrays, need)
+        self._w1 = torch.from_numpy(arrays["emb.input_layer.w1"]).to(self.device)      # the first-order vector
         lin_keys = {c["key"] for c in m["linear_columns"] if c["kind"].endswith("indicator")}
-        ptr = lambda k: self._dense.data_ptr() + 4 * offs[k]
         pm = _lib.PredictModel()
         pm.tables, pm.w1, pm.row_off = self._tables.data_ptr(), self._w1.data_ptr(), self._row_off.data_ptr()
         for l in range(len(widths)):
@@ -437,16 +455,43 @@ class Predictor:
         pm.w1_field_mask = lay.field_mask(lin_keys)
         pm.bn_eps = float(m["batch_norm_epsilon"])
         pm.F, pm.D, pm.L = lay.F, D, len(widths)
-        self._model = pm
-        # request buffers: ids and prob of one chunk (the static inputs / outputs of the captured graphs are slices of them)
-        self._ids = torch.zeros(self.max_batch_size, lay.F, dtype=torch.int32, device=dev)
-        self._prob = torch.zeros(self.max_batch_size, dtype=torch.float32, device=dev)
+        self._model, self._kernel = pm, "rsx_predict_fm_tower"
+        return True
+
+    def _fused_dcn_setup(self, arrays):
+        """dcn.py with one_launch=True: tables + ONE flat buffer of the dense tensors, no Estimator; False outside
+        rsx_predict_dcn's envelope."""
+        m, lay = self.manifest, self.layout
+        D = int(m["params"]["embedding_size"])
+        widths = [int(w) for w in str(m["params"].get("deep_layers", "")).split(",") if w]
+        Lc = int(m["params"].get("cross_layers", 0))
+        if len(widths) > _lib.PREDICT_MAX_LAYERS:
+            return False
+        wa = (C.c_int32 * _lib.PREDICT_MAX_LAYERS)(*widths)
+        if not _lib.lib().rsx_predict_dcn_supported(self.max_batch_size, lay.F, D, len(widths), wa, Lc):
+            return False
+        need = ["emb.input_layer.tables", "dense.cross.W", "dense.cross.b", "dense.out.W", "dense.out.b"]
+        for l in range(len(widths)):
+            need += ["dense.dnn.%s%d" % (v, l) for v in ("W", "b", "gamma", "beta")]
+        ptr = self._fused_variables(arrays, need)
+        pm = _lib.PredictDcnModel()
+        pm.tables, pm.row_off = self._tables.data_ptr(), self._row_off.data_ptr()
+        pm.cross_W, pm.cross_b = ptr("dense.cross.W"), ptr("dense.cross.b")
+        for l in range(len(widths)):
+            pm.W[l], pm.b[l] = ptr("dense.dnn.W%d" % l), ptr("dense.dnn.b%d" % l)
+            pm.gamma[l], pm.beta[l] = ptr("dense.dnn.gamma%d" % l), ptr("dense.dnn.beta%d" % l)
+            pm.widths[l] = widths[l]
+        pm.wo, pm.bo = ptr("dense.out.W"), ptr("dense.out.b")
+        pm.bn_eps = float(m["batch_norm_epsilon"])
+        pm.F, pm.D, pm.L, pm.Lc = lay.F, D, len(widths), Lc
+        self._model, self._kernel = pm, "rsx_predict_dcn"
         return True
 
     def _launch(self, n):
         import torch
-        _lib.check(_lib.lib().rsx_predict_fm_tower(C.byref(self._model), self._ids.data_ptr(), self._prob.data_ptr(), int(n),
-                                                   torch.cuda.current_stream().cuda_stream), "rsx_predict_fm_tower")
+        fn = getattr(_lib.lib(), self._kernel)          # rsx_predict_fm_tower / rsx_predict_dcn: the same call shape
+        _lib.check(fn(C.byref(self._model), self._ids.data_ptr(), self._prob.data_ptr(), int(n),
+                      torch.cuda.current_stream().cuda_stream), self._kernel)
 
     def _fused_chunk(self, ids):
         """ids: int32 [n, F] (host or device), n <= max_batch_size -> prob [n] (a view of the Predictor's output buffer,

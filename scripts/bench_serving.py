@@ -18,9 +18,16 @@ it, in ONE process, their timed regions alternating, `--repeats` rounds per requ
         where the kernel's time goes: rsx_predict_fm_tower through the C ABI on random weights with 0 to 3 layers of several
         widths, 20 launches back to back per graph replay, device time per launch at 16 and 4096 rows.
 
+    python scripts/bench_serving.py --model dcn [the same options]
+        the dcn.py leg (Criteo-39, d = 16, DNN 100-100, 3 cross layers), both contenders loaded from ONE exported bundle:
+        A  serving.Predictor as it loads by default: the layers path, HIP graphs on (the rebuilt Estimator's captured graph
+           of gather + cross forward + two tower-forward launches + head);
+        B  serving.Predictor.load(..., one_launch=True): the captured graph of ONE rsx_predict_dcn launch
+           (csrc/predict_dcn.hip).
+
 Roofline terms (named for what they are): bytes the request needs = B x 39 rows x 64 B + the dense weights once; FLOPs =
-2 x B x (624 x 100 + 100 x 100 + 100); over the kernel time.  At these sizes the kernel is latency-bound: the figure to watch
-is time per request."""
+2 x B x (624 x 100 + 100 x 100 + 100) (dcn: 2 x B x (624 x 100 + 100 x 100 + 100 + 624) + 3 x B x 5 x 624 for the cross
+layers); over the kernel time.  At these sizes the kernel is latency-bound: the figure to watch is time per request."""
 import argparse
 import csv
 import json
@@ -36,6 +43,9 @@ sys.path.insert(0, ROOT)
 
 A_KERNELS = ("gather_fm", "tower_fwd", "tower_head")        # the four launches of Estimator deepfm inference
 B_KERNEL = "predict_fm_tower_k"
+A_KERNELS_DCN = ("gather_fm", "cross_fwd", "tower_fwd", "tower_head")   # the launches of Estimator dcn inference
+B_KERNEL_DCN = "predict_dcn_k"
+DCN_CROSS_LAYERS = 3
 
 
 def build(dev, max_batch, export_dir):
@@ -59,6 +69,49 @@ def build(dev, max_batch, export_dir):
     assert pred.path == "fused", pred.path
     torch.cuda.synchronize()
     return est, pred, layout
+
+
+class LayersContender:
+    """The layers-path Predictor in the place of the Estimator of the deepfm leg: the calls the timing code makes."""
+
+    def __init__(self, pred):
+        self.pred, self.config = pred, pred._est.config
+        self._graphs = pred._est._graphs
+
+    def _infer_step(self, features, labels, mode):
+        return self.pred._est._infer_step(features, labels, mode)
+
+    def _call_model_fn(self, features, labels, mode):
+        return self.pred._est._call_model_fn(features, labels, mode)
+
+    def predict_examples(self, serialized):
+        return self.pred.predict_examples(serialized)
+
+
+def build_dcn(dev, max_batch, export_dir):
+    """-> (the default Predictor of a dcn.py bundle = layers path with HIP graphs on, the one_launch Predictor, layout)."""
+    import torch
+    from recsys_amd import dcn, serving
+    from recsys_amd.estimator import Estimator, ModeKeys, RunConfig
+    from recsys_amd.feature_columns import CriteoLayout, build_feature_columns
+    lin, emb = build_feature_columns(16, "numeric")
+    params = {"linear_feature_columns": lin, "embedding_feature_columns": emb, "embedding_size": 16, "learning_rate": 1e-3,
+              "dropout": 0.5, "deep_layers": "100,100", "cross_layers": DCN_CROSS_LAYERS, "max_batch_size": 64}
+    est = Estimator(dcn.model_fn, None, params, RunConfig(device=str(dev), seed=1234, use_hip_graph=False))
+    layout = CriteoLayout.from_columns(emb)
+    with torch.no_grad():
+        est._call_model_fn({"ids": torch.zeros(1, layout.F, dtype=torch.int32, device=dev)}, None, ModeKeys.PREDICT)
+        g = torch.Generator(device="cpu").manual_seed(7)          # a served model is a trained one: no all-zero biases
+        for k, p in est.store.dense.params.items():
+            if k.startswith("dnn.") and k.split(".")[-1][0] in "bg" or k == "out.b":
+                p.add_((torch.rand(p.shape, generator=g) * 0.2 - 0.1).to(dev))
+    d = est.export_savedmodel(export_dir)
+    del est
+    pa = serving.Predictor.load(d, device=str(dev), max_batch_size=max_batch)
+    pb = serving.Predictor.load(d, device=str(dev), max_batch_size=max_batch, one_launch=True)
+    assert pa.path == "layers" and pb.path == "fused", (pa.path, pb.path)
+    torch.cuda.synchronize()
+    return LayersContender(pa), pb, layout
 
 
 def request_ids(layout, B, seed):
@@ -106,8 +159,11 @@ def serialized_requests(n, seed=5):
         return list(tfrecord.unframe(open(path, "rb").read()))
 
 
-def algorithmic(B, dense_floats):
-    return {"bytes": B * 39 * 64 + 4 * dense_floats, "flops": 2 * B * (624 * 100 + 100 * 100 + 100)}
+def algorithmic(B, dense_floats, model="deepfm"):
+    flops = 2 * B * (624 * 100 + 100 * 100 + 100)
+    if model == "dcn":          # + the head's cross part, + per cross layer a 624-long dot (2) and s * x0 + x + b (3) per element
+        flops += 2 * B * 624 + DCN_CROSS_LAYERS * B * 5 * 624
+    return {"bytes": B * 39 * 64 + 4 * dense_floats, "flops": flops}
 
 
 def kernel_stats(path):
@@ -165,6 +221,7 @@ def main():
     import torch
     p = argparse.ArgumentParser()
     p.add_argument("--layer-probe", dest="layer_probe", action="store_true")
+    p.add_argument("--model", choices=("deepfm", "dcn"), default="deepfm")
     p.add_argument("--sizes", default="1,16,200,256,4096")
     p.add_argument("--replays", type=int, default=3000)
     p.add_argument("--repeats", type=int, default=3)
@@ -175,14 +232,18 @@ def main():
     p.add_argument("--kernel-stats", dest="kernel_stats", default=None)
     a = p.parse_args()
     dense_floats = 624 * 100 + 100 * 100 + 6 * 100 + 100 + 1 + 3 + 1 + 1
+    a_kernels, b_kernel = A_KERNELS, B_KERNEL
+    if a.model == "dcn":
+        dense_floats = 624 * 100 + 100 * 100 + 6 * 100 + 2 * DCN_CROSS_LAYERS * 624 + 100 + 624 + 1
+        a_kernels, b_kernel = A_KERNELS_DCN, B_KERNEL_DCN
     if a.kernel_stats:                            # no GPU needed: the trace's own numbers
         B, n = a.profile_run, a.profile_requests
         st = kernel_stats(a.kernel_stats)
-        a_ns = sum(t for name, (c, t, _) in st.items() if any(k in name for k in A_KERNELS))
-        a_calls = sum(c for name, (c, t, _) in st.items() if any(k in name for k in A_KERNELS))
-        b = [(c, t, avg) for name, (c, t, avg) in st.items() if B_KERNEL in name]
-        alg = algorithmic(B, dense_floats)
-        rec = {"batch_size": B, "A_kernels_per_request": round(a_calls / n, 2), "A_kernel_us_per_request": round(a_ns / n / 1e3, 3),
+        a_ns = sum(t for name, (c, t, _) in st.items() if any(k in name for k in a_kernels))
+        a_calls = sum(c for name, (c, t, _) in st.items() if any(k in name for k in a_kernels))
+        b = [(c, t, avg) for name, (c, t, avg) in st.items() if b_kernel in name]
+        alg = algorithmic(B, dense_floats, a.model)
+        rec = {"model": a.model, "batch_size": B, "A_kernels_per_request": round(a_calls / n, 2), "A_kernel_us_per_request": round(a_ns / n / 1e3, 3),
                "B_kernel_us_per_request": round(b[0][2] / 1e3, 3), "B_calls": b[0][0], "request_bytes": alg["bytes"],
                "request_flops": alg["flops"], "B_achieved_GBps": round(alg["bytes"] / b[0][2], 1),
                "B_achieved_GFLOPs": round(alg["flops"] / b[0][2], 1)}
@@ -195,7 +256,7 @@ def main():
     dev = torch.device("cuda")
     sizes = [int(s) for s in a.sizes.split(",")] if not a.profile_run else [a.profile_run]
     with tempfile.TemporaryDirectory() as tmp:
-        est, pred, layout = build(dev, max(sizes + [a.e2e_rows]), os.path.join(tmp, "export"))
+        est, pred, layout = (build_dcn if a.model == "dcn" else build)(dev, max(sizes + [a.e2e_rows]), os.path.join(tmp, "export"))
     if a.profile_run:
         from recsys_amd.estimator import ModeKeys
         est.config.use_hip_graph = pred.use_hip_graph = False       # eager: every launch appears in the trace under its name
@@ -218,8 +279,8 @@ def main():
             ta.append(time_replays(ga, a.replays))
             tb.append(time_replays(gb, a.replays))
         ma, mb = float(np.median(ta)), float(np.median(tb))
-        alg = algorithmic(B, dense_floats)
-        rec = {"batch_size": B, "A_estimator_us": round(ma, 3), "B_predictor_us": round(mb, 3), "B_over_A": round(mb / ma, 4),
+        alg = algorithmic(B, dense_floats, a.model)
+        rec = {"model": a.model, "batch_size": B, "A_estimator_us": round(ma, 3), "B_predictor_us": round(mb, 3), "B_over_A": round(mb / ma, 4),
                "A_repeats_us": [round(x, 3) for x in ta], "B_repeats_us": [round(x, 3) for x in tb],
                "A_spread": round((max(ta) - min(ta)) / ma, 4), "B_spread": round((max(tb) - min(tb)) / mb, 4),
                "max_abs_prob_diff": err, "request_bytes": alg["bytes"], "request_flops": alg["flops"]}
@@ -240,7 +301,7 @@ def main():
                     fn(reqs)                       # (ends in a device-to-host copy of prob: synchronises)
                 torch.cuda.synchronize()
                 dst.append((time.perf_counter() - t0) / a.e2e_calls * 1e6)
-        rec = {"predict_examples_rows": a.e2e_rows, "A_estimator_us": round(float(np.median(ta)), 1),
+        rec = {"model": a.model, "predict_examples_rows": a.e2e_rows, "A_estimator_us": round(float(np.median(ta)), 1),
                "B_predictor_us": round(float(np.median(tb)), 1), "A_repeats_us": [round(x, 1) for x in ta],
                "B_repeats_us": [round(x, 1) for x in tb]}
         out.append(rec)
