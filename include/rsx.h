@@ -680,10 +680,22 @@ int rsx_mlp_nobn_reduce_job(const rsx_mlp_step* step_h, rsx_mlp_reduce_job* job_
  * 32 * (max width rounded up to 16, + 4) and the layers' partial tiles (at most 8 192 floats up to 512 columns) -- within
  * 160 KB: every FusedTower width up to 256 at F = 64, inner widths up to ~600 at F = 39.  A layer whose width is no multiple
  * of 4 or whose W is not 16-byte aligned is read with 4-byte loads (slower, same results).
+ * 16-bit tables (since rsx_version() 101): `table_dtype` says how the rows of `tables` are stored -- RSX_TABLE_F32 (0, what a
+ * zeroed struct means), RSX_TABLE_BF16 or RSX_TABLE_F16: [R, 16] elements of 2 bytes, still 16-byte aligned.  A row is widened
+ * to fp32 as it is loaded (exact for both formats, subnormals and signed zeros included) and nothing else changes: the
+ * probabilities are bit-identical to an fp32 launch over the widened table.  w1 and every dense tensor stay fp32.  Any other
+ * table_dtype is RSX_EINVAL, before any HIP call.  `table_dtype` was APPENDED to rsx_predict_model and rsx_predict_dcn_model:
+ * a caller built against the earlier structs passes memory the library reads as table_dtype and must be rebuilt.
  * ------------------------------------------------------------------------------------------- */
 #define RSX_PREDICT_MAX_LAYERS 3
+/* How the rows of `tables` are stored (the models' last member `table_dtype`; a zeroed struct means fp32). */
+enum {
+  RSX_TABLE_F32 = 0,
+  RSX_TABLE_BF16 = 1,                           /* bfloat16 bit patterns, 2 bytes per element */
+  RSX_TABLE_F16 = 2                             /* IEEE binary16 */
+};
 typedef struct {
-  const float* tables;                          /* [R, D] */
+  const void* tables;                           /* [R, D] of table_dtype */
   const float* w1;                              /* nullable [R] */
   const int32_t* row_off;                       /* [F] first row of every field (device) */
   const float* W[RSX_PREDICT_MAX_LAYERS];       /* [K_l, widths[l]], K_0 = F * D */
@@ -699,6 +711,7 @@ typedef struct {
   float bn_eps;
   int32_t F, D, L;
   int32_t widths[RSX_PREDICT_MAX_LAYERS];
+  int32_t table_dtype;                          /* RSX_TABLE_*  (appended in version 101) */
 } rsx_predict_model;
 int rsx_predict_fm_tower_supported(int B, int F, int D, int L, const int32_t* widths);
 int rsx_predict_fm_tower(const rsx_predict_model* model_h, const int32_t* ids, float* prob, int B, rsx_stream_t stream);
@@ -717,8 +730,9 @@ int rsx_predict_fm_tower(const rsx_predict_model* model_h, const int32_t* ids, f
  * ids[B * F) is read.
  * Nullable: gamma[l] / beta[l] together (layer l without batch-norm); W / b / gamma / beta / widths are not read beyond L.
  * RSX_EINVAL (before any HIP call): a NULL model / ids / prob / tables / row_off / cross_W / cross_b / wo / bo / W[l] / b[l],
- * B <= 0, gamma[l] without beta[l] or the reverse, a bn_eps that is negative or not finite, tables / cross_W / cross_b not
- * 16-byte aligned (they are read as float4).  wo needs 4-byte alignment only: its cross part starts at widths[L-1] floats and is
+ * B <= 0, gamma[l] without beta[l] or the reverse, a bn_eps that is negative or not finite, a table_dtype that is none of
+ * RSX_TABLE_* (16-bit tables as in rsx_predict_fm_tower), tables / cross_W / cross_b not 16-byte aligned (they are read as
+ * float4; 16-bit rows as 8 bytes of a 32-byte row).  wo needs 4-byte alignment only: its cross part starts at widths[L-1] floats and is
  * read with 4-byte loads when that address is not 16-byte aligned.
  * Envelope (rsx_predict_dcn_supported; RSX_EUNSUPPORTED outside, where the caller serves through the TRAIN kernels' inference
  * form): D == 16, 1 <= F <= 64, 1 <= L <= RSX_PREDICT_MAX_LAYERS with the width rules of rsx_predict_fm_tower (inner widths
@@ -726,7 +740,7 @@ int rsx_predict_fm_tower(const rsx_predict_model* model_h, const int32_t* ids, f
  * rsx_predict_fm_tower: 16 * (16 F + 4) + 32 * (max width rounded up to 16, + 4) + the partial tiles + 32 floats within 160 KB.
  * ------------------------------------------------------------------------------------------- */
 typedef struct {
-  const float* tables;                          /* [R, D] */
+  const void* tables;                           /* [R, D] of table_dtype */
   const int32_t* row_off;                       /* [F] first row of every field (device) */
   const float* cross_W;                         /* [Lc, 16 F] */
   const float* cross_b;                         /* [Lc, 16 F] */
@@ -739,6 +753,7 @@ typedef struct {
   float bn_eps;
   int32_t F, D, L, Lc;
   int32_t widths[RSX_PREDICT_MAX_LAYERS];
+  int32_t table_dtype;                          /* RSX_TABLE_*  (appended in version 101) */
 } rsx_predict_dcn_model;
 int rsx_predict_dcn_supported(int B, int F, int D, int L, const int32_t* widths, int Lc);
 int rsx_predict_dcn(const rsx_predict_dcn_model* model_h, const int32_t* ids, float* prob, int B, rsx_stream_t stream);

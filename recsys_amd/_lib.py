@@ -187,6 +187,7 @@ class SparseOptHp(C.Structure):
 
 
 PREDICT_MAX_LAYERS = 3
+TABLE_DTYPES = {"float32": 0, "bfloat16": 1, "float16": 2}       # include/rsx.h RSX_TABLE_*
 
 
 class PredictModel(C.Structure):
@@ -195,7 +196,7 @@ class PredictModel(C.Structure):
                 ("b", C.c_void_p * PREDICT_MAX_LAYERS), ("gamma", C.c_void_p * PREDICT_MAX_LAYERS),
                 ("beta", C.c_void_p * PREDICT_MAX_LAYERS), ("wd", C.c_void_p), ("bd", C.c_void_p), ("c0", C.c_void_p),
                 ("wo", C.c_void_p), ("bo", C.c_void_p), ("w1_field_mask", C.c_uint64), ("bn_eps", C.c_float), ("F", C.c_int32),
-                ("D", C.c_int32), ("L", C.c_int32), ("widths", C.c_int32 * PREDICT_MAX_LAYERS)]
+                ("D", C.c_int32), ("L", C.c_int32), ("widths", C.c_int32 * PREDICT_MAX_LAYERS), ("table_dtype", C.c_int32)]
 
 
 class PredictDcnModel(C.Structure):
@@ -204,7 +205,7 @@ class PredictDcnModel(C.Structure):
                 ("W", C.c_void_p * PREDICT_MAX_LAYERS), ("b", C.c_void_p * PREDICT_MAX_LAYERS),
                 ("gamma", C.c_void_p * PREDICT_MAX_LAYERS), ("beta", C.c_void_p * PREDICT_MAX_LAYERS),
                 ("wo", C.c_void_p), ("bo", C.c_void_p), ("bn_eps", C.c_float), ("F", C.c_int32), ("D", C.c_int32),
-                ("L", C.c_int32), ("Lc", C.c_int32), ("widths", C.c_int32 * PREDICT_MAX_LAYERS)]
+                ("L", C.c_int32), ("Lc", C.c_int32), ("widths", C.c_int32 * PREDICT_MAX_LAYERS), ("table_dtype", C.c_int32)]
 
 
 class PredictDinModel(C.Structure):

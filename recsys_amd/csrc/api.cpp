@@ -1,7 +1,7 @@
 // Version / error strings of librsx.so.
 #include "rsx.h"
 
-extern "C" int rsx_version(void) { return 100; /* 0.1.0 */ }
+extern "C" int rsx_version(void) { return 101; /* 0.1.1: table_dtype appended to rsx_predict_model / rsx_predict_dcn_model */ }
 
 extern "C" const char* rsx_strerror(int status) {
   switch (status) {

@@ -24,6 +24,8 @@
 #include "predict_device.h"
 
 namespace {
+// TD: how the table rows are stored (RSX_TABLE_*); only the row load differs between the instantiations.
+template <int TD>
 __global__ __launch_bounds__(PR_T) void predict_fm_tower_k(const PredictArgs p) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
   const int tid = threadIdx.x;
@@ -37,7 +39,6 @@ __global__ __launch_bounds__(PR_T) void predict_fm_tower_k(const PredictArgs p) 
   // not stored. ----
   {
     const int r = tid >> 5, j = (tid >> 2) & 7, q = tid & 3;
-    const f32x4* __restrict__ TV = reinterpret_cast<const f32x4*>(p.tables);
     const int b = row0 + r < p.B ? row0 + r : p.B - 1;
     const uint32_t ib = (uint32_t)b * (uint32_t)F;
     int row[PR_GF], fc[PR_GF];
@@ -51,7 +52,7 @@ __global__ __launch_bounds__(PR_T) void predict_fm_tower_k(const PredictArgs p) 
     float wv[PR_GF];
 #pragma unroll
     for (int u = 0; u < PR_GF; ++u) {
-      ev[u] = TV[(size_t)row[u] * 4 + q];
+      ev[u] = load_row4<TD>(p.tables, row[u], q);
       wv[u] = p.w1 != nullptr ? p.w1[row[u]] : 0.f;
     }
     __builtin_amdgcn_sched_barrier(0);                   // (every load in flight before the first store)
@@ -115,6 +116,19 @@ __global__ __launch_bounds__(PR_T) void predict_fm_tower_k(const PredictArgs p) 
   }
 }
 
+// The raised LDS limit is a property of a kernel FUNCTION: every instantiation asks for its own, once.
+template <int TD>
+int launch_fm_tower(const PredictArgs& p, const size_t lds, hipStream_t stream) {
+  if (lds > 64 * 1024) {
+    static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(predict_fm_tower_k<TD>),
+                                                       hipFuncAttributeMaxDynamicSharedMemorySize, PR_MAX_LDS);
+    if (attr != hipSuccess) return RSX_EUNSUPPORTED;
+  }
+  RSX_LAUNCH(predict_fm_tower_k<TD>, dim3((p.B + PR_ROWS - 1) / PR_ROWS), dim3(PR_T), lds, stream, p);
+  RSX_CHECK_LAUNCH();
+  return RSX_OK;
+}
+
 }  // namespace
 
 extern "C" int rsx_predict_fm_tower_supported(int B, int F, int D, int L, const int32_t* widths) {
@@ -132,7 +146,8 @@ extern "C" int rsx_predict_fm_tower(const rsx_predict_model* m, const int32_t* i
     }
     if (m->L > 0 && (!m->wd || !m->bd)) return RSX_EINVAL;
   }
-  if (!al16(m->tables)) return RSX_EINVAL;               // rows are read as float4
+  if (!table_dtype_known(m->table_dtype)) return RSX_EINVAL;
+  if (!al16(m->tables)) return RSX_EINVAL;               // rows are read as float4 (16-bit rows: 8 bytes of a 32-byte row)
   PredictArgs p;
   const long long fl = predict_lds_floats(B, m->F, m->D, m->L, m->widths, &p);
   if (fl < 0) return RSX_EUNSUPPORTED;
@@ -150,12 +165,9 @@ extern "C" int rsx_predict_fm_tower(const rsx_predict_model* m, const int32_t* i
   p.bn_rstd = 1.0f / sqrtf(1.0f + m->bn_eps);
   p.B = B; p.F = m->F; p.L = m->L;
   const size_t lds = (size_t)fl * sizeof(float);
-  if (lds > 64 * 1024) {
-    static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(predict_fm_tower_k),
-                                                       hipFuncAttributeMaxDynamicSharedMemorySize, PR_MAX_LDS);
-    if (attr != hipSuccess) return RSX_EUNSUPPORTED;
+  switch (m->table_dtype) {
+    case RSX_TABLE_BF16: return launch_fm_tower<RSX_TABLE_BF16>(p, lds, rsx_s(stream));
+    case RSX_TABLE_F16: return launch_fm_tower<RSX_TABLE_F16>(p, lds, rsx_s(stream));
+    default: return launch_fm_tower<RSX_TABLE_F32>(p, lds, rsx_s(stream));
   }
-  RSX_LAUNCH(predict_fm_tower_k, dim3((B + PR_ROWS - 1) / PR_ROWS), dim3(PR_T), lds, rsx_s(stream), p);
-  RSX_CHECK_LAUNCH();
-  return RSX_OK;
 }

@@ -24,7 +24,7 @@ namespace {
 constexpr int DCN_MAX_LC = 8;                  // cross.hip's CROSS_MAX_L
 
 struct PredictDcnArgs {
-  const float* tables; const int32_t* row_off; const int32_t* ids;
+  const void* tables; const int32_t* row_off; const int32_t* ids;   // tables: [R, 16] of the kernel's TD
   const float* W[RSX_PREDICT_MAX_LAYERS]; const float* b[RSX_PREDICT_MAX_LAYERS];
   const float* gamma[RSX_PREDICT_MAX_LAYERS]; const float* beta[RSX_PREDICT_MAX_LAYERS];
   const float* cw; const float* cb;            // cross.W, cross.b [Lc][16 F] (16-byte aligned)
@@ -61,8 +61,9 @@ __device__ __forceinline__ float half_wave_sum(float v) {
   return v;
 }
 
-// NU: float4 slots per gather thread = fields j, j + 8, ..., j + 8 (NU - 1); 8 NU >= F.
-template <int NU>
+// NU: float4 slots per gather thread = fields j, j + 8, ..., j + 8 (NU - 1); 8 NU >= F.  TD: how the table rows are stored
+// (RSX_TABLE_*); only the row load differs.
+template <int NU, int TD>
 __global__ __launch_bounds__(PR_T) void predict_dcn_k(const PredictDcnArgs p) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
   const int tid = threadIdx.x;
@@ -74,7 +75,6 @@ __global__ __launch_bounds__(PR_T) void predict_dcn_k(const PredictDcnArgs p) {
   // last example's ids (never ids past B); their outputs are not stored. ----
   {
     const int r = tid >> 5, j = (tid >> 2) & 7, q = tid & 3;
-    const f32x4* __restrict__ TV = reinterpret_cast<const f32x4*>(p.tables);
     const int b = row0 + r < p.B ? row0 + r : p.B - 1;
     const uint32_t ib = (uint32_t)b * (uint32_t)F;
     const int dim = 16 * F;
@@ -93,7 +93,7 @@ __global__ __launch_bounds__(PR_T) void predict_dcn_k(const PredictDcnArgs p) {
     const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
     f32x4 x0[NU], wc[NU];
 #pragma unroll
-    for (int u = 0; u < NU; ++u) x0[u] = TV[(size_t)row[u] * 4 + q];
+    for (int u = 0; u < NU; ++u) x0[u] = load_row4<TD>(p.tables, row[u], q);
     load_slices<NU>(wc, p.cw, off, true);                // w_0
     __builtin_amdgcn_sched_barrier(0);                   // (every load in flight before the first store)
     f32x4 x[NU];
@@ -163,16 +163,23 @@ long long predict_dcn_lds_floats(int B, int F, int D, int L, const int32_t* widt
   return predict_lds_floats(B, F, D, L, widths, plan);
 }
 
-template <int NU>
+// The raised LDS limit is a property of a kernel FUNCTION: every instantiation asks for its own, once.
+template <int NU, int TD>
 int launch_dcn(const PredictDcnArgs& p, const size_t lds, hipStream_t stream) {
   if (lds > 64 * 1024) {
-    static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(predict_dcn_k<NU>),
+    static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(predict_dcn_k<NU, TD>),
                                                        hipFuncAttributeMaxDynamicSharedMemorySize, PR_MAX_LDS);
     if (attr != hipSuccess) return RSX_EUNSUPPORTED;
   }
-  RSX_LAUNCH(predict_dcn_k<NU>, dim3((p.B + PR_ROWS - 1) / PR_ROWS), dim3(PR_T), lds, stream, p);
+  RSX_LAUNCH((predict_dcn_k<NU, TD>), dim3((p.B + PR_ROWS - 1) / PR_ROWS), dim3(PR_T), lds, stream, p);
   RSX_CHECK_LAUNCH();
   return RSX_OK;
+}
+
+// fields per gather thread: 5 covers F <= 40 (Criteo-39), 8 every F of the envelope
+template <int TD>
+int launch_dcn_nu(const PredictDcnArgs& p, const size_t lds, hipStream_t stream) {
+  return p.F <= 40 ? launch_dcn<5, TD>(p, lds, stream) : launch_dcn<8, TD>(p, lds, stream);
 }
 
 }  // namespace
@@ -192,6 +199,7 @@ extern "C" int rsx_predict_dcn(const rsx_predict_dcn_model* m, const int32_t* id
       if ((m->gamma[l] == nullptr) != (m->beta[l] == nullptr)) return RSX_EINVAL;
     }
   }
+  if (!table_dtype_known(m->table_dtype)) return RSX_EINVAL;
   if (!al16(m->tables) || !al16(m->cross_W) || !al16(m->cross_b)) return RSX_EINVAL;   // read as float4
   PredictArgs plan;
   const long long fl = predict_dcn_lds_floats(B, m->F, m->D, m->L, m->widths, m->Lc, &plan);
@@ -212,6 +220,9 @@ extern "C" int rsx_predict_dcn(const rsx_predict_dcn_model* m, const int32_t* id
   p.ldx = plan.ldx; p.lda = plan.lda;
   p.oA0 = plan.oA0; p.oA1 = plan.oA1; p.oP = plan.oP; p.oY = plan.oY;
   const size_t lds = (size_t)fl * sizeof(float);
-  // fields per gather thread: 5 covers F <= 40 (Criteo-39), 8 every F of the envelope
-  return m->F <= 40 ? launch_dcn<5>(p, lds, rsx_s(stream)) : launch_dcn<8>(p, lds, rsx_s(stream));
+  switch (m->table_dtype) {
+    case RSX_TABLE_BF16: return launch_dcn_nu<RSX_TABLE_BF16>(p, lds, rsx_s(stream));
+    case RSX_TABLE_F16: return launch_dcn_nu<RSX_TABLE_F16>(p, lds, rsx_s(stream));
+    default: return launch_dcn_nu<RSX_TABLE_F32>(p, lds, rsx_s(stream));
+  }
 }

@@ -1,6 +1,7 @@
 // The device functions and the LDS plan shared by the one-launch serving kernels (predict.hip: fm.py / deepfm.py,
-// predict_dcn.hip: dcn.py): the fp32 MFMA layer loop `dense_bn_layer` over a 16-example tile held in LDS, and
-// `predict_lds_floats`, the tile's LDS layout and envelope.  See predict.hip's head for the layer loop's shape.
+// predict_dcn.hip: dcn.py): the fp32 MFMA layer loop `dense_bn_layer` over a 16-example tile held in LDS,
+// `predict_lds_floats`, the tile's LDS layout and envelope, and `load_row4`, the one place that knows how a table row is
+// stored (fp32, or bfloat16 / float16 widened exactly).  See predict.hip's head for the layer loop's shape.
 #pragma once
 #include "rsx_common.h"
 
@@ -13,8 +14,29 @@ constexpr int PR_ROWS = 16;                    // examples per workgroup
 constexpr int PR_GF = 8;                       // fields per gather thread: 64 fields / 8 field lanes
 constexpr int PR_MAX_LDS = 160 * 1024;
 
+// Elements 4 q .. 4 q + 3 of row `row` of tables [R, 16] stored as TD (RSX_TABLE_*), as fp32.  A 16-bit row is 32 bytes: the
+// thread loads the 8 bytes that hold its four elements and widens them, which is exact for both formats (subnormals, signed
+// zeros included), so the kernel computes what its fp32 instantiation computes over the widened table, bit for bit.
+// bfloat16 is the upper half of the fp32 pattern: a shift for the even elements, a mask for the odd ones.  float16 takes the
+// hardware convert (v_cvt_f32_f16 keeps fp16 subnormals: the fp16 denormal mode is on in every HIP kernel).
+typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
+template <int TD>
+__device__ __forceinline__ f32x4 load_row4(const void* __restrict__ tables, const int row, const int q) {
+  if constexpr (TD == RSX_TABLE_F32) {
+    return reinterpret_cast<const f32x4*>(tables)[(size_t)row * 4 + q];
+  } else if constexpr (TD == RSX_TABLE_BF16) {
+    const uint2 v = reinterpret_cast<const uint2*>(tables)[(size_t)row * 4 + q];
+    return f32x4{__uint_as_float(v.x << 16), __uint_as_float(v.x & 0xffff0000u), __uint_as_float(v.y << 16),
+                 __uint_as_float(v.y & 0xffff0000u)};
+  } else {
+    static_assert(TD == RSX_TABLE_F16, "unknown table dtype");
+    return __builtin_convertvector(reinterpret_cast<const f16x4*>(tables)[(size_t)row * 4 + q], f32x4);
+  }
+}
+inline bool table_dtype_known(int td) { return td == RSX_TABLE_F32 || td == RSX_TABLE_BF16 || td == RSX_TABLE_F16; }
+
 struct PredictArgs {
-  const float* tables; const float* w1; const int32_t* row_off; const int32_t* ids;
+  const void* tables; const float* w1; const int32_t* row_off; const int32_t* ids;   // tables: [R, 16] of the kernel's TD
   const float* W[RSX_PREDICT_MAX_LAYERS]; const float* b[RSX_PREDICT_MAX_LAYERS];
   const float* gamma[RSX_PREDICT_MAX_LAYERS]; const float* beta[RSX_PREDICT_MAX_LAYERS];
   const float* wd; const float* bd; const float* c0; const float* wo; const float* bo;

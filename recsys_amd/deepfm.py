@@ -187,6 +187,10 @@ def define_flags(p=None):
     p.add_argument("--task_type", default="train", help="{train, infer, eval, export}")
     p.add_argument("--export_path", default="./export/",
                    help="--task_type export: the latest checkpoint of --model_dir goes to <export_path>/<unix seconds>/")
+    p.add_argument("--export_table_dtype", default="float32", choices=("float32", "bfloat16", "float16"),
+                   help="--task_type export: how the bundle stores the embedding tables.  A 16-bit dtype rounds them (to nearest "
+                        "even), halves the bundle and the tables a fused-path Predictor keeps on the device, and moves the "
+                        "probabilities by 1e-4 to 1e-2; first-order weights and dense tensors stay float32")
     p.add_argument("--num_epochs", type=int, default=10)
     p.add_argument("--deep_layers", default="100,100")
     p.add_argument("--train_path", default="/home/wangrc/criteo_data/train/")
@@ -306,7 +310,7 @@ def run_main(model_fn, FLAGS, make_params_fn):
                 break
         return out
     if FLAGS.task_type == "export":
-        return est.export_savedmodel(FLAGS.export_path)
+        return est.export_savedmodel(FLAGS.export_path, table_dtype=FLAGS.export_table_dtype)
     raise SystemExit("unknown --task_type %r" % FLAGS.task_type)
 
 

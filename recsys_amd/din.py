@@ -574,6 +574,10 @@ def define_flags():
     p.add_argument("--task_type", default="train", help="{train, infer, eval, export}")
     p.add_argument("--export_path", default="./export/",
                    help="--task_type export: the latest checkpoint of --model_dir goes to <export_path>/<unix seconds>/")
+    p.add_argument("--export_table_dtype", default="float32", choices=("float32", "bfloat16", "float16"),
+                   help="--task_type export: how the bundle stores the embedding tables.  A 16-bit dtype rounds them (to nearest "
+                        "even), halves the bundle and the tables a fused-path Predictor keeps on the device, and moves the "
+                        "probabilities by 1e-4 to 1e-2; first-order weights and dense tensors stay float32")
     p.add_argument("--num_epochs", type=int, default=5)
     p.add_argument("--deep_layers", default="100,100")        # accepted, ignored like the reference (:19,85-86)
     p.add_argument("--din_layers", default="80,40")
@@ -622,7 +626,7 @@ def main(argv=None):
     if FLAGS.task_type == "eval":
         return est.evaluate(lambda: input_fn(eval_files, FLAGS.batch_size, 1, False, FLAGS.hist_len, shard, True), steps=FLAGS.eval_steps)
     if FLAGS.task_type == "export":     # (only when asked: the reference's deepfm.py exports after every task, its main falls through)
-        return est.export_savedmodel(FLAGS.export_path)
+        return est.export_savedmodel(FLAGS.export_path, table_dtype=FLAGS.export_table_dtype)
     return list(zip(range(10), est.predict(lambda: input_fn(eval_files, FLAGS.batch_size, 1, False, FLAGS.hist_len))))
 
 

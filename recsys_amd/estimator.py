@@ -987,13 +987,15 @@ class Estimator:
         return {"prob": np.concatenate(out) if out else np.zeros(0, np.float32)}
 
 
-    def export_savedmodel(self, export_dir_base):
+    def export_savedmodel(self, export_dir_base, table_dtype="float32"):
         """Estimator.export_savedmodel (deepfm/deepfm.py:220-234): the latest checkpoint of model_dir as a serving bundle
         `<export_dir_base>/<unix seconds>/` = model.json + variables.npz (recsys_amd.serving: the variables in fp32, no
         optimizer slots or state), written under a temporary name and renamed when complete.  -> the directory (the chief's
-        under data parallelism; None on the other ranks).  serving.Predictor.load() serves it."""
+        under data parallelism; None on the other ranks).  serving.Predictor.load() serves it.
+        table_dtype "bfloat16" / "float16" (--export_table_dtype): the embedding tables are rounded to that dtype and stored
+        in it (a format_version 2 bundle); opt-in, it changes the probabilities."""
         from . import serving
-        return serving.export_estimator(self, export_dir_base)
+        return serving.export_estimator(self, export_dir_base, table_dtype=table_dtype)
 
 
 class _LaunchThread:

@@ -7,6 +7,10 @@ The reference exports a SavedModel whose serving signature parses serialized `tf
               batch-norm epsilon, name / shape / dtype of every tensor) + `variables.npz` (the variables in fp32: tables,
               first-order weights, the dense arena's named tensors; no optimizer slots, no optimizer state), written under a
               temporary name and renamed when complete (`Estimator.export_savedmodel`, `--task_type export`).
+              `--export_table_dtype bfloat16 | float16` (opt-in) stores the embedding tables rounded to that dtype: a
+              format_version 2 bundle with a top-level "table_dtype"; bfloat16 rows are uint16 bit patterns whose tensor entry
+              carries "encoding": "bfloat16".  First-order weights, din.py's bias table and the dense tensors stay fp32.  A
+              float32 export is format_version 1, byte for byte what it was before the option existed.
   Predictor   loads a bundle and answers `predict_examples(list of serialized Examples)` / `predict(features)`.
               path == "fused":  fm.py / deepfm.py bundles inside the kernel's envelope -- the variables live on the device once
                                 and a batch is ONE launch of rsx_predict_fm_tower (csrc/predict.hip), captured per request size
@@ -14,10 +18,14 @@ The reference exports a SavedModel whose serving signature parses serialized `tf
                                 dcn.py bundles loaded with `Predictor.load(..., one_launch=True)` inside rsx_predict_dcn's
                                 envelope (csrc/predict_dcn.hip) -- the same buffers, graphs and chunking, ONE launch of that
                                 kernel per batch.  Opt-in: it agrees with the Estimator to 2e-5, not bit for bit.
+                                A 16-bit bundle's table goes to the device as stored (R x 16 x 2 bytes) and the kernel widens
+                                a row as it loads it: bit-identical to an fp32 bundle holding the rounded values.
               path == "layers": dcn.py (the default) / xdeepfm.py / din.py bundles, and fm / deepfm / dcn shapes outside the
                                 envelope -- the script's Estimator rebuilt from the manifest (model_dir=None) with the
                                 bundle's variables, answering through Estimator._infer_step (the TRAIN kernels' inference
-                                form), bit-identical to the Estimator the bundle came from.
+                                form), bit-identical to the Estimator the bundle came from.  A 16-bit bundle's tables are
+                                widened to fp32 on the host first: it answers like an fp32 bundle holding the rounded values,
+                                and saves no device memory here.
               din.py bundles also answer `rank_candidates(u_iid_seq, u_icat_seq, i_id, i_cate)`: ONE user history against C
               candidate items (or U histories against C candidates each) -> prob [C] / [U, C].
               rank_path == "fused":  ONE launch of rsx_predict_din_rank (csrc/predict_din.hip) over the variables where the
@@ -39,13 +47,73 @@ from . import _lib
 from .feature_columns import Column, CriteoLayout
 from .layers import BN_EPS
 
-FORMAT_VERSION = 1
+FORMAT_VERSION = 1                    # float32 tables; 16-bit tables (`table_dtype`, `encoding`) make a bundle version 2
+FORMAT_VERSION_16BIT = 2
+TABLE_DTYPES = ("float32", "bfloat16", "float16")
 SCRIPTS = ("fm", "deepfm", "xdeepfm", "dcn", "din")
 MANIFEST, VARIABLES = "model.json", "variables.npz"
 # model_fn parameters that shape the network (what a Predictor needs to rebuild it without the training flags)
 _NETWORK_PARAMS = ("embedding_size", "deep_layers", "cross_layers", "cin_bf16", "cin_split", "hist_len", "n_item", "n_cate",
                    "tower", "force_generic")
 SIGNATURE = {"serving_default": {"inputs": "examples", "outputs": ["prob"]}}
+
+
+# ---- 16-bit embedding rows: plain numpy, no device ---------------------------------------------------------------------------
+def is_embedding_rows(name, shape, embedding_size):
+    """An embedding-row tensor: `emb.<arena>.tables` / `emb.<arena>.table` whose last dimension is the model's embedding_size
+    (not the first-order vector `w1`, not din.py's 4-wide bias table, no dense tensor)."""
+    return (name.startswith("emb.") and name.rsplit(".", 1)[-1] in ("tables", "table") and len(shape) >= 1
+            and int(shape[-1]) == int(embedding_size))
+
+
+def quantize_rows(a, dtype, name="tensor"):
+    """fp32 array -> its stored form in `dtype`, rounded to nearest even: "float32" the array itself, "float16" a numpy
+    float16 array, "bfloat16" the bit patterns as uint16 (numpy has no bfloat16).  Refuses (RsxError naming `name`) a value
+    that is not finite and a finite one that rounds to infinity (float16 beyond 65504, bfloat16 just below the fp32 maximum)."""
+    if dtype not in TABLE_DTYPES:
+        raise _lib.RsxError("table dtype %r is none of %s" % (dtype, ", ".join(TABLE_DTYPES)))
+    a = np.ascontiguousarray(a, np.float32)
+    if dtype == "float32":
+        return a
+    if not np.isfinite(a).all():
+        raise _lib.RsxError("tensor %r holds values that are not finite: it cannot be stored as %s" % (name, dtype))
+    if dtype == "float16":
+        with np.errstate(over="ignore"):
+            out = a.astype(np.float16)
+        over = ~np.isfinite(out)
+    else:
+        u = a.view(np.uint32)
+        out = ((u + np.uint32(0x7fff) + ((u >> np.uint32(16)) & np.uint32(1))) >> np.uint32(16)).astype(np.uint16)
+        over = (out & np.uint16(0x7fff)) == np.uint16(0x7f80)
+    if over.any():
+        raise _lib.RsxError("tensor %r holds finite values (largest magnitude %g) that round to infinity in %s"
+                            % (name, float(np.abs(a).max()), dtype))
+    return out
+
+
+def dequantize_rows(a, encoding=None):
+    """The stored form back to fp32, exactly: encoding "bfloat16" takes uint16 bit patterns, otherwise the array's own dtype
+    (float16 or float32) says what it is."""
+    a = np.asarray(a)
+    if encoding == "bfloat16":
+        if a.dtype != np.uint16:
+            raise _lib.RsxError("bfloat16 rows are stored as uint16 bit patterns, not %s" % a.dtype)
+        return (a.astype(np.uint32) << np.uint32(16)).view(np.float32)
+    if encoding not in (None, "float16", "float32") or a.dtype not in (np.float16, np.float32):
+        raise _lib.RsxError("cannot widen rows of dtype %s with encoding %r" % (a.dtype, encoding))
+    return a.astype(np.float32)
+
+
+def quantize_tensors(tensors, embedding_size, table_dtype):
+    """{name: fp32 array} -> the same with every embedding-row tensor in its stored 16-bit form (the rest untouched)."""
+    return {k: quantize_rows(v, table_dtype, k) if is_embedding_rows(k, v.shape, embedding_size) else v
+            for k, v in tensors.items()}
+
+
+def widen_tensors(manifest, arrays):
+    """A bundle's arrays as read -> every tensor fp32 (what the layers path loads); a version 1 bundle's arrays unchanged."""
+    enc = {t["name"]: t.get("encoding") for t in manifest["tensors"]}
+    return {k: v if v.dtype == np.float32 else dequantize_rows(v, enc.get(k)) for k, v in arrays.items()}
 
 
 # ---- manifest ------------------------------------------------------------------------------------------------------------
@@ -70,8 +138,11 @@ def linear_mode(linear_columns):
     return "custom"
 
 
-def make_manifest(script, params, global_step, tensors):
-    """The settings of one exported model.  tensors: {name: numpy array} -- only names, shapes and dtypes go in here."""
+def make_manifest(script, params, global_step, tensors, table_dtype="float32"):
+    """The settings of one exported model.  tensors: {name: numpy array} as stored -- only names, shapes and dtypes go in
+    here.  A 16-bit table_dtype makes a format_version 2 manifest (see the module docstring); "float32" adds no key."""
+    if table_dtype not in TABLE_DTYPES:
+        raise _lib.RsxError("export: table dtype %r is none of %s" % (table_dtype, ", ".join(TABLE_DTYPES)))
     if script not in SCRIPTS:
         raise _lib.RsxError("export: unknown script %r (known: %s)" % (script, ", ".join(SCRIPTS)))
     emb = params.get("embedding_feature_columns")
@@ -89,6 +160,12 @@ def make_manifest(script, params, global_step, tensors):
          "linear_columns": [_column_json(c) for c in lin],
          "signature": SIGNATURE,
          "tensors": [{"name": k, "shape": [int(d) for d in v.shape], "dtype": str(v.dtype)} for k, v in tensors.items()]}
+    if table_dtype != "float32":
+        m["format_version"], m["table_dtype"] = FORMAT_VERSION_16BIT, table_dtype
+        if table_dtype == "bfloat16":
+            for t in m["tensors"]:
+                if is_embedding_rows(t["name"], t["shape"], params["embedding_size"]):
+                    t["encoding"] = "bfloat16"
     return m
 
 
@@ -156,8 +233,11 @@ def latest_bundle(path):
 
 
 def read_bundle(bundle_dir):
-    """-> (manifest, {name: numpy array}).  Refuses (RsxError naming the cause): an unknown format_version, a tensor the
-    manifest lists and the archive lacks or the reverse, a shape or dtype that disagrees with the manifest."""
+    """-> (manifest, {name: numpy array as stored}).  Refuses (RsxError naming the cause): an unknown format_version, a tensor
+    the manifest lists and the archive lacks or the reverse, a shape or dtype that disagrees with the manifest; a version 2
+    manifest whose table_dtype is no 16-bit dtype, a uint16 tensor without an encoding, an encoding on a tensor that is no
+    embedding-row tensor, an embedding-row tensor stored in another dtype than table_dtype, and a version 1 manifest that
+    carries `table_dtype` or an `encoding`."""
     mp = os.path.join(bundle_dir, MANIFEST)
     try:
         with open(mp) as f:
@@ -165,9 +245,15 @@ def read_bundle(bundle_dir):
     except (OSError, ValueError) as e:
         raise _lib.RsxError("bundle %r: cannot read %s (%s)" % (bundle_dir, MANIFEST, e)) from e
     ver = manifest.get("format_version") if isinstance(manifest, dict) else None
-    if ver != FORMAT_VERSION:
-        raise _lib.RsxError("bundle %r: format_version %r is not supported (this reader knows %d)"
-                            % (bundle_dir, ver, FORMAT_VERSION))
+    if ver not in (FORMAT_VERSION, FORMAT_VERSION_16BIT) or isinstance(ver, bool):
+        raise _lib.RsxError("bundle %r: format_version %r is not supported (this reader knows %d and %d)"
+                            % (bundle_dir, ver, FORMAT_VERSION, FORMAT_VERSION_16BIT))
+    table_dtype = manifest.get("table_dtype")
+    if ver == FORMAT_VERSION_16BIT and table_dtype not in TABLE_DTYPES[1:]:
+        raise _lib.RsxError("bundle %r: a format_version %d manifest needs a table_dtype of %s, not %r"
+                            % (bundle_dir, ver, " or ".join(TABLE_DTYPES[1:]), table_dtype))
+    if ver == FORMAT_VERSION and "table_dtype" in manifest:
+        raise _lib.RsxError("bundle %r: a format_version %d manifest cannot carry table_dtype (%r)" % (bundle_dir, ver, table_dtype))
     if manifest.get("script") not in SCRIPTS:
         raise _lib.RsxError("bundle %r: unknown script %r" % (bundle_dir, manifest.get("script")))
     try:
@@ -188,6 +274,20 @@ def read_bundle(bundle_dir):
                                 % (bundle_dir, k, list(arrays[k].shape), MANIFEST, list(t["shape"])))
         if str(arrays[k].dtype) != t["dtype"]:
             raise _lib.RsxError("bundle %r: tensor %r has dtype %s, %s says %s" % (bundle_dir, k, arrays[k].dtype, MANIFEST, t["dtype"]))
+    D = (manifest.get("params") or {}).get("embedding_size")
+    stored = {"bfloat16": ("uint16", "bfloat16"), "float16": ("float16", None)}.get(table_dtype)      # (dtype, encoding)
+    for k, t in listed.items():
+        enc = t.get("encoding")
+        rows = D is not None and is_embedding_rows(k, t["shape"], D)
+        if "encoding" in t and ver == FORMAT_VERSION:
+            raise _lib.RsxError("bundle %r: tensor %r carries an encoding (%r) in a format_version %d manifest" % (bundle_dir, k, enc, ver))
+        if "encoding" in t and not rows:
+            raise _lib.RsxError("bundle %r: tensor %r carries an encoding (%r) but is no embedding-row tensor" % (bundle_dir, k, enc))
+        if t["dtype"] == "uint16" and enc is None:
+            raise _lib.RsxError("bundle %r: tensor %r is uint16 without an encoding" % (bundle_dir, k))
+        if rows and stored is not None and (t["dtype"], enc) != stored:
+            raise _lib.RsxError("bundle %r: embedding-row tensor %r is stored as %s (encoding %r), the bundle's table_dtype is %s"
+                                % (bundle_dir, k, t["dtype"], enc, table_dtype))
     return manifest, arrays
 
 
@@ -238,9 +338,12 @@ def store_variables_names(store):
     return names + ["dense." + k for k in store.dense.params]
 
 
-def export_estimator(est, export_dir_base):
-    """Estimator.export_savedmodel's body: the latest checkpoint of est.model_dir as a bundle -> its directory."""
+def export_estimator(est, export_dir_base, table_dtype="float32"):
+    """Estimator.export_savedmodel's body: the latest checkpoint of est.model_dir as a bundle -> its directory.  table_dtype
+    "bfloat16" / "float16": every embedding-row tensor is rounded to it (`quantize_rows`) and stored in it."""
     from . import checkpoint
+    if table_dtype not in TABLE_DTYPES:
+        raise _lib.RsxError("export: table dtype %r is none of %s" % (table_dtype, ", ".join(TABLE_DTYPES)))
     script = est.model_fn.__module__.rsplit(".", 1)[-1]
     if script not in SCRIPTS:
         raise _lib.RsxError("export: model_fn of module %r is none of the scripts %s" % (est.model_fn.__module__, ", ".join(SCRIPTS)))
@@ -259,7 +362,9 @@ def export_estimator(est, export_dir_base):
     out = None
     if est._is_chief():                   # replicas are bit-identical: the chief writes (the rule of _save_checkpoint)
         tensors = store_variables(est.store)
-        out = write_bundle(export_dir_base, make_manifest(script, est.params, est.global_step, tensors), tensors)
+        if table_dtype != "float32":
+            tensors = quantize_tensors(tensors, est.params["embedding_size"], table_dtype)
+        out = write_bundle(export_dir_base, make_manifest(script, est.params, est.global_step, tensors, table_dtype), tensors)
         print("INFO:Model exported.", flush=True)
     if est.store.dp is not None:
         est.store.dp.barrier()
@@ -352,7 +457,9 @@ def check_rank_request(u_iid_seq, u_icat_seq, i_id, i_cate, hist_len, n_item, n_
 
 # ---- Predictor ---------------------------------------------------------------------------------------------------------------
 class Predictor:
-    """An exported model ready to answer requests.  See the module docstring for the two paths."""
+    """An exported model ready to answer requests.  See the module docstring for the two paths.  `table_dtype` is the
+    bundle's ("float32" for a version 1 bundle): on the fused path the device holds the table in that dtype; on the layers
+    path a 16-bit table is widened to fp32 on the host (the rounded values, no memory saved, `rank_candidates` unchanged)."""
 
     MAX_GRAPHS = 32            # request sizes that get a captured graph at most (Estimator.MAX_INFER_GRAPHS' twin)
 
@@ -372,6 +479,7 @@ class Predictor:
         self.manifest, arrays = read_bundle(self.bundle_dir)
         m = self.manifest
         self.script, self.global_step = m["script"], int(m["global_step"])
+        self.table_dtype = m.get("table_dtype", "float32")
         self.signature = SIGNATURE
         self.device = torch.device(device)
         if self.device.type != "cuda":
@@ -403,13 +511,15 @@ class Predictor:
     # -- the one-launch path ----------------------------------------------------------------------------------------------
     def _fused_variables(self, arrays, need):
         """The variables of a one-launch model on the device, once: the tables and every dense tensor of `need` in ONE flat
-        buffer (16-byte aligned parts), the row offsets, and the request buffers -> the dense tensors' address by name."""
+        buffer (16-byte aligned parts), the row offsets, and the request buffers -> the dense tensors' address by name.
+        The table goes up in its stored form: fp32, float16, or bfloat16 bit patterns (the model struct's table_dtype)."""
         import torch
         if set(need) != set(arrays):
             raise _lib.RsxError("bundle %r: a %s bundle holds the tensors %s, not %s"
                                 % (self.bundle_dir, self.script, sorted(need), sorted(arrays)))
         dev, lay = self.device, self.layout
-        self._tables = torch.from_numpy(arrays["emb.input_layer.tables"]).to(dev)
+        tables = arrays["emb.input_layer.tables"]
+        self._tables = torch.from_numpy(tables.view(np.int16) if tables.dtype == np.uint16 else tables).to(dev)
         dense = [k for k in need if k.startswith("dense.")]
         offs, n = {}, 0
         for k in dense:
@@ -455,6 +565,7 @@ class Predictor:
         pm.w1_field_mask = lay.field_mask(lin_keys)
         pm.bn_eps = float(m["batch_norm_epsilon"])
         pm.F, pm.D, pm.L = lay.F, D, len(widths)
+        pm.table_dtype = _lib.TABLE_DTYPES[self.table_dtype]
         self._model, self._kernel = pm, "rsx_predict_fm_tower"
         return True
 
@@ -484,6 +595,7 @@ class Predictor:
         pm.wo, pm.bo = ptr("dense.out.W"), ptr("dense.out.b")
         pm.bn_eps = float(m["batch_norm_epsilon"])
         pm.F, pm.D, pm.L, pm.Lc = lay.F, D, len(widths), Lc
+        pm.table_dtype = _lib.TABLE_DTYPES[self.table_dtype]
         self._model, self._kernel = pm, "rsx_predict_dcn"
         return True
 
@@ -527,7 +639,7 @@ class Predictor:
         params = params_from_manifest(self.manifest, self.max_batch_size)
         est = Estimator(mod.model_fn, None, params, RunConfig(use_hip_graph=self.use_hip_graph, device=str(self.device)))
         _build_store(est, self.script)
-        load_store_variables(est.store, arrays)
+        load_store_variables(est.store, widen_tensors(self.manifest, arrays))      # (16-bit tables: fp32 on the host first)
         torch.cuda.synchronize()
         self._est = est
 

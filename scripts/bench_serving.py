@@ -25,6 +25,15 @@ it, in ONE process, their timed regions alternating, `--repeats` rounds per requ
         B  serving.Predictor.load(..., one_launch=True): the captured graph of ONE rsx_predict_dcn launch
            (csrc/predict_dcn.hip).
 
+    python scripts/bench_serving.py --table_dtype bfloat16|float16 [--model dcn] [the same options]
+        16-bit embedding tables (--export_table_dtype): ONE model exported twice,
+        A  the float32 bundle on the fused path (dcn: one_launch=True),
+        B  the same model exported with the 16-bit dtype, its table on the device in 16 bits;
+        device time per request over graph replays as above, torch.cuda.memory_allocated after each load, and max / mean
+        |prob_B - prob_A| on each request batch (an UNTRAINED, randomly initialised model: not an accuracy figure).
+        With --profile-run / --kernel-stats: the kernel-trace time of every instantiation of the kernel; a request reads
+        B x 39 x 32 B of 16-bit rows (64 B of fp32 rows) + the dense weights once.
+
 Roofline terms (named for what they are): bytes the request needs = B x 39 rows x 64 B + the dense weights once; FLOPs =
 2 x B x (624 x 100 + 100 x 100 + 100) (dcn: 2 x B x (624 x 100 + 100 x 100 + 100 + 624) + 3 x B x 5 x 624 for the cross
 layers); over the kernel time.  At these sizes the kernel is latency-bound: the figure to watch is time per request."""
@@ -112,6 +121,109 @@ def build_dcn(dev, max_batch, export_dir):
     assert pa.path == "layers" and pb.path == "fused", (pa.path, pb.path)
     torch.cuda.synchronize()
     return LayersContender(pa), pb, layout
+
+
+def build_table_dtype(dev, max_batch, export_dir, model, dtype):
+    """-> (Predictor of the float32 bundle, Predictor of the `dtype` bundle of the same model, layout, device bytes of each
+    load): both on the fused path."""
+    import torch
+    from recsys_amd import dcn, deepfm, serving
+    from recsys_amd.estimator import Estimator, ModeKeys, RunConfig
+    from recsys_amd.feature_columns import CriteoLayout, build_feature_columns
+    lin, emb = build_feature_columns(16, "numeric" if model == "dcn" else "indicator_all")
+    params = {"linear_feature_columns": lin, "embedding_feature_columns": emb, "embedding_size": 16, "learning_rate": 1e-3,
+              "dropout": 0.5, "deep_layers": "100,100", "max_batch_size": 64}
+    if model == "dcn":
+        params["cross_layers"] = DCN_CROSS_LAYERS
+    est = Estimator((dcn if model == "dcn" else deepfm).model_fn, None, params,
+                    RunConfig(device=str(dev), seed=1234, use_hip_graph=False))
+    layout = CriteoLayout.from_columns(emb)
+    with torch.no_grad():
+        est._call_model_fn({"ids": torch.zeros(1, layout.F, dtype=torch.int32, device=dev)}, None, ModeKeys.PREDICT)
+        g = torch.Generator(device="cpu").manual_seed(7)          # a served model is a trained one: no all-zero biases
+        for k, p in est.store.dense.params.items():
+            if k.split(".")[-1][0] in "bg":
+                p.add_((torch.rand(p.shape, generator=g) * 0.2 - 0.1).to(dev))
+    da = est.export_savedmodel(os.path.join(export_dir, "float32"))
+    db = est.export_savedmodel(os.path.join(export_dir, dtype), table_dtype=dtype)
+    del est
+    kw = {"one_launch": True} if model == "dcn" else {}
+    preds, mem = [], []
+    for d in (da, db):
+        torch.cuda.synchronize()
+        before = torch.cuda.memory_allocated()
+        preds.append(serving.Predictor.load(d, device=str(dev), max_batch_size=max_batch, **kw))
+        torch.cuda.synchronize()
+        mem.append(torch.cuda.memory_allocated() - before)
+        assert preds[-1].path == "fused", preds[-1].path
+    assert preds[0].table_dtype == "float32" and preds[1].table_dtype == dtype
+    return preds[0], preds[1], layout, mem
+
+
+def capture_predictors(pa, pb, ids):
+    """Warm up and capture the request size on both Predictors -> (A's graph, B's graph, max and mean |prob_B - prob_A|)."""
+    for _ in range(3):                           # eager warm-up, capture + replay, replay
+        a, b = pa.predict({"ids": ids})["prob"], pb.predict({"ids": ids})["prob"]
+    B = ids.shape[0]
+    assert "graph" in pa._graphs[B] and "graph" in pb._graphs[B]
+    d = np.abs(b.astype(np.float64) - a.astype(np.float64))
+    return pa._graphs[B]["graph"], pb._graphs[B]["graph"], float(d.max()), float(d.mean())
+
+
+def table_dtype_stats(a, b_kernel, dense_floats):
+    """--kernel-stats of a --table_dtype --profile-run trace: every instantiation of the kernel (its last template argument
+    is the table dtype: 0 float32, 1 bfloat16, 2 float16) with the bytes a request needs over its time."""
+    import re
+    out = []
+    for name, (calls, _, avg) in sorted(kernel_stats(a.kernel_stats).items()):
+        m = re.search(b_kernel + r"<([\d, ]+)>", name)
+        if not m:
+            continue
+        td = int(m.group(1).split(",")[-1])
+        nbytes = a.profile_run * 39 * (64 if td == 0 else 32) + 4 * dense_floats
+        rec = {"model": a.model, "kernel": b_kernel + "<" + m.group(1) + ">", "table_dtype": ("float32", "bfloat16", "float16")[td],
+               "batch_size": a.profile_run, "calls": calls, "kernel_us_per_request": round(avg / 1e3, 3), "request_bytes": nbytes,
+               "achieved_GBps": round(nbytes / avg, 1)}
+        out.append(rec)
+        print(json.dumps(rec), flush=True)
+    return out
+
+
+def run_table_dtype(a, dev, sizes):
+    import torch
+    with tempfile.TemporaryDirectory() as tmp:
+        pa, pb, layout, mem = build_table_dtype(dev, max(sizes), tmp, a.model, a.table_dtype)
+    if a.profile_run:
+        pa.use_hip_graph = pb.use_hip_graph = False                 # eager: every launch appears in the trace under its name
+        ids = torch.from_numpy(request_ids(layout, a.profile_run, 11)).to(dev)
+        for pr in (pa, pb):
+            for _ in range(a.profile_requests):
+                pr.predict({"ids": ids})
+        torch.cuda.synchronize()
+        return None
+    out = [{"model": a.model, "A_table_dtype": "float32", "B_table_dtype": a.table_dtype,
+            "A_load_device_bytes": mem[0], "B_load_device_bytes": mem[1], "A_table_bytes": pa._tables.numel() * pa._tables.element_size(),
+            "B_table_bytes": pb._tables.numel() * pb._tables.element_size(),
+            "note": "prob_diff figures: an UNTRAINED, randomly initialised model -- what rounding the tables does to its "
+                    "probabilities, not an accuracy figure of a trained one"}]
+    print(json.dumps(out[0]), flush=True)
+    graphs = {B: capture_predictors(pa, pb, request_ids(layout, B, 100 + B)) for B in sizes}     # every size, before any timing
+    for B in sizes:
+        ga, gb, dmax, dmean = graphs[B]
+        for g in (ga, gb):
+            time_replays(g, 200)
+        ta, tb = [], []
+        for _ in range(a.repeats):                 # the contenders alternate within every round
+            ta.append(time_replays(ga, a.replays))
+            tb.append(time_replays(gb, a.replays))
+        ma, mb = float(np.median(ta)), float(np.median(tb))
+        rec = {"model": a.model, "table_dtype": a.table_dtype, "batch_size": B, "A_float32_us": round(ma, 3), "B_16bit_us": round(mb, 3),
+               "B_minus_A_us": round(mb - ma, 3), "A_repeats_us": [round(x, 3) for x in ta], "B_repeats_us": [round(x, 3) for x in tb],
+               "A_spread_us": round(max(ta) - min(ta), 3), "B_spread_us": round(max(tb) - min(tb), 3),
+               "max_abs_prob_diff": dmax, "mean_abs_prob_diff": dmean}
+        out.append(rec)
+        print(json.dumps(rec), flush=True)
+    return out
 
 
 def request_ids(layout, B, seed):
@@ -230,12 +342,16 @@ def main():
     p.add_argument("--profile-run", dest="profile_run", type=int, default=0, help="request size of a rocprofv3 run")
     p.add_argument("--profile-requests", dest="profile_requests", type=int, default=200)
     p.add_argument("--kernel-stats", dest="kernel_stats", default=None)
+    p.add_argument("--table_dtype", choices=("bfloat16", "float16"), default=None,
+                   help="A = the float32 bundle, B = the same model exported with this table dtype, both on the fused path")
     a = p.parse_args()
     dense_floats = 624 * 100 + 100 * 100 + 6 * 100 + 100 + 1 + 3 + 1 + 1
     a_kernels, b_kernel = A_KERNELS, B_KERNEL
     if a.model == "dcn":
         dense_floats = 624 * 100 + 100 * 100 + 6 * 100 + 2 * DCN_CROSS_LAYERS * 624 + 100 + 624 + 1
         a_kernels, b_kernel = A_KERNELS_DCN, B_KERNEL_DCN
+    if a.kernel_stats and a.table_dtype:
+        return table_dtype_stats(a, b_kernel, dense_floats)
     if a.kernel_stats:                            # no GPU needed: the trace's own numbers
         B, n = a.profile_run, a.profile_requests
         st = kernel_stats(a.kernel_stats)
@@ -255,6 +371,8 @@ def main():
         return layer_probe()
     dev = torch.device("cuda")
     sizes = [int(s) for s in a.sizes.split(",")] if not a.profile_run else [a.profile_run]
+    if a.table_dtype:
+        return run_table_dtype(a, dev, sizes)
     with tempfile.TemporaryDirectory() as tmp:
         est, pred, layout = (build_dcn if a.model == "dcn" else build)(dev, max(sizes + [a.e2e_rows]), os.path.join(tmp, "export"))
     if a.profile_run:
