@@ -1120,6 +1120,69 @@ int64_t rsx_criteo_encode_h(const float* label_h, const float* cont_h, const uin
 int64_t rsx_din_encode_h(const int64_t* label_h, const int64_t* i_id_h, const int64_t* i_cate_h, const int64_t* hist_i_h,
                          const int64_t* hist_c_h, int64_t n, int P, int keep_padding, uint8_t* out_h, int64_t cap);
 
+/* ---------------------------------------------------------------------------------------------
+ * Device parse of a serving request (since rsx_version() 102): serialized tf.train.Example records of the Criteo-39 schema
+ * -> ids [n, F] in ONE launch, to run in front of rsx_predict_fm_tower / rsx_predict_dcn (the ParseExample that TF-Serving
+ * runs inside the served graph, deepfm/deepfm.py:220-234).  Contract: DECLINE, NEVER GUESS.  For any bytes, status[r] is
+ *   RSX_PARSE_OK               ids[r, :] are exactly what rsx_criteo_parse_h (label optional, bit 16 of `threads`) writes;
+ *   anything else              ids[r, :] were NOT written, and the caller parses the request on the host:
+ *   RSX_PARSE_MALFORMED        the host parser refuses the record (RSX_EDATA): a truncated varint, a length past the end of its
+ *                              parent, an unknown wire type in the Example, a Features message or a map entry
+ *   RSX_PARSE_MISSING_NUMERIC  one of `_c1` .. `_c13` has no value (RSX_EDATA on the host too)
+ *   RSX_PARSE_TOO_LONG         the record is longer than RSX_PARSE_MAX_RECORD bytes (the kernel's LDS stage); the host may accept it
+ *   RSX_PARSE_BAD_OFFSETS      offs[r] < 0, offs[r + 1] < offs[r] or offs[r + 1] > buf_bytes: no byte of the record was read
+ *   RSX_PARSE_BAD_SPEC         a slot_src outside 1 .. 39, a categorical slot with slot_rows <= 0, thr_off going backwards
+ * What is matched: keys `_c0` .. `_c39` only (`_c0` optional and unused, other keys ignored); an absent categorical takes
+ * null_hash; of duplicated keys the last entry that yields a value wins; a float packed (first 4 bytes) or unpacked (wire type
+ * 5); a bytes value of length 0; repeated Example.features and map-entry fields; over-long varints.  Categorical id =
+ * Fingerprint64(bytes) % slot_rows (all four length branches, 64-bit integer arithmetic).  Numeric id: v = x + shift (one
+ * fp32 add), id = (v != v || v < 0) ? nb : #{k : thr[k] <= v}, where thr[k] = rsx_log_thresholds_h's threshold of boundary k:
+ * equal to #{k : b_k <= logf(v)} of rsx_bucketize_log_h as long as the host's logf is monotone, without a device logf.
+ * rsx_parse_spec: slot_src[F] (source field 1 .. 39 of each slot), slot_rows[F], thr / thr_off[F + 1] (thresholds of the numeric
+ * slots, thr_off[s + 1] - thr_off[s] of them for slot s, 0 for a categorical one), shift[13] -- DEVICE pointers for
+ * rsx_criteo_parse_examples, host pointers for rsx_criteo_parse_dev_h -- F, and null_hash = Fingerprint64("NULL").
+ * buf: the records' bytes, 4-byte aligned, buf_bytes a multiple of 4 that the caller owns IN FULL (a record's last bytes are
+ * read as the aligned 4-byte word that holds them); offs[n + 1] int32: record r is buf[offs[r], offs[r + 1]).
+ * One workgroup of one wave per example: record staged in LDS, lane i takes map entry i.  No atomics, no workspace, no sync;
+ * only ids rows of accepted examples and status[0, n) are written.
+ * Every argument is refused before any device call -- RSX_EINVAL: a NULL buf / offs / spec / ids / status or spec member,
+ * n <= 0, F <= 0, buf_bytes <= 0, above 2^31 - 4 or no multiple of 4, buf / offs / ids / status not 4-byte aligned;
+ * RSX_EUNSUPPORTED outside rsx_criteo_parse_examples_supported(n, F): F > 64.
+ * rsx_criteo_parse_dev_h is the kernel's HOST TWIN: the same byte-level routines (csrc/parse_device.h) and the same decisions
+ * in a plain loop, same arguments as host pointers, same status words.  For tests; the product path does not call it.
+ * ------------------------------------------------------------------------------------------- */
+#define RSX_PARSE_MAX_RECORD 8192
+enum {
+  RSX_PARSE_OK = 0,
+  RSX_PARSE_MALFORMED = 1,
+  RSX_PARSE_MISSING_NUMERIC = 2,
+  RSX_PARSE_TOO_LONG = 3,
+  RSX_PARSE_BAD_OFFSETS = 4,
+  RSX_PARSE_BAD_SPEC = 5
+};
+typedef struct {
+  const int32_t* slot_src;                      /* [F] */
+  const int32_t* slot_rows;                     /* [F] */
+  const float* thr;                             /* thresholds of the numeric slots, concatenated */
+  const int32_t* thr_off;                       /* [F + 1] */
+  const float* shift;                           /* [13] log shift of _c1 .. _c13 */
+  int32_t F;
+  uint64_t null_hash;
+} rsx_parse_spec;
+int rsx_criteo_parse_examples_supported(int n, int F);
+int rsx_criteo_parse_examples(const uint8_t* buf, int64_t buf_bytes, const int32_t* offs, int n, const rsx_parse_spec* spec_h,
+                              int32_t* ids, int32_t* status, rsx_stream_t stream);
+int rsx_criteo_parse_dev_h(const uint8_t* buf_h, int64_t buf_bytes, const int32_t* offs_h, int n,
+                           const rsx_parse_spec* spec_h, int32_t* ids_h, int32_t* status_h);
+/* thr_h[k] = the smallest non-negative fp32 v (bit-pattern order +0 .. +inf) with logf(v) >= boundaries_h[k], by bisection on
+ * this host's logf, verified per boundary (logf(prev(thr)) < b <= logf(thr); RSX_EUNSUPPORTED when that fails).  RSX_EINVAL:
+ * a boundary that is not finite, boundaries that are not sorted.  A boundary above logf(FLT_MAX) gets +inf.
+ * rsx_bucketize_thr_h: rsx_bucketize_log_h's ids from such thresholds (the routine the device runs), for tests.
+ * rsx_fingerprint64_dev_h: csrc/parse_device.h's Fingerprint64 (n < 2^32), for tests.                              */
+int rsx_log_thresholds_h(const float* boundaries_h, int nb, float* thr_h);
+int rsx_bucketize_thr_h(const float* x_h, int64_t n, const float* thr_h, int nb, float shift, int32_t* out_h);
+uint64_t rsx_fingerprint64_dev_h(const uint8_t* s_h, size_t n);
+
 /* bf16 MFMA path of the CIN layer (north_star: "MFMA only on the CIN feature-map contraction where it is genuinely a
  * dense bf16 GEMM"; xdeepfm/xdeepfm.py:145-169).  Same contract as rsx_cin_layer_fwd / rsx_cin_layer_bwd, with the
  * filter W replaced by a bf16 image prepared once per step:

@@ -218,6 +218,15 @@ class PredictDinModel(C.Structure):
                 ("ld", C.c_int32 * PREDICT_MAX_LAYERS)]
 
 
+class ParseSpec(C.Structure):
+    """include/rsx.h rsx_parse_spec (the device parse of serialized Criteo Examples)."""
+    _fields_ = [("slot_src", C.c_void_p), ("slot_rows", C.c_void_p), ("thr", C.c_void_p), ("thr_off", C.c_void_p),
+                ("shift", C.c_void_p), ("F", C.c_int32), ("null_hash", C.c_uint64)]
+
+
+PARSE_MAX_RECORD = 8192               # include/rsx.h RSX_PARSE_MAX_RECORD
+(PARSE_OK, PARSE_MALFORMED, PARSE_MISSING_NUMERIC, PARSE_TOO_LONG, PARSE_BAD_OFFSETS, PARSE_BAD_SPEC) = range(6)
+
 ADAM_STATE_WORDS = 4 + 32 * 32        # include/rsx.h RSX_ADAM_STATE_WORDS
 
 
@@ -376,6 +385,12 @@ _SIGS = {
     "rsx_predict_dcn": (_I, [C.POINTER(PredictDcnModel), _P, _P, _I, _P]),
     "rsx_predict_din_rank_supported": (_I, [_I] * 7 + [_P]),
     "rsx_predict_din_rank": (_I, [C.POINTER(PredictDinModel)] + [_P] * 5 + [_I, _I, _I, _P]),
+    "rsx_criteo_parse_examples_supported": (_I, [_I, _I]),
+    "rsx_criteo_parse_examples": (_I, [_P, C.c_int64, _P, _I, C.POINTER(ParseSpec), _P, _P, _P]),
+    "rsx_criteo_parse_dev_h": (_I, [_P, C.c_int64, _P, _I, C.POINTER(ParseSpec), _P, _P]),
+    "rsx_log_thresholds_h": (_I, [_P, _I, _P]),
+    "rsx_bucketize_thr_h": (_I, [_P, C.c_int64, _P, _I, _F, _P]),
+    "rsx_fingerprint64_dev_h": (C.c_uint64, [_P, C.c_size_t]),
     "rsx_eval_metrics_state_words": (_I, [_I]),
     "rsx_eval_metrics_update": (_I, [_P, _P, _P, _I, _P, _P, _I, _P]),
 }

@@ -64,6 +64,30 @@ class _CriteoParser:
         return {"ids": ids, "cont_log": cont}, label
 
 
+def log_thresholds(boundaries):
+    """rsx_log_thresholds_h: per boundary b the smallest non-negative fp32 v with logf(v) >= b on THIS host's logf (verified
+    per boundary).  Raises RsxError for unsorted or non-finite boundaries, or when the verification fails."""
+    bd = np.ascontiguousarray(boundaries, np.float32).reshape(-1)
+    thr = np.empty(bd.size, np.float32)
+    check(lib().rsx_log_thresholds_h(_p(bd), int(bd.size), _p(thr)), "rsx_log_thresholds_h")
+    return thr
+
+
+def criteo_parse_spec(layout):
+    """What the device parse (include/rsx.h rsx_parse_spec) needs of a Criteo layout, as host arrays: slot_src, slot_rows,
+    thr / thr_off (the logf thresholds of every numeric slot's boundaries), shift, F, null_hash.  Raises RsxError when a slot's
+    boundaries cannot be turned into thresholds."""
+    cp = _CriteoParser(layout, 1, label_optional=True)
+    thr, off = [], [0]
+    for c in layout.columns:
+        if c.boundaries is not None:
+            thr += list(log_thresholds(c.boundaries))
+        off.append(len(thr))
+    return {"slot_src": cp.slot_src, "slot_rows": cp.slot_rows, "thr": np.array(thr if thr else [0.0], np.float32),
+            "thr_off": np.array(off, np.int32), "shift": cp.shift, "F": int(layout.F),
+            "null_hash": int(lib().rsx_fingerprint64_h(b"NULL", 4))}
+
+
 def _batched(parse, filenames, batch_size, num_epochs, chunk_records=65536):
     """map(parse) -> batch: record streams of consecutive files are concatenated before batching, like TFRecordDataset."""
     epoch = 0

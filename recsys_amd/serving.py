@@ -12,6 +12,10 @@ The reference exports a SavedModel whose serving signature parses serialized `tf
               carries "encoding": "bfloat16".  First-order weights, din.py's bias table and the dense tensors stay fp32.  A
               float32 export is format_version 1, byte for byte what it was before the option existed.
   Predictor   loads a bundle and answers `predict_examples(list of serialized Examples)` / `predict(features)`.
+              `Predictor.load(..., device_parse=True)` (opt-in; Criteo bundles on the fused path, `parse_path` == "device"):
+              predict_examples ships the request's BYTES and rsx_criteo_parse_examples (csrc/parse_examples.hip) turns them
+              into the ids on the device, two launches per request in one graph; the ids -- so the probabilities -- are the
+              host parse's bit for bit, and whatever the device declines is parsed on the host as before.
               path == "fused":  fm.py / deepfm.py bundles inside the kernel's envelope -- the variables live on the device once
                                 and a batch is ONE launch of rsx_predict_fm_tower (csrc/predict.hip), captured per request size
                                 into a HIP graph over static input buffers.
@@ -467,12 +471,20 @@ class Predictor:
         raise TypeError("use Predictor.load(export_dir)")
 
     @classmethod
-    def load(cls, export_dir, device="cuda", max_batch_size=4096, use_hip_graph=True, max_candidates=None, one_launch=False):
+    def load(cls, export_dir, device="cuda", max_batch_size=4096, use_hip_graph=True, max_candidates=None, one_launch=False,
+             device_parse=False, parse_row_bytes=2048):
         """export_dir: a bundle, or the --export_path that holds bundles (the newest is taken).  max_candidates (din.py bundles;
         default max_batch_size): the candidates per user one `rank_candidates` launch takes, longer requests are cut along C.
         one_launch (dcn.py bundles; the other scripts ignore it): answer through rsx_predict_dcn, path == "fused", instead of
         the rebuilt Estimator.  Off by default: the one-launch forward sums in another order than the Estimator's kernels, so
-        it agrees with them to 2e-5, not bit for bit."""
+        it agrees with them to 2e-5, not bit for bit.
+        device_parse (Criteo bundles on the fused path; everything else ignores it, `parse_path` says which): predict_examples
+        ships the request's bytes and a launch of rsx_criteo_parse_examples (csrc/parse_examples.hip) writes the ids in front of
+        the predict launch, both in the graph of the request size.  The ids are the host parser's bit for bit; a chunk with an
+        example the device declines (malformed, a missing numeric, a record above 8 KB) or with more bytes than the staging
+        buffer holds is parsed on the host exactly as without the flag.  Off by default.
+        parse_row_bytes: the staging buffers (one pinned, one on the device) hold max_batch_size * parse_row_bytes request
+        bytes; a Criteo request row is about 0.9 KB (39 entries, 8-byte categorical values), 2048 leaves room for two."""
         import torch
         self = object.__new__(cls)
         self.bundle_dir = latest_bundle(export_dir)
@@ -502,6 +514,9 @@ class Predictor:
         self.max_candidates = self.max_batch_size if max_candidates is None else int(max_candidates)
         if self.max_candidates < 1:
             raise _lib.RsxError("Predictor: max_candidates must be at least 1")
+        self.parse_path, self._dp = "host", None
+        if device_parse:
+            self._device_parse_setup(int(parse_row_bytes))
         self.rank_path = None
         self._rank = None
         if self.script == "din":
@@ -605,31 +620,103 @@ class Predictor:
         _lib.check(fn(C.byref(self._model), self._ids.data_ptr(), self._prob.data_ptr(), int(n),
                       torch.cuda.current_stream().cuda_stream), self._kernel)
 
-    def _fused_chunk(self, ids):
-        """ids: int32 [n, F] (host or device), n <= max_batch_size -> prob [n] (a view of the Predictor's output buffer,
-        valid until the next call)."""
+    def _run(self, key, launch):
+        """`launch()` eagerly, or as the captured graph of `key`: warm-up on the first request, capture on the second."""
         import torch
-        n = int(ids.shape[0])
-        self._ids[:n].copy_(ids, non_blocking=True)
-        g = self._graphs.get(n) if self.use_hip_graph else None
+        g = self._graphs.get(key) if self.use_hip_graph else None
         if g is None and self.use_hip_graph and self._n_graphs < self.MAX_GRAPHS:
-            g = self._graphs[n] = {"warm": 0}
+            g = self._graphs[key] = {"warm": 0}
             self._n_graphs += 1
         if g is None:                       # graphs off, or a serving loop with ever-new request sizes: eager
-            self._launch(n)
+            launch()
         elif "graph" in g:
             g["graph"].replay()
         elif g["warm"] < 1:                 # first request of this size: eager
             g["warm"] += 1
-            self._launch(n)
+            launch()
         else:
             torch.cuda.synchronize()
             graph = torch.cuda.CUDAGraph()
             with torch.cuda.graph(graph):
-                self._launch(n)
+                launch()
             g["graph"] = graph
             graph.replay()                  # capture executes nothing
+
+    def _fused_chunk(self, ids):
+        """ids: int32 [n, F] (host or device), n <= max_batch_size -> prob [n] (a view of the Predictor's output buffer,
+        valid until the next call)."""
+        n = int(ids.shape[0])
+        self._ids[:n].copy_(ids, non_blocking=True)
+        self._run(n, lambda: self._launch(n))
         return self._prob[:n]
+
+    # -- the device parse (device_parse=True) --------------------------------------------------------------------------------
+    def _device_parse_setup(self, row_bytes):
+        """Inside the envelope (a Criteo fm.py / deepfm.py / one_launch dcn.py bundle on the fused path, F <= 64, boundaries
+        that give thresholds): the spec on the device and the two staging buffers, parse_path = "device".  Outside: nothing,
+        the host parse stays."""
+        import torch
+        from . import input_pipeline as ip
+        if self.path != "fused" or self.manifest["feature_set"] != "criteo" or row_bytes < 1:
+            return
+        lay, B = self.layout, self.max_batch_size
+        if not _lib.lib().rsx_criteo_parse_examples_supported(B, lay.F):
+            return
+        try:
+            a = ip.criteo_parse_spec(lay)
+        except _lib.RsxError:               # boundaries without thresholds (unsorted, not finite): the host parse
+            return
+        dev = self.device
+        keep = {k: torch.from_numpy(a[k]).to(dev) for k in ("slot_src", "slot_rows", "thr", "thr_off", "shift")}
+        sp = _lib.ParseSpec()
+        for k, t in keep.items():
+            setattr(sp, k, t.data_ptr())
+        sp.F, sp.null_hash = lay.F, a["null_hash"]
+        # one staging buffer: int32 offs[n + 1] | (16-byte aligned) the request's bytes | >= 64 bytes of slack
+        cap = B * row_bytes
+        size = (self._dp_bytes_at(B) + cap + 64 + 15) & ~15
+        pinned = torch.empty(size, dtype=torch.uint8).pin_memory()
+        # prob [n] | status int32 [n] come back in ONE copy: the output buffer doubles, the status words follow the n probs
+        self._prob = torch.zeros(2 * B, dtype=torch.float32, device=dev)
+        self._dp = {"spec": sp, "keep": keep, "cap": cap, "size": size, "pinned": pinned, "host": pinned.numpy(),
+                    "stage": torch.zeros(size, dtype=torch.uint8, device=dev)}
+        self.parse_path = "device"
+
+    @staticmethod
+    def _dp_bytes_at(n):
+        """Where the request bytes of an n-row request start in the staging buffer."""
+        return (4 * (n + 1) + 15) & ~15
+
+    def _parse_launch(self, n):
+        import torch
+        d = self._dp
+        at = self._dp_bytes_at(n)
+        base = d["stage"].data_ptr()
+        _lib.check(_lib.lib().rsx_criteo_parse_examples(base + at, (d["size"] - at) & ~3, base, int(n), C.byref(d["spec"]),
+                                                       self._ids.data_ptr(), self._prob.data_ptr() + 4 * n,
+                                                       torch.cuda.current_stream().cuda_stream), "rsx_criteo_parse_examples")
+        self._launch(n)
+
+    def _device_parse_chunk(self, chunk):
+        """One chunk of serialized Examples -> prob [n] numpy, or None when the chunk has to be parsed on the host (more
+        bytes than the staging buffer holds, or an example the device declined)."""
+        d, n = self._dp, len(chunk)
+        lens = np.fromiter((len(x) for x in chunk), np.int64, n)
+        total = int(lens.sum())
+        if total > d["cap"]:
+            return None
+        at = self._dp_bytes_at(n)
+        offs = d["host"][:4 * (n + 1)].view(np.int32)
+        offs[0] = 0
+        np.cumsum(lens, out=offs[1:])
+        d["host"][at:at + total] = np.frombuffer(b"".join(chunk), np.uint8)
+        used = (at + total + 3) & ~3
+        d["stage"][:used].copy_(d["pinned"][:used], non_blocking=True)       # the ONE H2D copy: offs and the bytes in use
+        self._run(("examples", n), lambda: self._parse_launch(n))
+        out = self._prob[:2 * n].cpu().numpy()                               # prob | status in one D2H copy
+        if out[n:].view(np.int32).any():
+            return None
+        return out[:n]
 
     # -- the Estimator path -----------------------------------------------------------------------------------------------
     def _layers_setup(self, arrays):
@@ -805,9 +892,17 @@ class Predictor:
         serialized = list(serialized)
         if not serialized:
             return {"prob": np.zeros(0, np.float32)}
+        import torch
         out = []
         for s in range(0, len(serialized), self.max_batch_size):
-            out.append(self.predict(self._parse(serialized[s:s + self.max_batch_size]))["prob"])
+            chunk = serialized[s:s + self.max_batch_size]
+            prob = None
+            if self._dp is not None:
+                with torch.no_grad():
+                    prob = self._device_parse_chunk(chunk)
+            if prob is None:                # the host parse: no device parse, a chunk over the byte budget, a declined example
+                prob = self.predict(self._parse(chunk))["prob"]
+            out.append(prob)
         return {"prob": np.concatenate(out)}
 
 

@@ -34,6 +34,15 @@ it, in ONE process, their timed regions alternating, `--repeats` rounds per requ
         With --profile-run / --kernel-stats: the kernel-trace time of every instantiation of the kernel; a request reads
         B x 39 x 32 B of 16-bit rows (64 B of fp32 rows) + the dense weights once.
 
+    python scripts/bench_serving.py --device_parse [--parse_sizes 1,16,200,4096] [--e2e_calls 300] [--repeats 3]
+        `predict_examples` end to end (wall clock, host to host, around a synchronise) of ONE exported deepfm.py bundle,
+        A  serving.Predictor as it loads by default: the request parsed on the host (rsx_criteo_parse_h), ids shipped, one launch;
+        B  serving.Predictor.load(..., device_parse=True): the request's bytes shipped, rsx_criteo_parse_examples + the predict
+           launch in one graph (csrc/parse_examples.hip),
+        alternating within every repeat at every request size, with the method of the predict_examples_rows line; the
+        probabilities must be equal bit for bit.  Then a one-off split of A at 200 rows: the host parse alone, and everything
+        else (predict() on the parsed ids).
+
 Roofline terms (named for what they are): bytes the request needs = B x 39 rows x 64 B + the dense weights once; FLOPs =
 2 x B x (624 x 100 + 100 x 100 + 100) (dcn: 2 x B x (624 x 100 + 100 x 100 + 100 + 624) + 3 x B x 5 x 624 for the cross
 layers); over the kernel time.  At these sizes the kernel is latency-bound: the figure to watch is time per request."""
@@ -226,6 +235,59 @@ def run_table_dtype(a, dev, sizes):
     return out
 
 
+def run_device_parse(a, dev):
+    import torch
+    from recsys_amd import serving
+    sizes = [int(x) for x in a.parse_sizes.split(",")]
+    with tempfile.TemporaryDirectory() as tmp:
+        est, host, layout = build(dev, max(sizes), os.path.join(tmp, "export"))
+        del est
+        devp = serving.Predictor.load(host.bundle_dir, device=str(dev), max_batch_size=max(sizes), device_parse=True)
+    assert host.parse_path == "host" and devp.parse_path == "device"
+
+    def wall(fn, calls):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(calls):
+            fn()                                   # (ends in a device-to-host copy: synchronises)
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) / calls * 1e6
+
+    out = []
+    for n in sizes:
+        reqs = serialized_requests(n)
+        for _ in range(3):                         # eager warm-up, capture + replay, replay
+            pa, pb = host.predict_examples(reqs)["prob"], devp.predict_examples(reqs)["prob"]
+        assert np.array_equal(pa.view(np.uint32), pb.view(np.uint32)), n
+        calls = max(20, min(a.e2e_calls, 100000 // n))
+        ta, tb = [], []
+        for _ in range(a.repeats):                 # the contenders alternate within every repeat
+            ta.append(wall(lambda: host.predict_examples(reqs), calls))
+            tb.append(wall(lambda: devp.predict_examples(reqs), calls))
+        ma, mb = float(np.median(ta)), float(np.median(tb))
+        rec = {"predict_examples_rows": n, "request_bytes": sum(map(len, reqs)), "calls": calls, "A_host_parse_us": round(ma, 1),
+               "B_device_parse_us": round(mb, 1), "B_over_A": round(mb / ma, 4), "A_repeats_us": [round(x, 1) for x in ta],
+               "B_repeats_us": [round(x, 1) for x in tb], "A_spread_us": round(max(ta) - min(ta), 1),
+               "B_spread_us": round(max(tb) - min(tb), 1), "bit_identical": True}
+        out.append(rec)
+        print(json.dumps(rec), flush=True)
+    reqs = serialized_requests(200)                # the split of the host path: the parse alone, and everything else
+    feats = host._parse(reqs)
+    host.predict(feats)
+    tp, tr, tt = [], [], []
+    for _ in range(a.repeats):
+        tp.append(wall(lambda: host._parse(reqs), a.e2e_calls))
+        tr.append(wall(lambda: host.predict(feats), a.e2e_calls))
+        tt.append(wall(lambda: host.predict_examples(reqs), a.e2e_calls))
+    rec = {"host_path_split_rows": 200, "parse_alone_us": round(float(np.median(tp)), 1),
+           "everything_else_us": round(float(np.median(tr)), 1), "predict_examples_us": round(float(np.median(tt)), 1),
+           "parse_repeats_us": [round(x, 1) for x in tp], "else_repeats_us": [round(x, 1) for x in tr],
+           "total_repeats_us": [round(x, 1) for x in tt]}
+    out.append(rec)
+    print(json.dumps(rec), flush=True)
+    return out
+
+
 def request_ids(layout, B, seed):
     from recsys_amd import synthetic
     return synthetic.criteo_id_batches(layout, 1, B, seed=seed)[0][0]
@@ -344,6 +406,9 @@ def main():
     p.add_argument("--kernel-stats", dest="kernel_stats", default=None)
     p.add_argument("--table_dtype", choices=("bfloat16", "float16"), default=None,
                    help="A = the float32 bundle, B = the same model exported with this table dtype, both on the fused path")
+    p.add_argument("--device_parse", action="store_true",
+                   help="predict_examples end to end: A = the host parse, B = Predictor.load(..., device_parse=True)")
+    p.add_argument("--parse_sizes", default="1,16,200,4096")
     a = p.parse_args()
     dense_floats = 624 * 100 + 100 * 100 + 6 * 100 + 100 + 1 + 3 + 1 + 1
     a_kernels, b_kernel = A_KERNELS, B_KERNEL
@@ -373,6 +438,8 @@ def main():
     sizes = [int(s) for s in a.sizes.split(",")] if not a.profile_run else [a.profile_run]
     if a.table_dtype:
         return run_table_dtype(a, dev, sizes)
+    if a.device_parse:
+        return run_device_parse(a, dev)
     with tempfile.TemporaryDirectory() as tmp:
         est, pred, layout = (build_dcn if a.model == "dcn" else build)(dev, max(sizes + [a.e2e_rows]), os.path.join(tmp, "export"))
     if a.profile_run:
