@@ -30,9 +30,9 @@ __global__ __launch_bounds__(PR_T) void predict_fm_tower_k(const PredictArgs p) 
   extern __shared__ __attribute__((aligned(16))) float lds[];
   const int tid = threadIdx.x;
   const int row0 = blockIdx.x * PR_ROWS;
-  const int F = p.F, ldx = p.ldx;
+  const int F = p.F, ldx = p.t.ldx;
   float* X = lds;                                        // [16][ldx]: the examples' rows, field-major (= E.reshape(B, F * 16))
-  float* ys = lds + p.oY;                                // y1 [16] | y2 [16]
+  float* ys = lds + p.t.oY;                              // y1 [16] | y2 [16]
   // ---- gather + first-order sum + FM term (the lane mapping of gather_device.h on half a wave per example): thread =
   // (example r, field lane j, float4 quarter q), fields j, j + 8, ...; ids and offsets first, then every row load, then the
   // stores and sums in ascending f.  Rows past the batch take the last example's ids (never ids past B); their outputs are
@@ -85,48 +85,19 @@ __global__ __launch_bounds__(PR_T) void predict_fm_tower_k(const PredictArgs p) 
     }
   }
   __syncthreads();
-  // ---- the tower: activation tiles ping-pong between two LDS buffers ----
-  float* A0 = lds + p.oA0;
-  float* A1 = lds + p.oA1;
-  float* part = lds + p.oP;
-  const int lda = p.lda;
-  if (p.L > 0)
-    dense_bn_layer(X, ldx, 16 * F, p.W[0], p.b[0], p.gamma[0], p.beta[0], p.bn_rstd, p.N[0], p.ksplit[0], part, A0, lda, tid);
-  if (p.L > 1)
-    dense_bn_layer(A0, lda, p.N[0], p.W[1], p.b[1], p.gamma[1], p.beta[1], p.bn_rstd, p.N[1], p.ksplit[1], part, A1, lda, tid);
-  if (p.L > 2)
-    dense_bn_layer(A1, lda, p.N[1], p.W[2], p.b[2], p.gamma[2], p.beta[2], p.bn_rstd, p.N[2], p.ksplit[2], part, A0, lda, tid);
-  // ---- the 1-unit layer, the logits layer, sigmoid: thread (r, d) of the first 256; the 16 lanes of an example are an
-  // aligned group of a wave, so the xor-butterfly stays inside it ----
+  // ---- the tower, then the 1-unit layer, the logits layer, sigmoid: thread (r, d) of the first 256 ----
+  const float* AL = run_tower(p.t, lds, 16 * F, tid);
   if (tid < 256) {
     const int r = tid >> 4, d = tid & 15;
     const float t0 = fmaxf(ys[r] + (p.c0 != nullptr ? p.c0[0] : 0.f), 0.f);
     float z = p.wo[0] * t0 + p.wo[1] * ys[16 + r];
-    if (p.L > 0) {
-      const float* o = (p.L == 2 ? A1 : A0) + r * lda;
-      const int NL = p.L == 1 ? p.N[0] : (p.L == 2 ? p.N[1] : p.N[2]);
-      float u = 0.f;
-      for (int n = d; n < NL; n += 16) u += o[n] * p.wd[n];
-#pragma unroll
-      for (int m = 1; m < 16; m <<= 1) u += __shfl_xor(u, m);
-      z += p.wo[2] * fmaxf(u + p.bd[0], 0.f);
+    if (p.t.L > 0) {
+      const int NL = p.t.L == 1 ? p.t.N[0] : (p.t.L == 2 ? p.t.N[1] : p.t.N[2]);
+      z += p.wo[2] * fmaxf(head_dot16(AL + r * p.t.lda, p.wd, NL, d) + p.bd[0], 0.f);
     }
     z += p.bo[0];
     if (d == 0 && row0 + r < p.B) p.prob[row0 + r] = 1.f / (1.f + expf(-z));
   }
-}
-
-// The raised LDS limit is a property of a kernel FUNCTION: every instantiation asks for its own, once.
-template <int TD>
-int launch_fm_tower(const PredictArgs& p, const size_t lds, hipStream_t stream) {
-  if (lds > 64 * 1024) {
-    static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(predict_fm_tower_k<TD>),
-                                                       hipFuncAttributeMaxDynamicSharedMemorySize, PR_MAX_LDS);
-    if (attr != hipSuccess) return RSX_EUNSUPPORTED;
-  }
-  RSX_LAUNCH(predict_fm_tower_k<TD>, dim3((p.B + PR_ROWS - 1) / PR_ROWS), dim3(PR_T), lds, stream, p);
-  RSX_CHECK_LAUNCH();
-  return RSX_OK;
 }
 
 }  // namespace
@@ -136,38 +107,20 @@ extern "C" int rsx_predict_fm_tower_supported(int B, int F, int D, int L, const 
 }
 
 extern "C" int rsx_predict_fm_tower(const rsx_predict_model* m, const int32_t* ids, float* prob, int B, rsx_stream_t stream) {
-  if (!m || !ids || !prob || B <= 0) return RSX_EINVAL;
-  if (!m->tables || !m->row_off || !m->wo || !m->bo || m->F <= 0 || m->D <= 0 || m->L < 0) return RSX_EINVAL;
-  if (!(m->bn_eps >= 0.f) || !(m->bn_eps < INFINITY)) return RSX_EINVAL;
-  if (m->L <= RSX_PREDICT_MAX_LAYERS) {
-    for (int l = 0; l < m->L; ++l) {
-      if (!m->W[l] || !m->b[l] || m->widths[l] <= 0) return RSX_EINVAL;
-      if ((m->gamma[l] == nullptr) != (m->beta[l] == nullptr)) return RSX_EINVAL;
-    }
-    if (m->L > 0 && (!m->wd || !m->bd)) return RSX_EINVAL;
-  }
-  if (!table_dtype_known(m->table_dtype)) return RSX_EINVAL;
-  if (!al16(m->tables)) return RSX_EINVAL;               // rows are read as float4 (16-bit rows: 8 bytes of a 32-byte row)
+  if (!m || !ids || !prob || B <= 0 || !tower_model_valid(m)) return RSX_EINVAL;
+  if (m->L > 0 && m->L <= RSX_PREDICT_MAX_LAYERS && (!m->wd || !m->bd)) return RSX_EINVAL;
   PredictArgs p;
-  const long long fl = predict_lds_floats(B, m->F, m->D, m->L, m->widths, &p);
+  const long long fl = predict_lds_floats(B, m->F, m->D, m->L, m->widths, &p.t);
   if (fl < 0) return RSX_EUNSUPPORTED;
+  fill_tower(&p.t, m);
   p.tables = m->tables; p.w1 = m->w1; p.row_off = m->row_off; p.ids = ids;
-  for (int l = 0; l < RSX_PREDICT_MAX_LAYERS; ++l) {
-    const bool on = l < m->L;
-    p.W[l] = on ? m->W[l] : nullptr; p.b[l] = on ? m->b[l] : nullptr;
-    p.gamma[l] = on ? m->gamma[l] : nullptr; p.beta[l] = on ? m->beta[l] : nullptr;
-    p.N[l] = on ? m->widths[l] : 0;
-    if (!on) p.ksplit[l] = 1;
-  }
   p.wd = m->wd; p.bd = m->bd; p.c0 = m->c0; p.wo = m->wo; p.bo = m->bo;
   p.prob = prob;
   p.w1_mask = m->w1_field_mask;
-  p.bn_rstd = 1.0f / sqrtf(1.0f + m->bn_eps);
-  p.B = B; p.F = m->F; p.L = m->L;
+  p.B = B; p.F = m->F;
+  const unsigned grid = (B + PR_ROWS - 1) / PR_ROWS;
   const size_t lds = (size_t)fl * sizeof(float);
-  switch (m->table_dtype) {
-    case RSX_TABLE_BF16: return launch_fm_tower<RSX_TABLE_BF16>(p, lds, rsx_s(stream));
-    case RSX_TABLE_F16: return launch_fm_tower<RSX_TABLE_F16>(p, lds, rsx_s(stream));
-    default: return launch_fm_tower<RSX_TABLE_F32>(p, lds, rsx_s(stream));
-  }
+  return dispatch_table_dtype(m->table_dtype, [&](auto td) {
+    return launch_big_lds<predict_fm_tower_k<decltype(td)::value>>(p, grid, PR_T, lds, rsx_s(stream));
+  });
 }

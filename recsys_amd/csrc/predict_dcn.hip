@@ -25,17 +25,11 @@ constexpr int DCN_MAX_LC = 8;                  // cross.hip's CROSS_MAX_L
 
 struct PredictDcnArgs {
   const void* tables; const int32_t* row_off; const int32_t* ids;   // tables: [R, 16] of the kernel's TD
-  const float* W[RSX_PREDICT_MAX_LAYERS]; const float* b[RSX_PREDICT_MAX_LAYERS];
-  const float* gamma[RSX_PREDICT_MAX_LAYERS]; const float* beta[RSX_PREDICT_MAX_LAYERS];
+  TowerArgs t;                                 // t.L >= 1; t.oY: cz [16]
   const float* cw; const float* cb;            // cross.W, cross.b [Lc][16 F] (16-byte aligned)
-  const float* wo; const float* bo;            // out.W [N[L-1] + 16 F], out.b [1]
+  const float* wo; const float* bo;            // out.W [t.N[t.L-1] + 16 F], out.b [1]
   float* prob;
-  float bn_rstd;                               // 1 / sqrt(1 + eps)
-  int B, F, L, Lc;
-  int N[RSX_PREDICT_MAX_LAYERS];
-  int ksplit[RSX_PREDICT_MAX_LAYERS];
-  int ldx, lda;
-  int oA0, oA1, oP, oY;                        // LDS offsets (floats) as in PredictArgs; oY: cz [16]
+  int B, F, Lc;
 };
 
 // v[u] = the 4 floats at base + off[u]: one 16-byte load each (VEC: base 16-byte aligned; off[u] is a multiple of 4) or four
@@ -68,9 +62,10 @@ __global__ __launch_bounds__(PR_T) void predict_dcn_k(const PredictDcnArgs p) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
   const int tid = threadIdx.x;
   const int row0 = blockIdx.x * PR_ROWS;
-  const int F = p.F, ldx = p.ldx;
+  const int F = p.F, ldx = p.t.ldx;
   float* X = lds;                                        // [16][ldx]: the examples' rows, field-major (= x0)
-  float* czs = lds + p.oY;                               // cz [16]
+  float* czs = lds + p.t.oY;                             // cz [16]
+  const int NL = p.t.N[p.t.L - 1];                       // the last width: out.W = [tower part NL | cross part 16 F]
   // ---- gather (predict_fm_tower_k's mapping) + the cross layers on the gathered registers.  Rows past the batch take the
   // last example's ids (never ids past B); their outputs are not stored. ----
   {
@@ -78,7 +73,7 @@ __global__ __launch_bounds__(PR_T) void predict_dcn_k(const PredictDcnArgs p) {
     const int b = row0 + r < p.B ? row0 + r : p.B - 1;
     const uint32_t ib = (uint32_t)b * (uint32_t)F;
     const int dim = 16 * F;
-    const float* __restrict__ wox = p.wo + p.N[p.L - 1];  // out.W's cross part [16 F]
+    const float* __restrict__ wox = p.wo + NL;                // out.W's cross part [16 F]
     const bool wox_vec = (reinterpret_cast<uintptr_t>(wox) & 15u) == 0;
     int row[NU], off[NU];                                // off: this thread's float offset inside a [16 F] vector (clamped)
     bool on[NU];
@@ -132,54 +127,22 @@ __global__ __launch_bounds__(PR_T) void predict_dcn_k(const PredictDcnArgs p) {
     if ((tid & 31) == 0) czs[r] = cz;
   }
   __syncthreads();
-  // ---- the tower: activation tiles ping-pong between two LDS buffers ----
-  float* A0 = lds + p.oA0;
-  float* A1 = lds + p.oA1;
-  float* part = lds + p.oP;
-  const int lda = p.lda;
-  dense_bn_layer(X, ldx, 16 * F, p.W[0], p.b[0], p.gamma[0], p.beta[0], p.bn_rstd, p.N[0], p.ksplit[0], part, A0, lda, tid);
-  if (p.L > 1)
-    dense_bn_layer(A0, lda, p.N[0], p.W[1], p.b[1], p.gamma[1], p.beta[1], p.bn_rstd, p.N[1], p.ksplit[1], part, A1, lda, tid);
-  if (p.L > 2)
-    dense_bn_layer(A1, lda, p.N[1], p.W[2], p.b[2], p.gamma[2], p.beta[2], p.bn_rstd, p.N[2], p.ksplit[2], part, A0, lda, tid);
-  // ---- the logits layer, sigmoid: thread (r, d) of the first 256; the 16 lanes of an example are an aligned group of a
-  // wave, so the xor-butterfly stays inside it ----
+  // ---- the tower, then the logits layer, sigmoid: thread (r, d) of the first 256 ----
+  // predict_dcn_lds_floats refuses L < 1 before any launch: run_tower's first layer needs no guard here.  An envelope that
+  // lets L = 0 through must drop this line.
+  __builtin_assume(p.t.L >= 1);
+  const float* AL = run_tower(p.t, lds, 16 * F, tid);
   if (tid < 256) {
     const int r = tid >> 4, d = tid & 15;
-    const float* o = (p.L == 2 ? A1 : A0) + r * lda;
-    const int NL = p.N[p.L - 1];
-    float u = 0.f;
-    for (int n = d; n < NL; n += 16) u += o[n] * p.wo[n];
-#pragma unroll
-    for (int m = 1; m < 16; m <<= 1) u += __shfl_xor(u, m);
-    const float z = (u + czs[r]) + p.bo[0];
+    const float z = (head_dot16(AL + r * p.t.lda, p.wo, NL, d) + czs[r]) + p.bo[0];
     if (d == 0 && row0 + r < p.B) p.prob[row0 + r] = 1.f / (1.f + expf(-z));
   }
 }
 
 // LDS floats of a launch (predict_fm_tower's plan: the cz slot takes the place of y1 | y2), or -1 outside the envelope.
-long long predict_dcn_lds_floats(int B, int F, int D, int L, const int32_t* widths, int Lc, PredictArgs* plan) {
+long long predict_dcn_lds_floats(int B, int F, int D, int L, const int32_t* widths, int Lc, TowerArgs* plan) {
   if (L < 1 || Lc < 1 || Lc > DCN_MAX_LC) return -1;
   return predict_lds_floats(B, F, D, L, widths, plan);
-}
-
-// The raised LDS limit is a property of a kernel FUNCTION: every instantiation asks for its own, once.
-template <int NU, int TD>
-int launch_dcn(const PredictDcnArgs& p, const size_t lds, hipStream_t stream) {
-  if (lds > 64 * 1024) {
-    static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(predict_dcn_k<NU, TD>),
-                                                       hipFuncAttributeMaxDynamicSharedMemorySize, PR_MAX_LDS);
-    if (attr != hipSuccess) return RSX_EUNSUPPORTED;
-  }
-  RSX_LAUNCH((predict_dcn_k<NU, TD>), dim3((p.B + PR_ROWS - 1) / PR_ROWS), dim3(PR_T), lds, stream, p);
-  RSX_CHECK_LAUNCH();
-  return RSX_OK;
-}
-
-// fields per gather thread: 5 covers F <= 40 (Criteo-39), 8 every F of the envelope
-template <int TD>
-int launch_dcn_nu(const PredictDcnArgs& p, const size_t lds, hipStream_t stream) {
-  return p.F <= 40 ? launch_dcn<5, TD>(p, lds, stream) : launch_dcn<8, TD>(p, lds, stream);
 }
 
 }  // namespace
@@ -189,40 +152,21 @@ extern "C" int rsx_predict_dcn_supported(int B, int F, int D, int L, const int32
 }
 
 extern "C" int rsx_predict_dcn(const rsx_predict_dcn_model* m, const int32_t* ids, float* prob, int B, rsx_stream_t stream) {
-  if (!m || !ids || !prob || B <= 0) return RSX_EINVAL;
-  if (!m->tables || !m->row_off || !m->cross_W || !m->cross_b || !m->wo || !m->bo) return RSX_EINVAL;
-  if (m->F <= 0 || m->D <= 0 || m->L < 0 || m->Lc < 0) return RSX_EINVAL;
-  if (!(m->bn_eps >= 0.f) || !(m->bn_eps < INFINITY)) return RSX_EINVAL;
-  if (m->L <= RSX_PREDICT_MAX_LAYERS) {
-    for (int l = 0; l < m->L; ++l) {
-      if (!m->W[l] || !m->b[l] || m->widths[l] <= 0) return RSX_EINVAL;
-      if ((m->gamma[l] == nullptr) != (m->beta[l] == nullptr)) return RSX_EINVAL;
-    }
-  }
-  if (!table_dtype_known(m->table_dtype)) return RSX_EINVAL;
-  if (!al16(m->tables) || !al16(m->cross_W) || !al16(m->cross_b)) return RSX_EINVAL;   // read as float4
-  PredictArgs plan;
-  const long long fl = predict_dcn_lds_floats(B, m->F, m->D, m->L, m->widths, m->Lc, &plan);
-  if (fl < 0) return RSX_EUNSUPPORTED;
+  if (!m || !ids || !prob || B <= 0 || !tower_model_valid(m)) return RSX_EINVAL;
+  if (m->Lc < 0 || !m->cross_W || !m->cross_b || !al16(m->cross_W) || !al16(m->cross_b)) return RSX_EINVAL;   // read as float4
   PredictDcnArgs p;
+  const long long fl = predict_dcn_lds_floats(B, m->F, m->D, m->L, m->widths, m->Lc, &p.t);
+  if (fl < 0) return RSX_EUNSUPPORTED;
+  fill_tower(&p.t, m);
   p.tables = m->tables; p.row_off = m->row_off; p.ids = ids;
-  for (int l = 0; l < RSX_PREDICT_MAX_LAYERS; ++l) {
-    const bool on = l < m->L;
-    p.W[l] = on ? m->W[l] : nullptr; p.b[l] = on ? m->b[l] : nullptr;
-    p.gamma[l] = on ? m->gamma[l] : nullptr; p.beta[l] = on ? m->beta[l] : nullptr;
-    p.N[l] = on ? m->widths[l] : 0;
-    p.ksplit[l] = on ? plan.ksplit[l] : 1;
-  }
   p.cw = m->cross_W; p.cb = m->cross_b; p.wo = m->wo; p.bo = m->bo;
   p.prob = prob;
-  p.bn_rstd = 1.0f / sqrtf(1.0f + m->bn_eps);
-  p.B = B; p.F = m->F; p.L = m->L; p.Lc = m->Lc;
-  p.ldx = plan.ldx; p.lda = plan.lda;
-  p.oA0 = plan.oA0; p.oA1 = plan.oA1; p.oP = plan.oP; p.oY = plan.oY;
+  p.B = B; p.F = m->F; p.Lc = m->Lc;
+  const unsigned grid = (B + PR_ROWS - 1) / PR_ROWS;
   const size_t lds = (size_t)fl * sizeof(float);
-  switch (m->table_dtype) {
-    case RSX_TABLE_BF16: return launch_dcn_nu<RSX_TABLE_BF16>(p, lds, rsx_s(stream));
-    case RSX_TABLE_F16: return launch_dcn_nu<RSX_TABLE_F16>(p, lds, rsx_s(stream));
-    default: return launch_dcn_nu<RSX_TABLE_F32>(p, lds, rsx_s(stream));
-  }
+  return dispatch_table_dtype(m->table_dtype, [&](auto td) {
+    constexpr int TD = decltype(td)::value;    // fields per gather thread: 5 covers F <= 40 (Criteo-39), 8 every F of the envelope
+    return p.F <= 40 ? launch_big_lds<predict_dcn_k<5, TD>>(p, grid, PR_T, lds, rsx_s(stream))
+                     : launch_big_lds<predict_dcn_k<8, TD>>(p, grid, PR_T, lds, rsx_s(stream));
+  });
 }

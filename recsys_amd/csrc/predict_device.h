@@ -1,8 +1,14 @@
-// The device functions and the LDS plan shared by the one-launch serving kernels (predict.hip: fm.py / deepfm.py,
-// predict_dcn.hip: dcn.py): the fp32 MFMA layer loop `dense_bn_layer` over a 16-example tile held in LDS,
-// `predict_lds_floats`, the tile's LDS layout and envelope, and `load_row4`, the one place that knows how a table row is
-// stored (fp32, or bfloat16 / float16 widened exactly).  See predict.hip's head for the layer loop's shape.
+// What the one-launch serving kernels share.  All three (predict.hip: fm.py / deepfm.py, predict_dcn.hip: dcn.py,
+// predict_din.hip: din.py's ranking): `f32x4` / `mfma16`, `up16` / `al16`, and `launch_big_lds`, the launch of a kernel that
+// may need more than 64 KB of dynamic LDS.  The two tower kernels (predict.hip, predict_dcn.hip): `TowerArgs`, the tower of a
+// launch with its LDS plan (`predict_lds_floats`: layout and envelope; `tower_model_valid` / `fill_tower` on the host),
+// `run_tower` = the fp32 MFMA layer loop `dense_bn_layer` over a 16-example tile held in LDS, `head_dot16`, and `load_row4`, the
+// one place that knows how a table row is stored (fp32, or bfloat16 / float16 widened exactly), with `dispatch_table_dtype`.
+// See predict.hip's head for the layer loop's shape.
+// The two gather phases stay in their kernels: they do different arithmetic on the gathered registers (fm: 8 slots, first-order
+// and FM sums; dcn: NU slots, the cross layers), so a shared body would branch on its caller.
 #pragma once
+#include <type_traits>
 #include "rsx_common.h"
 
 namespace {
@@ -13,6 +19,23 @@ constexpr int PR_T = 512, PR_NW = PR_T / 64;   // threads / waves per workgroup
 constexpr int PR_ROWS = 16;                    // examples per workgroup
 constexpr int PR_GF = 8;                       // fields per gather thread: 64 fields / 8 field lanes
 constexpr int PR_MAX_LDS = 160 * 1024;
+
+inline int up16(int x) { return (x + 15) & ~15; }
+inline bool al16(const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15u) == 0; }
+
+// Launch of a kernel that may need more than 64 KB of dynamic LDS.  The raised limit is a property of a kernel FUNCTION: every
+// KERNEL (so every instantiation of a kernel template) asks for its own, once.
+template <auto KERNEL, class Args>
+int launch_big_lds(const Args& p, const unsigned grid, const unsigned threads, const size_t lds, hipStream_t stream) {
+  if (lds > 64 * 1024) {
+    static const hipError_t attr =
+        hipFuncSetAttribute(reinterpret_cast<const void*>(KERNEL), hipFuncAttributeMaxDynamicSharedMemorySize, PR_MAX_LDS);
+    if (attr != hipSuccess) return RSX_EUNSUPPORTED;
+  }
+  RSX_LAUNCH(KERNEL, dim3(grid), dim3(threads), lds, stream, p);
+  RSX_CHECK_LAUNCH();
+  return RSX_OK;
+}
 
 // Elements 4 q .. 4 q + 3 of row `row` of tables [R, 16] stored as TD (RSX_TABLE_*), as fp32.  A 16-bit row is 32 bytes: the
 // thread loads the 8 bytes that hold its four elements and widens them, which is exact for both formats (subnormals, signed
@@ -35,19 +58,35 @@ __device__ __forceinline__ f32x4 load_row4(const void* __restrict__ tables, cons
 }
 inline bool table_dtype_known(int td) { return td == RSX_TABLE_F32 || td == RSX_TABLE_BF16 || td == RSX_TABLE_F16; }
 
-struct PredictArgs {
-  const void* tables; const float* w1; const int32_t* row_off; const int32_t* ids;   // tables: [R, 16] of the kernel's TD
+// f(std::integral_constant<int, TD>) for the RSX_TABLE_* value td (a known one: table_dtype_known).
+template <class Fn>
+int dispatch_table_dtype(const int td, Fn&& f) {
+  switch (td) {
+    case RSX_TABLE_BF16: return f(std::integral_constant<int, RSX_TABLE_BF16>());
+    case RSX_TABLE_F16: return f(std::integral_constant<int, RSX_TABLE_F16>());
+    default: return f(std::integral_constant<int, RSX_TABLE_F32>());
+  }
+}
+
+// The tower of a launch and the LDS plan of its tile: what predict_fm_tower_k and predict_dcn_k have in common.
+struct TowerArgs {
   const float* W[RSX_PREDICT_MAX_LAYERS]; const float* b[RSX_PREDICT_MAX_LAYERS];
   const float* gamma[RSX_PREDICT_MAX_LAYERS]; const float* beta[RSX_PREDICT_MAX_LAYERS];
-  const float* wd; const float* bd; const float* c0; const float* wo; const float* bo;
-  float* prob;
-  uint64_t w1_mask;
   float bn_rstd;                               // 1 / sqrt(1 + eps)
-  int B, F, L;
+  int L;
   int N[RSX_PREDICT_MAX_LAYERS];
   int ksplit[RSX_PREDICT_MAX_LAYERS];          // K-splits of a layer: its column groups x ksplit work units go round the 8 waves
   int ldx, lda;                                // row strides of the gathered tile and of the activation tiles (floats, == 4 mod 8)
-  int oA0, oA1, oP, oY;                        // LDS offsets (floats): activation tiles, partial tiles, y1 | y2 [2][16]
+  int oA0, oA1, oP, oY;                        // LDS offsets (floats): activation tiles, partial tiles, the kernel's [32] slot
+};
+
+struct PredictArgs {
+  const void* tables; const float* w1; const int32_t* row_off; const int32_t* ids;   // tables: [R, 16] of the kernel's TD
+  TowerArgs t;                                 // t.oY: y1 | y2 [2][16]
+  const float* wd; const float* bd; const float* c0; const float* wo; const float* bo;
+  float* prob;
+  uint64_t w1_mask;
+  int B, F;
 };
 
 // B operands of one k-step for a column group: b[t] = W[16 ks + 4 kq + t][c0 .. c0 + 3].  Rows past K are clamped to K - 1 (the A
@@ -149,10 +188,64 @@ __device__ __forceinline__ void dense_bn_layer(const float* in, const int ldi, c
   __syncthreads();
 }
 
-inline int up16(int x) { return (x + 15) & ~15; }
+// The tower over the gathered tile X = lds [16][t.ldx] of K0 columns: the activation tiles ping-pong between two LDS buffers
+// -> the last layer's tile [16][t.lda].  t.L == 0 (fm.py) is allowed and runs no layer; the returned pointer means something
+// for t.L >= 1 only.
+__device__ __forceinline__ const float* run_tower(const TowerArgs& t, float* lds, const int K0, const int tid) {
+  float* A0 = lds + t.oA0;
+  float* A1 = lds + t.oA1;
+  float* part = lds + t.oP;
+  const int lda = t.lda;
+  if (t.L > 0)
+    dense_bn_layer(lds, t.ldx, K0, t.W[0], t.b[0], t.gamma[0], t.beta[0], t.bn_rstd, t.N[0], t.ksplit[0], part, A0, lda, tid);
+  if (t.L > 1)
+    dense_bn_layer(A0, lda, t.N[0], t.W[1], t.b[1], t.gamma[1], t.beta[1], t.bn_rstd, t.N[1], t.ksplit[1], part, A1, lda, tid);
+  if (t.L > 2)
+    dense_bn_layer(A1, lda, t.N[1], t.W[2], t.b[2], t.gamma[2], t.beta[2], t.bn_rstd, t.N[2], t.ksplit[2], part, A0, lda, tid);
+  return t.L == 2 ? A1 : A0;
+}
+
+// <o [0, N), w [0, N)> by the 16 lanes d of an example, an aligned group of a wave: n = d, d + 16, ..., then an xor butterfly
+// that stays inside the group (every lane ends with the sum).
+__device__ __forceinline__ float head_dot16(const float* o, const float* __restrict__ w, const int N, const int d) {
+  float u = 0.f;
+  for (int n = d; n < N; n += 16) u += o[n] * w[n];
+#pragma unroll
+  for (int m = 1; m < 16; m <<= 1) u += __shfl_xor(u, m);
+  return u;
+}
+
+// What makes a model RSX_EINVAL in the members rsx_predict_model and rsx_predict_dcn_model (M) spell alike.  Layers past
+// RSX_PREDICT_MAX_LAYERS are not looked at: the arrays end there, and such an L is outside the envelope.
+template <class M>
+bool tower_model_valid(const M* m) {
+  if (!m->tables || !m->row_off || !m->wo || !m->bo || m->F <= 0 || m->D <= 0 || m->L < 0) return false;
+  if (!(m->bn_eps >= 0.f) || !(m->bn_eps < INFINITY)) return false;
+  if (m->L <= RSX_PREDICT_MAX_LAYERS) {
+    for (int l = 0; l < m->L; ++l) {
+      if (!m->W[l] || !m->b[l] || m->widths[l] <= 0) return false;
+      if ((m->gamma[l] == nullptr) != (m->beta[l] == nullptr)) return false;
+    }
+  }
+  return table_dtype_known(m->table_dtype) && al16(m->tables);   // rows are read as float4 (16-bit rows: 8 bytes of a 32-byte row)
+}
+
+// The model's part of a TowerArgs that predict_lds_floats has planned (so m->L <= RSX_PREDICT_MAX_LAYERS).
+template <class M>
+void fill_tower(TowerArgs* t, const M* m) {
+  for (int l = 0; l < RSX_PREDICT_MAX_LAYERS; ++l) {
+    const bool on = l < m->L;
+    t->W[l] = on ? m->W[l] : nullptr; t->b[l] = on ? m->b[l] : nullptr;
+    t->gamma[l] = on ? m->gamma[l] : nullptr; t->beta[l] = on ? m->beta[l] : nullptr;
+    t->N[l] = on ? m->widths[l] : 0;
+    if (!on) t->ksplit[l] = 1;
+  }
+  t->bn_rstd = 1.0f / sqrtf(1.0f + m->bn_eps);
+  t->L = m->L;
+}
 
 // LDS floats of a launch, or -1 outside the envelope.
-long long predict_lds_floats(int B, int F, int D, int L, const int32_t* widths, PredictArgs* p) {
+inline long long predict_lds_floats(int B, int F, int D, int L, const int32_t* widths, TowerArgs* p) {
   if (D != 16 || F < 1 || F > 64 || L < 0 || L > RSX_PREDICT_MAX_LAYERS || B < 1) return -1;
   if ((long long)B * F >= (1ll << 31)) return -1;
   if (L > 0 && widths == nullptr) return -1;
@@ -187,7 +280,5 @@ long long predict_lds_floats(int B, int F, int D, int L, const int32_t* widths, 
   }
   return fl;
 }
-
-inline bool al16(const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15u) == 0; }
 
 }  // namespace

@@ -25,11 +25,9 @@
 // No atomics, no workspace; every sum has a fixed order that does not involve C, the candidate's position, U or its
 // neighbours, so a pair's bits depend on its ids and the model only.
 #include "rsx_common.h"
+#include "predict_device.h"      // f32x4, mfma16, up16, al16, launch_big_lds
 
 namespace {
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ f32x4 mfma16(float a, float b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
-
 constexpr int DR_T = 512, DR_NW = DR_T / 64;
 constexpr int DR_N1 = 80, DR_N2 = 40;          // attention widths (din/din.py:85)
 constexpr int DR_T1 = DR_N1 / 16, DR_T2 = (DR_N2 + 15) / 16;
@@ -37,7 +35,6 @@ constexpr int DR_PMAX = 128, DR_CT_MAX = 8, DR_MAXTILES = DR_PMAX / 16;
 constexpr int DR_LDU = DR_N1 + 4;
 constexpr int DR_M0 = 100, DR_M1 = 50, DR_M2 = 20;                     // 'mlp_layer' widths (din/din.py:86)
 constexpr int DR_LDA1 = 116, DR_LDA2 = 68, DR_LDA3 = 36;                // activation row strides (width rounded up to 16, + 4)
-constexpr int DR_MAX_LDS = 160 * 1024;
 
 struct DinRankArgs {
   const float* tab[2];                         // item rows, category rows [., K]
@@ -332,8 +329,6 @@ __global__ __launch_bounds__(DR_T) void predict_din_rank_k(const DinRankArgs p) 
   }
 }
 
-inline int up16(int x) { return (x + 15) & ~15; }
-
 bool din_rank_envelope(int U, int C, int P, int K, int n1, int n2, int L, const int32_t* widths) {
   if (U < 1 || C < 1 || P < 1 || P > DR_PMAX) return false;
   if (K != 16 && K != 32) return false;
@@ -365,20 +360,6 @@ size_t din_rank_layout(DinRankArgs* p, int K) {
   p->oA3 = o; o += CT * DR_LDA3;
   p->oVid = o; o += 2 * PT + 4;
   return (size_t)o * sizeof(float);
-}
-
-inline bool al16(const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15u) == 0; }
-
-template <int K>
-int din_rank_launch(const DinRankArgs& p, size_t lds, hipStream_t st) {
-  if (lds > 64 * 1024) {
-    static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(predict_din_rank_k<K>),
-                                                       hipFuncAttributeMaxDynamicSharedMemorySize, DR_MAX_LDS);
-    if (attr != hipSuccess) return RSX_EUNSUPPORTED;
-  }
-  RSX_LAUNCH(predict_din_rank_k<K>, dim3((unsigned)(p.U * p.ctiles)), dim3(DR_T), lds, st, p);
-  RSX_CHECK_LAUNCH();
-  return RSX_OK;
 }
 
 }  // namespace
@@ -418,6 +399,8 @@ extern "C" int rsx_predict_din_rank(const rsx_predict_din_model* m, const int32_
   p.ctiles = (C + p.CT - 1) / p.CT;
   p.PT = up16(P);
   const size_t lds = din_rank_layout(&p, m->K);
-  if (lds > (size_t)DR_MAX_LDS) return RSX_EUNSUPPORTED;
-  return m->K == 32 ? din_rank_launch<32>(p, lds, rsx_s(stream)) : din_rank_launch<16>(p, lds, rsx_s(stream));
+  if (lds > (size_t)PR_MAX_LDS) return RSX_EUNSUPPORTED;
+  const unsigned grid = (unsigned)(U * p.ctiles);
+  return m->K == 32 ? launch_big_lds<predict_din_rank_k<32>>(p, grid, DR_T, lds, rsx_s(stream))
+                    : launch_big_lds<predict_din_rank_k<16>>(p, grid, DR_T, lds, rsx_s(stream));
 }

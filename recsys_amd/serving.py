@@ -142,13 +142,20 @@ def linear_mode(linear_columns):
     return "custom"
 
 
-def make_manifest(script, params, global_step, tensors, table_dtype="float32"):
-    """The settings of one exported model.  tensors: {name: numpy array} as stored -- only names, shapes and dtypes go in
-    here.  A 16-bit table_dtype makes a format_version 2 manifest (see the module docstring); "float32" adds no key."""
+def _check_export(script, table_dtype, module=None):
+    """What an export refuses about its table dtype and its script (`module`: the model_fn's module the script name came from)."""
     if table_dtype not in TABLE_DTYPES:
         raise _lib.RsxError("export: table dtype %r is none of %s" % (table_dtype, ", ".join(TABLE_DTYPES)))
     if script not in SCRIPTS:
+        if module is not None:
+            raise _lib.RsxError("export: model_fn of module %r is none of the scripts %s" % (module, ", ".join(SCRIPTS)))
         raise _lib.RsxError("export: unknown script %r (known: %s)" % (script, ", ".join(SCRIPTS)))
+
+
+def make_manifest(script, params, global_step, tensors, table_dtype="float32"):
+    """The settings of one exported model.  tensors: {name: numpy array} as stored -- only names, shapes and dtypes go in
+    here.  A 16-bit table_dtype makes a format_version 2 manifest (see the module docstring); "float32" adds no key."""
+    _check_export(script, table_dtype)
     emb = params.get("embedding_feature_columns")
     lin = params.get("linear_feature_columns") or []
     if script == "din":
@@ -299,17 +306,21 @@ def read_bundle(bundle_dir):
 _TABLE_ATTRS = ("tables", "w1", "table")      # what an EmbeddingArena / SparseTable holds besides optimizer slots
 
 
-def store_variables(store):
-    """{name: fp32 numpy array} of a built VariableStore: `emb.<arena>.<tables|w1|table>` and `dense.<variable>`."""
-    out = {}
+def _store_tensors(store):
+    """(bundle name, tensor) of every variable of a built VariableStore: `emb.<arena>.<tables|w1|table>`, then
+    `dense.<variable>`."""
     for name, a in store.embeddings.items():
         for attr in _TABLE_ATTRS:
             t = getattr(a, attr, None)
             if t is not None:
-                out["emb.%s.%s" % (name, attr)] = t.detach().float().cpu().numpy().copy()
+                yield "emb.%s.%s" % (name, attr), t
     for k, p in store.dense.params.items():
-        out["dense." + k] = p.detach().float().cpu().contiguous().numpy().copy()
-    return out
+        yield "dense." + k, p
+
+
+def store_variables(store):
+    """{name: fp32 numpy array} of a built VariableStore."""
+    return {k: t.detach().float().cpu().contiguous().numpy().copy() for k, t in _store_tensors(store)}
 
 
 def load_store_variables(store, arrays):
@@ -320,37 +331,22 @@ def load_store_variables(store, arrays):
         raise _lib.RsxError("bundle and model disagree on the variables: only in the bundle %s, only in the model %s"
                             % (sorted(set(arrays) - want), sorted(want - set(arrays))))
     with torch.no_grad():
-        for name, a in store.embeddings.items():
-            for attr in _TABLE_ATTRS:
-                t = getattr(a, attr, None)
-                if t is not None:
-                    src = arrays["emb.%s.%s" % (name, attr)]
-                    if tuple(src.shape) != tuple(t.shape):
-                        raise _lib.RsxError("bundle tensor emb.%s.%s has shape %s, the model's is %s"
-                                            % (name, attr, tuple(src.shape), tuple(t.shape)))
-                    t.copy_(torch.from_numpy(src))
-        for k, p in store.dense.params.items():
-            src = arrays["dense." + k]
-            if tuple(src.shape) != tuple(p.shape):
-                raise _lib.RsxError("bundle tensor dense.%s has shape %s, the model's is %s" % (k, tuple(src.shape), tuple(p.shape)))
-            p.copy_(torch.from_numpy(src))
+        for k, t in _store_tensors(store):
+            if tuple(arrays[k].shape) != tuple(t.shape):
+                raise _lib.RsxError("bundle tensor %s has shape %s, the model's is %s" % (k, tuple(arrays[k].shape), tuple(t.shape)))
+            t.copy_(torch.from_numpy(arrays[k]))
 
 
 def store_variables_names(store):
-    names = ["emb.%s.%s" % (n, attr) for n, a in store.embeddings.items() for attr in _TABLE_ATTRS
-             if getattr(a, attr, None) is not None]
-    return names + ["dense." + k for k in store.dense.params]
+    return [k for k, _ in _store_tensors(store)]
 
 
 def export_estimator(est, export_dir_base, table_dtype="float32"):
     """Estimator.export_savedmodel's body: the latest checkpoint of est.model_dir as a bundle -> its directory.  table_dtype
     "bfloat16" / "float16": every embedding-row tensor is rounded to it (`quantize_rows`) and stored in it."""
     from . import checkpoint
-    if table_dtype not in TABLE_DTYPES:
-        raise _lib.RsxError("export: table dtype %r is none of %s" % (table_dtype, ", ".join(TABLE_DTYPES)))
     script = est.model_fn.__module__.rsplit(".", 1)[-1]
-    if script not in SCRIPTS:
-        raise _lib.RsxError("export: model_fn of module %r is none of the scripts %s" % (est.model_fn.__module__, ", ".join(SCRIPTS)))
+    _check_export(script, table_dtype, module=est.model_fn.__module__)
     # With a model_dir the bundle is its latest checkpoint (restored now unless this Estimator already runs from it); an
     # Estimator without one (model_dir=None: tests, notebooks) exports the variables it holds.
     if est.model_dir:
@@ -550,37 +546,49 @@ class Predictor:
         self._prob = torch.zeros(self.max_batch_size, dtype=torch.float32, device=dev)
         return lambda k: self._dense.data_ptr() + 4 * offs[k]
 
+    def _tower_widths(self):
+        """The manifest's `deep_layers` (fm.py: no tower) -> (widths, their array for the C ABI; None when the model structs
+        cannot hold them)."""
+        deep = "" if self.script == "fm" else str(self.manifest["params"].get("deep_layers", ""))
+        widths = [int(w) for w in deep.split(",") if w]
+        fits = len(widths) <= _lib.PREDICT_MAX_LAYERS
+        return widths, (C.c_int32 * _lib.PREDICT_MAX_LAYERS)(*widths) if fits else None
+
+    @staticmethod
+    def _tower_need(widths):
+        return ["dense.dnn.%s%d" % (v, l) for l in range(len(widths)) for v in ("W", "b", "gamma", "beta")]
+
+    def _fill_tower(self, pm, ptr, widths, D):
+        """What rsx_predict_model and rsx_predict_dcn_model spell alike: the table, the tower's layers, the sizes."""
+        pm.tables, pm.row_off = self._tables.data_ptr(), self._row_off.data_ptr()
+        for l in range(len(widths)):
+            pm.W[l], pm.b[l] = ptr("dense.dnn.W%d" % l), ptr("dense.dnn.b%d" % l)
+            pm.gamma[l], pm.beta[l] = ptr("dense.dnn.gamma%d" % l), ptr("dense.dnn.beta%d" % l)
+            pm.widths[l] = widths[l]
+        pm.wo, pm.bo = ptr("dense.out.W"), ptr("dense.out.b")
+        pm.bn_eps = float(self.manifest["batch_norm_epsilon"])
+        pm.F, pm.D, pm.L = self.layout.F, D, len(widths)
+        pm.table_dtype = _lib.TABLE_DTYPES[self.table_dtype]
+
     def _fused_setup(self, arrays):
         import torch
         m, lay = self.manifest, self.layout
         D = int(m["params"]["embedding_size"])
-        widths = [int(w) for w in str(m["params"].get("deep_layers", "")).split(",") if w] if self.script == "deepfm" else []
-        if len(widths) > _lib.PREDICT_MAX_LAYERS:
+        widths, wa = self._tower_widths()
+        if wa is None or not _lib.lib().rsx_predict_fm_tower_supported(self.max_batch_size, lay.F, D, len(widths), wa):
             return False
-        wa = (C.c_int32 * _lib.PREDICT_MAX_LAYERS)(*widths)
-        if not _lib.lib().rsx_predict_fm_tower_supported(self.max_batch_size, lay.F, D, len(widths), wa):
-            return False
-        need = ["emb.input_layer.tables", "emb.input_layer.w1", "dense.b1", "dense.out.W", "dense.out.b"]
-        for l in range(len(widths)):
-            need += ["dense.dnn.%s%d" % (v, l) for v in ("W", "b", "gamma", "beta")]
+        need = ["emb.input_layer.tables", "emb.input_layer.w1", "dense.b1", "dense.out.W", "dense.out.b"] + self._tower_need(widths)
         if widths:
             need += ["dense.dnn.Wout", "dense.dnn.bout"]
         ptr = self._fused_variables(arrays, need)
         self._w1 = torch.from_numpy(arrays["emb.input_layer.w1"]).to(self.device)      # the first-order vector
         lin_keys = {c["key"] for c in m["linear_columns"] if c["kind"].endswith("indicator")}
         pm = _lib.PredictModel()
-        pm.tables, pm.w1, pm.row_off = self._tables.data_ptr(), self._w1.data_ptr(), self._row_off.data_ptr()
-        for l in range(len(widths)):
-            pm.W[l], pm.b[l] = ptr("dense.dnn.W%d" % l), ptr("dense.dnn.b%d" % l)
-            pm.gamma[l], pm.beta[l] = ptr("dense.dnn.gamma%d" % l), ptr("dense.dnn.beta%d" % l)
-            pm.widths[l] = widths[l]
+        self._fill_tower(pm, ptr, widths, D)
+        pm.w1, pm.c0 = self._w1.data_ptr(), ptr("dense.b1")
         if widths:
             pm.wd, pm.bd = ptr("dense.dnn.Wout"), ptr("dense.dnn.bout")
-        pm.c0, pm.wo, pm.bo = ptr("dense.b1"), ptr("dense.out.W"), ptr("dense.out.b")
         pm.w1_field_mask = lay.field_mask(lin_keys)
-        pm.bn_eps = float(m["batch_norm_epsilon"])
-        pm.F, pm.D, pm.L = lay.F, D, len(widths)
-        pm.table_dtype = _lib.TABLE_DTYPES[self.table_dtype]
         self._model, self._kernel = pm, "rsx_predict_fm_tower"
         return True
 
@@ -588,29 +596,16 @@ class Predictor:
         """dcn.py with one_launch=True: tables + ONE flat buffer of the dense tensors, no Estimator; False outside
         rsx_predict_dcn's envelope."""
         m, lay = self.manifest, self.layout
-        D = int(m["params"]["embedding_size"])
-        widths = [int(w) for w in str(m["params"].get("deep_layers", "")).split(",") if w]
+        widths, wa = self._tower_widths()
         Lc = int(m["params"].get("cross_layers", 0))
-        if len(widths) > _lib.PREDICT_MAX_LAYERS:
+        D = int(m["params"]["embedding_size"])
+        if wa is None or not _lib.lib().rsx_predict_dcn_supported(self.max_batch_size, lay.F, D, len(widths), wa, Lc):
             return False
-        wa = (C.c_int32 * _lib.PREDICT_MAX_LAYERS)(*widths)
-        if not _lib.lib().rsx_predict_dcn_supported(self.max_batch_size, lay.F, D, len(widths), wa, Lc):
-            return False
-        need = ["emb.input_layer.tables", "dense.cross.W", "dense.cross.b", "dense.out.W", "dense.out.b"]
-        for l in range(len(widths)):
-            need += ["dense.dnn.%s%d" % (v, l) for v in ("W", "b", "gamma", "beta")]
+        need = ["emb.input_layer.tables", "dense.cross.W", "dense.cross.b", "dense.out.W", "dense.out.b"] + self._tower_need(widths)
         ptr = self._fused_variables(arrays, need)
         pm = _lib.PredictDcnModel()
-        pm.tables, pm.row_off = self._tables.data_ptr(), self._row_off.data_ptr()
-        pm.cross_W, pm.cross_b = ptr("dense.cross.W"), ptr("dense.cross.b")
-        for l in range(len(widths)):
-            pm.W[l], pm.b[l] = ptr("dense.dnn.W%d" % l), ptr("dense.dnn.b%d" % l)
-            pm.gamma[l], pm.beta[l] = ptr("dense.dnn.gamma%d" % l), ptr("dense.dnn.beta%d" % l)
-            pm.widths[l] = widths[l]
-        pm.wo, pm.bo = ptr("dense.out.W"), ptr("dense.out.b")
-        pm.bn_eps = float(m["batch_norm_epsilon"])
-        pm.F, pm.D, pm.L, pm.Lc = lay.F, D, len(widths), Lc
-        pm.table_dtype = _lib.TABLE_DTYPES[self.table_dtype]
+        self._fill_tower(pm, ptr, widths, D)
+        pm.cross_W, pm.cross_b, pm.Lc = ptr("dense.cross.W"), ptr("dense.cross.b"), Lc
         self._model, self._kernel = pm, "rsx_predict_dcn"
         return True
 
@@ -795,30 +790,11 @@ class Predictor:
     def _rank_chunk(self, U, ci, cc):
         """ci, cc: int32 [U, n] (host or device), n <= max_candidates; the histories are in place -> prob [U, n] (a view of
         the output buffer, valid until the next call).  Graphs: the rule of _fused_chunk, keyed by the request shape."""
-        import torch
         r = self._rank
         n = int(ci.shape[1])
         r["cand"][0][:U * n].view(U, n).copy_(ci, non_blocking=True)
         r["cand"][1][:U * n].view(U, n).copy_(cc, non_blocking=True)
-        key = ("rank", U, n)
-        g = self._graphs.get(key) if self.use_hip_graph else None
-        if g is None and self.use_hip_graph and self._n_graphs < self.MAX_GRAPHS:
-            g = self._graphs[key] = {"warm": 0}
-            self._n_graphs += 1
-        if g is None:
-            self._rank_launch(U, n)
-        elif "graph" in g:
-            g["graph"].replay()
-        elif g["warm"] < 1:
-            g["warm"] += 1
-            self._rank_launch(U, n)
-        else:
-            torch.cuda.synchronize()
-            graph = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(graph):
-                self._rank_launch(U, n)
-            g["graph"] = graph
-            graph.replay()
+        self._run(("rank", U, n), lambda: self._rank_launch(U, n))
         return r["prob"][:U * n].view(U, n)
 
     def rank_candidates(self, u_iid_seq, u_icat_seq, i_id, i_cate):
