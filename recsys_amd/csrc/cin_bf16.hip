@@ -25,27 +25,16 @@
 #include "rsx_common.h"
 #include "adam_device.h"
 #include "cin_bf16_wide.h"
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16_t;
+#include "split_device.h"
 
 constexpr int CB_D = 16;
 
-__device__ __forceinline__ f32x4 mfma_bf16(bf16x8 a, bf16x8 b, f32x4 c) {
-  return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
-}
-__device__ __forceinline__ bf16x8 ld_bf16x8(const bf16_t* p) {
-  return __builtin_bit_cast(bf16x8, *reinterpret_cast<const uint4*>(p));
-}
 __device__ __forceinline__ bf16x8 cvt8(float4 a, float4 b) {
   bf16x8 r;
   r[0] = (bf16_t)a.x; r[1] = (bf16_t)a.y; r[2] = (bf16_t)a.z; r[3] = (bf16_t)a.w;
   r[4] = (bf16_t)b.x; r[5] = (bf16_t)b.y; r[6] = (bf16_t)b.z; r[7] = (bf16_t)b.w;
   return r;
 }
-static inline int rup(int x, int m) { return (x + m - 1) / m * m; }
 
 // ------------------------------------------------------------------------------------------------ weight preparation
 // Fragment-major images: the 64 lanes' 16-byte operand quads of one (field, tile, k-step) are 1 KiB contiguous, so every
@@ -705,16 +694,13 @@ static int cb_launch_dx(const float* X0, const float* Xk, const void* w16, const
   if (rcs != RSX_OK) return rcs;
   const size_t lds = (size_t)2 * 16 * (Np + 8) * 2 +
                      ((size_t)2 * F * CB_D + (size_t)HT * 2 * F * CB_D + (size_t)(PART - 1) * HT * 2 * 256) * sizeof(float);
-  if (lds > 160 * 1024) return RSX_EUNSUPPORTED;
   const unsigned per = (unsigned)(64 * HT * PART) / 256;                     // sweep blocks per rider workgroup (>= 3)
   const dim3 grid((unsigned)a.ntile + (a.sweep.n_blk + per - 1) / per), block((unsigned)(64 * HT * PART));
   const void* fn = Np / 32 == 1 ? reinterpret_cast<const void*>(cin_bwd_dx_bf16_k<1>)
                  : Np / 32 == 2 ? reinterpret_cast<const void*>(cin_bwd_dx_bf16_k<2>)
                  : Np / 32 == 3 ? reinterpret_cast<const void*>(cin_bwd_dx_bf16_k<3>)
                                 : reinterpret_cast<const void*>(cin_bwd_dx_bf16_k<4>);
-  // gfx950 has 160 KiB of LDS per CU; above 64 KiB a kernel must opt in (host-side attribute, no stream work)
-  if (lds > 64 * 1024 && hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-    return RSX_ELAUNCH;
+  if (const int rc = opt_in_lds(fn, lds); rc != RSX_OK) return rc;
   switch (Np / 32) {
     case 1: RSX_LAUNCH(cin_bwd_dx_bf16_k<1>, grid, block, lds, rsx_s(stream), a); break;
     case 2: RSX_LAUNCH(cin_bwd_dx_bf16_k<2>, grid, block, lds, rsx_s(stream), a); break;

@@ -18,32 +18,15 @@
 //   h tile (dx0_parts [HT][B][F*16]); cin_dx0_reduce_k adds the tiles in order (one launch for all layers).
 // All sums in fixed order: deterministic, no atomics.
 #include "rsx_common.h"
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16_t;
+#include "split_device.h"
 
 namespace {
 
 constexpr int CW_D = 16;
 constexpr int CW_E = 8;        // examples per workgroup
 constexpr int CW_NFW = 5;      // fields per wave: F <= 40
-
-__device__ __forceinline__ f32x4 mfma_bf16(bf16x8 a, bf16x8 b, f32x4 c) {
-  return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
-}
-__device__ __forceinline__ bf16x8 ld_bf16x8(const bf16_t* p) {
-  return __builtin_bit_cast(bf16x8, *reinterpret_cast<const uint4*>(p));
-}
-__device__ __forceinline__ uint32_t pack2(float lo, float hi) {
-  bf16x2 v;
-  v[0] = (bf16_t)lo;
-  v[1] = (bf16_t)hi;
-  return __builtin_bit_cast(uint32_t, v);
-}
-inline int rup(int x, int m) { return (x + m - 1) / m * m; }
+constexpr int CW_FP = 8 * CW_NFW;   // fields, padded (X0 reads as zero past F: a wave's five fields need no bounds test)
+static_assert(CW_FP == StageX0<CW_E>::FP && CW_D == StageX0<CW_E>::D, "StageX0's layout");
 
 // [E][rows][16] fp32 (through `load(e, row, quarter)`, rows >= the real count must come back as zeros) -> bf16, transposed
 // to dst[e][d][RPP] (rows contiguous: what the MFMA's k index walks).  A thread takes TWO rows of one d-quarter and writes
@@ -75,34 +58,6 @@ struct StageRows {
       t[1 * (RPP / 2)] = pack2(a[u].y, b[u].y);
       t[2 * (RPP / 2)] = pack2(a[u].z, b[u].z);
       t[3 * (RPP / 2)] = pack2(a[u].w, b[u].w);
-    }
-  }
-};
-
-// X0 of the eight examples -> LDS [E][CW_FP * 16], zeros for the fields F .. CW_FP - 1 (a wave's five fields need no bounds
-// test: a field past F multiplies by zero) -- 3 float4 per thread, requested together
-constexpr int CW_FP = 8 * CW_NFW;
-struct StageX0 {
-  float4 v[3];
-  __device__ __forceinline__ void load(const float* X0, int b0, int B, int F, int tid) {
-#pragma unroll
-    for (int u = 0; u < 3; ++u) {
-      const int e4 = tid + 512 * u;
-      const int ex = e4 / (CW_FP * 4), r = e4 % (CW_FP * 4);
-      // (unconditional loads from clamped addresses, zeroed afterwards: a load under a condition becomes a branch, and the
-      // compiler waits for each of them in turn)
-      const int exc = ex < CW_E ? ex : CW_E - 1;
-      const bool ok = e4 < CW_E * CW_FP * 4 && (r >> 2) < F && b0 + ex < B;
-      const int bc = b0 + exc < B ? b0 + exc : B - 1, rc = (r >> 2) < F ? r : 0;
-      const float4 t = reinterpret_cast<const float4*>(X0 + (size_t)bc * F * CW_D)[rc];
-      v[u] = make_float4(ok ? t.x : 0.f, ok ? t.y : 0.f, ok ? t.z : 0.f, ok ? t.w : 0.f);
-    }
-  }
-  __device__ __forceinline__ void store(float* sX0, int tid) const {
-#pragma unroll
-    for (int u = 0; u < 3; ++u) {
-      const int e4 = tid + 512 * u;
-      if (e4 < CW_E * CW_FP * 4) reinterpret_cast<float4*>(sX0)[e4] = v[u];
     }
   }
 };
@@ -146,7 +101,7 @@ __global__ __launch_bounds__(512) void cin_fwd_bf16_wide_k(const CwFwdArgs p) {
   };
 #pragma unroll
   for (int g = 0; g < RING; ++g) load_w(g, w[g]);
-  StageX0 sx;
+  StageX0<CW_E> sx;
   StageRows<KS> sr;
   sx.load(p.X0, b0, p.B, p.F, tid);
   sr.load(tid, [&](int e, int h, int dq) {
@@ -262,7 +217,7 @@ __global__ __launch_bounds__(512) void cin_bwd_dx_bf16_wide_k(const CwDxArgs p) 
   };
 #pragma unroll
   for (int g = 0; g < RING; ++g) load_w(g, w[g]);
-  StageX0 sx;
+  StageX0<CW_E> sx;
   sx.load(p.X0, b0, p.B, p.F, tid);
   {   // Xk of this tile: thread = (example, h in tile, d-quarter) -> sXkT[e][h >> 2][d][h & 3]
     const int e = tid >> 6, h16 = (tid >> 2) & 15, dq = tid & 3;
@@ -399,15 +354,6 @@ __global__ __launch_bounds__(256) void cin_dx0_reduce_k(const CwRedArgs p) {
   }
 }
 
-template <typename K>
-int opt_in_lds(K kernel, size_t lds) {
-  if (lds > 160 * 1024) return RSX_EUNSUPPORTED;
-  if (lds > 64 * 1024 &&
-      hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-    return RSX_ELAUNCH;
-  return RSX_OK;
-}
-
 }  // namespace
 
 #ifdef RSX_STAMPS
@@ -429,21 +375,14 @@ int cin_wide_fwd(const float* X0, const float* Xk, const void* wt16, const float
   const CwFwdArgs a{X0, Xk, static_cast<const bf16_t*>(wt16), c, out, B, F, H, N, N16, Hp};
   const dim3 grid((unsigned)(N16 / 16), (unsigned)((B + CW_E - 1) / CW_E));
   const size_t lds = ((size_t)CW_E * CW_FP * CW_D + 8 * CW_E * 256) * sizeof(float) + (size_t)CW_E * 16 * (Hp + 8) * 2;
-#define RSX_CW_FWD(KS)                                                               \
-  {                                                                                  \
-    const int rc = opt_in_lds(cin_fwd_bf16_wide_k<KS>, lds);                         \
-    if (rc != RSX_OK) return rc;                                                     \
-    RSX_LAUNCH(cin_fwd_bf16_wide_k<KS>, grid, dim3(512), lds, stream, a);            \
-  }
-  switch (Hp / 32) {
-    case 1: RSX_CW_FWD(1); break;
-    case 2: RSX_CW_FWD(2); break;
-    case 3: RSX_CW_FWD(3); break;
-    default: RSX_CW_FWD(4); break;
-  }
-#undef RSX_CW_FWD
-  RSX_CHECK_LAUNCH();
-  return RSX_OK;
+  return dispatch_ks(Hp / 32, [&](auto ks) -> int {
+    constexpr int KS = decltype(ks)::value;
+    const int rc = opt_in_lds(cin_fwd_bf16_wide_k<KS>, lds);
+    if (rc != RSX_OK) return rc;
+    RSX_LAUNCH(cin_fwd_bf16_wide_k<KS>, grid, dim3(512), lds, stream, a);
+    RSX_CHECK_LAUNCH();
+    return RSX_OK;
+  });
 }
 
 int cin_wide_dx(const float* X0, const float* Xk, const void* w16, const float* out, const float* dout, const float* gs,
@@ -455,21 +394,14 @@ int cin_wide_dx(const float* X0, const float* Xk, const void* w16, const float* 
   const dim3 grid((unsigned)(H16 / 16), (unsigned)((B + CW_E - 1) / CW_E));
   const size_t sp = (size_t)CW_E * CW_FP * 64, sdx = (size_t)8 * CW_E * 256;
   const size_t lds = (size_t)CW_E * 16 * (Np + 8) * 2 + ((size_t)CW_E * CW_FP * CW_D + CW_E * 256 + (sp > sdx ? sp : sdx)) * sizeof(float);
-#define RSX_CW_DX(KSN)                                                               \
-  {                                                                                  \
-    const int rc = opt_in_lds(cin_bwd_dx_bf16_wide_k<KSN>, lds);                     \
-    if (rc != RSX_OK) return rc;                                                     \
-    RSX_LAUNCH(cin_bwd_dx_bf16_wide_k<KSN>, grid, dim3(512), lds, stream, a);        \
-  }
-  switch (Np / 32) {
-    case 1: RSX_CW_DX(1); break;
-    case 2: RSX_CW_DX(2); break;
-    case 3: RSX_CW_DX(3); break;
-    default: RSX_CW_DX(4); break;
-  }
-#undef RSX_CW_DX
-  RSX_CHECK_LAUNCH();
-  return RSX_OK;
+  return dispatch_ks(Np / 32, [&](auto ks) -> int {
+    constexpr int KSN = decltype(ks)::value;
+    const int rc = opt_in_lds(cin_bwd_dx_bf16_wide_k<KSN>, lds);
+    if (rc != RSX_OK) return rc;
+    RSX_LAUNCH(cin_bwd_dx_bf16_wide_k<KSN>, grid, dim3(512), lds, stream, a);
+    RSX_CHECK_LAUNCH();
+    return RSX_OK;
+  });
 }
 
 int cin_wide_dx0_reduce(const float* const* parts, const int* tiles, int njobs, float* dX0, int acc, int B, int F,

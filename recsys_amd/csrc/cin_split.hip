@@ -5,108 +5,38 @@
 // 8-bit-significand operands EXACTLY and accumulates in fp32.  An fp32 number is the exact sum of three bf16 numbers
 // (x = x1 + x2 + x3, x1 = bf16(x), x2 = bf16(x - x1), x3 = x - x1 - x2: 8 + 8 + 8 significand bits), so a product of two fp32
 // numbers is the sum of nine exact bf16 products; the six with i + j <= 4 carry everything above 2^-24 of the product:
-//   NS = 3   x1y1 + (x1y2 + x2y1) + (x1y3 + x2y2 + x3y1): fp32-grade (|dropped| < 3 * 2^-24 |xy|), 6 MFMAs = 3/8 of the fp32
-//            MFMA's time for the same k -- this is the PARITY path of the bf16 matrix cores (1e-5 against the oracle)
-//   NS = 2   x1y1 + x1y2 + x2y1: 2^-16-grade products (3 MFMAs)
-//   NS = 1   x1y1: plain bf16 operands (what cin_bf16.hip computes)
+//   x1y1 + (x1y2 + x2y1) + (x1y3 + x2y2 + x3y1): fp32-grade (|dropped| < 3 * 2^-24 |xy|), 6 MFMAs = 3/8 of the fp32 MFMA's time
+//   for the same k -- this is the PARITY path of the bf16 matrix cores (1e-5 against the oracle).
+// Two forms are built (ns of the C ABI): ns = 3, the three bf16 planes above in every launch ("first form" below), and ns = 4,
+// forward / data gradients with two scaled fp16 planes per operand ("deep-ring kernels" below, the default of xdeepfm.py) and
+// the weight gradients on three bf16 planes.  ns = 1 / 2 (fewer planes: A/B arithmetic of round 5) answer RSX_EUNSUPPORTED; the
+// plain bf16-operand path is csrc/cin_bf16.hip.
 // Everything that is not a contraction operand (X0 row scaling, bias, relu, every sum) is fp32, as in the other two paths.
 //
-// Work split (forward; the backward mirrors it): a workgroup of 8 waves owns 8 examples and one 16-wide tile of outputs n,
-// and walks the fields two at a time -- waves 0,2,4,6 take the even field, waves 1,3,5,7 the odd one, wave pair p the
-// examples 2p, 2p + 1.  The filter fragments of a step (2 fields x NS planes x KS k-steps, 1 KiB each) come through LDS
+// Work split of the first form (forward; the backward mirrors it): a workgroup of 4 waves owns 4 examples and one 16-wide tile
+// of outputs n, and walks the fields two at a time -- waves 0, 2 take the even field, waves 1, 3 the odd one, wave pair p the
+// examples 2p, 2p + 1.  The filter fragments of a step (2 fields x 3 planes x KS k-steps, 1 KiB each) come through LDS
 // once per workgroup (double buffered, one barrier per step, the next step's loads in flight during the MFMAs), so a
-// fragment is read from L2 once per 8 examples; the Xk operand of a wave's two examples is split once and stays in
-// registers (NS x 2 x KS quads).  Per step and wave: 2 examples x (1 | 3 | 6) terms x KS MFMAs.
+// fragment is read from L2 once per 4 examples; the Xk operand of a wave's two examples is split once and stays in
+// registers (3 x 2 x KS quads).  Per step and wave: 2 examples x 6 terms x KS MFMAs.
 // Sums in fixed order (terms smallest first, k-steps, fields in step order, the two field parities at the end).
 #include "rsx_common.h"
 #include "gather_two_device.h"
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16_t;
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(1))) float gfloat_t;
+#include "split_device.h"
 
 namespace {
 
 constexpr int CS_D = 16;
 constexpr int CS_FP = 40;       // fields, padded (X0 reads as zero past F): F <= 40
 constexpr int CS_MAXJ = 4;
-
-__device__ __forceinline__ f32x4 mfma_bf16(bf16x8 a, bf16x8 b, f32x4 c) {
-  return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
-}
-__device__ __forceinline__ uint32_t pack2(float lo, float hi) {
-  bf16x2 v;
-  v[0] = (bf16_t)lo;
-  v[1] = (bf16_t)hi;
-  return __builtin_bit_cast(uint32_t, v);
-}
-inline int rup(int x, int m) { return (x + m - 1) / m * m; }
-
-// two fp32 values -> NS packed bf16 pairs: plane s holds bf16 of what the planes before it left over
-template <int NS>
-__device__ __forceinline__ void split2(float lo, float hi, uint32_t (&out)[NS]) {
-#pragma unroll
-  for (int s = 0; s < NS; ++s) {
-    const uint32_t pk = pack2(lo, hi);
-    out[s] = pk;
-    if (s + 1 < NS) {
-      lo -= __uint_as_float(pk << 16);
-      hi -= __uint_as_float(pk & 0xffff0000u);
-    }
-  }
-}
-// eight fp32 values (two float4) -> NS operand quads
-template <int NS>
-__device__ __forceinline__ void split8(float4 a, float4 b, bf16x8 (&out)[NS]) {
-  uint32_t p0[NS], p1[NS], p2[NS], p3[NS];
-  split2<NS>(a.x, a.y, p0);
-  split2<NS>(a.z, a.w, p1);
-  split2<NS>(b.x, b.y, p2);
-  split2<NS>(b.z, b.w, p3);
-#pragma unroll
-  for (int s = 0; s < NS; ++s) out[s] = __builtin_bit_cast(bf16x8, (u32x4){p0[s], p1[s], p2[s], p3[s]});
-}
-
-// T += sum over the kept terms (smallest first) and the k-steps of A-plane x B-plane
-// RSX_CIN_DBG (probe builds only, scripts/cin_split_where.sh; results are WRONG): 1 = one VALU fma in place of every MFMA, 2 = no
-// global filter loads inside the field loop, 3 = no barrier inside the field loop
-#ifndef RSX_CIN_DBG
-#define RSX_CIN_DBG 0
-#endif
-template <int NS, int KS>
-__device__ __forceinline__ f32x4 split_mma(const bf16x8 (&a)[NS][KS], const bf16x8 (&b)[NS][KS], f32x4 T) {
-#pragma unroll
-  for (int lvl = NS - 1; lvl >= 0; --lvl)          // lvl = i + j (zero based): 2^-8lvl relative size
-#pragma unroll
-    for (int sa = 0; sa <= lvl; ++sa)
-#pragma unroll
-      for (int ks = 0; ks < KS; ++ks) {
-#if RSX_CIN_DBG == 1
-        T[0] = __builtin_fmaf(__builtin_bit_cast(f32x4, a[sa][ks])[0], __builtin_bit_cast(f32x4, b[lvl - sa][ks])[0], T[0]);
-#else
-        T = mfma_bf16(a[sa][ks], b[lvl - sa][ks], T);
-#endif
-      }
-  return T;
-}
-template <int NS, int KS>
-__device__ __forceinline__ f32x4 split_mma_ba(const bf16x8 (&a)[NS][KS], const bf16x8 (&b)[NS][KS], f32x4 T) {   // (b as the MFMA's first operand)
-#pragma unroll
-  for (int lvl = NS - 1; lvl >= 0; --lvl)
-#pragma unroll
-    for (int sa = 0; sa <= lvl; ++sa)
-#pragma unroll
-      for (int ks = 0; ks < KS; ++ks) T = mfma_bf16(b[lvl - sa][ks], a[sa][ks], T);
-  return T;
-}
+constexpr int CS_E = 4;         // examples per workgroup of the first form (two independent 256-thread workgroups per CU; 8 measured slower)
+constexpr int CS_H2 = 4;        // ns of the two-fp16-plane mode
+static_assert(CS_FP == StageX0<CS_E>::FP && CS_D == StageX0<CS_E>::D, "StageX0's layout");
 
 // ------------------------------------------------------------------------------------------------ filter preparation
-// Fragment-major bf16 images, NS planes each (plane stride = the image size):
-//   W16  [NS][F][H16/16][Np/32][64][8]: element j of lane (i, kq) = W[f][h = 16 ht + i][n = 32 ks + 8 kq + j]   (A of dX)
-//   Wt16 [NS][F][N16/16][Hp/32][64][8]: element j of lane (i, kq) = W[f][h = 32 ks + 8 kq + j][n = 16 nt + i]   (B of fwd)
+// Fragment-major bf16 images, three planes each (plane stride = the image size):
+//   W16  [3][F][H16/16][Np/32][64][8]: element j of lane (i, kq) = W[f][h = 16 ht + i][n = 32 ks + 8 kq + j]   (A of dX)
+//   Wt16 [3][F][N16/16][Hp/32][64][8]: element j of lane (i, kq) = W[f][h = 32 ks + 8 kq + j][n = 16 nt + i]   (B of fwd)
 struct CsPrepJob { const float* W; bf16_t* W16; bf16_t* Wt16; float* winv; int H, N, H16, N16, Hp, Np; long long end; };
 struct CsPrepArgs {
   CsPrepJob job[CS_MAXJ];
@@ -123,7 +53,6 @@ struct CsPrepArgs {
     if (b_ < (P).gt.B) RSX_GATHER_TWO_EXAMPLE(16, (P).gt, b_, (int)(threadIdx.x & 63));       \
     return;                                                                                   \
   }
-template <int NS>
 __global__ __launch_bounds__(256) void cin_split_prep_k(const CsPrepArgs p) {
   CS_PREP_GATHER_ROLE(p)
   const long long total = p.job[p.njobs - 1].end;           // operand quads (of one plane) over all jobs
@@ -162,50 +91,21 @@ __global__ __launch_bounds__(256) void cin_split_prep_k(const CsPrepArgs p) {
         v[j] = src[(size_t)(h < jb.H ? h : jb.H - 1) * jb.N] * ((h < jb.H && n < jb.N) ? 1.f : 0.f);
       }
     }
-    bf16x8 o[NS];
-    split8<NS>(make_float4(v[0], v[1], v[2], v[3]), make_float4(v[4], v[5], v[6], v[7]), o);
+    bf16x8 o[3];
+    split8(make_float4(v[0], v[1], v[2], v[3]), make_float4(v[4], v[5], v[6], v[7]), o);
     bf16_t* dst = (first ? jb.W16 : jb.Wt16) + q * 8;
     const size_t plane = (first ? n1 : n2) * 8;
 #pragma unroll
-    for (int s = 0; s < NS; ++s) *reinterpret_cast<bf16x8*>(dst + (size_t)s * plane) = o[s];
+    for (int s = 0; s < 3; ++s) *reinterpret_cast<bf16x8*>(dst + (size_t)s * plane) = o[s];
   }
 }
 
-// X0 of the workgroup's E examples -> LDS [E][CS_FP * 16], zeros for the fields past F: 3 float4 per thread (E * 160 items over
-// 64 E threads), requested together
-template <int E>
-struct StageX0 {
-  static constexpr int NTHR = 64 * E;
-  float4 v[3];
-  __device__ __forceinline__ void load(const float* X0, int b0, int B, int F, int tid) {
-#pragma unroll
-    for (int u = 0; u < 3; ++u) {
-      const int e4 = tid + NTHR * u;
-      const int ex = e4 / (CS_FP * 4), r = e4 % (CS_FP * 4);
-      // (unconditional loads from clamped addresses, zeroed afterwards: a load under a condition becomes a branch, and the
-      // compiler waits for each of them in turn)
-      const int exc = ex < E ? ex : E - 1;
-      const bool ok = e4 < E * CS_FP * 4 && (r >> 2) < F && b0 + ex < B;
-      const int bc = b0 + exc < B ? b0 + exc : B - 1, rc = (r >> 2) < F ? r : 0;
-      const float4 t = reinterpret_cast<const float4*>(X0 + (size_t)bc * F * CS_D)[rc];
-      v[u] = make_float4(ok ? t.x : 0.f, ok ? t.y : 0.f, ok ? t.z : 0.f, ok ? t.w : 0.f);
-    }
-  }
-  __device__ __forceinline__ void store(float* sX0, int tid) const {
-#pragma unroll
-    for (int u = 0; u < 3; ++u) {
-      const int e4 = tid + NTHR * u;
-      if (e4 < E * CS_FP * 4) reinterpret_cast<float4*>(sX0)[e4] = v[u];
-    }
-  }
-};
-
-// [E][rows][16] fp32 (through `ld(e, row, quarter)`, zeros past the real rows) -> LDS, transposed to dst[e][d][RP] fp32 (rows
+// [CS_E][rows][16] fp32 (through `ld(e, row, quarter)`, zeros past the real rows) -> LDS, transposed to dst[e][d][RP] fp32 (rows
 // contiguous: what the MFMA's k index walks), RP = 32 KS + 4.  2 KS float4 per thread, all requested before the first store;
 // lanes = (quarter fastest, row): a wave's 64 scalar stores hit 64 banks.
-template <int KS, int E>
+template <int KS>
 struct StageRowsF32 {
-  static constexpr int RP = 32 * KS + 4, NTHR = 64 * E;
+  static constexpr int RP = 32 * KS + 4, NTHR = 64 * CS_E;
   float4 v[2 * KS];
   template <typename Load>
   __device__ __forceinline__ void load(int tid, Load ld) {
@@ -230,16 +130,16 @@ struct StageRowsF32 {
   }
 };
 
-// The filter fragments of one step: 2 fields x NS planes x KS k-steps, 1 KiB each, contiguous in LDS in that order, copied by
+// The filter fragments of one step: 2 fields x 3 planes x KS k-steps, 1 KiB each, contiguous in LDS in that order, copied by
 // global_load_lds_dwordx4 (L2 -> LDS without staging registers or a ds_write pass: the register-staged form spent 13 LDS cycles
 // per 1-KiB ds_write_b128 AFTER the step's MFMAs, before its barrier).  Item = one 16-byte lane quad, U per thread; a wave's 64
 // items are one fragment = 1 KiB contiguous on both sides (the LDS destination of an LDS-DMA is wave-uniform base + lane * 16).
 // f >= F is clamped (its X0 is zero); a ring slot is padded to U * NTHR quads (no conditional issue).
 typedef __attribute__((address_space(3))) void lds_void_t;
 typedef __attribute__((address_space(1))) const void glb_void_t;
-template <int NS, int KS, int E>
+template <int KS>
 struct StageW {
-  static constexpr int FRAGS = 2 * NS * KS, NTHR = 64 * E;
+  static constexpr int FRAGS = 2 * 3 * KS, NTHR = 64 * CS_E;
   static constexpr int U = (FRAGS * 64 + NTHR - 1) / NTHR;
   static constexpr int SLOT = U * NTHR * 8;        // bf16 elements per ring slot
   // base: image + (tile * KS) * 512 elements; fstride: elements per field; plane: elements per plane
@@ -248,7 +148,7 @@ struct StageW {
     for (int u = 0; u < U; ++u) {
       const int it = tid + NTHR * u;
       const int lane = it & 63, frag = (it >> 6) < FRAGS ? (it >> 6) : FRAGS - 1;
-      const int ks = frag % KS, sp = (frag / KS) % NS, par = frag / (KS * NS);
+      const int ks = frag % KS, sp = (frag / KS) % 3, par = frag / (KS * 3);
       const int f = f0 + par < F ? f0 + par : F - 1;
       const bf16_t* src = base + (size_t)sp * plane + (size_t)f * fstride + (size_t)ks * 512 + lane * 8;
       __builtin_amdgcn_global_load_lds((glb_void_t*)src, (lds_void_t*)(slot + (size_t)(it - lane) * 8), 16, 0, 0);
@@ -257,25 +157,15 @@ struct StageW {
 };
 
 constexpr size_t cs_max(size_t a, size_t b) { return a > b ? a : b; }
-#if RSX_CIN_DBG == 2
-#define CS_DBG_LOAD(X)
-#else
-#define CS_DBG_LOAD(X) X
-#endif
-#if RSX_CIN_DBG == 3
-#define CS_DBG_BARRIER
-#else
-#define CS_DBG_BARRIER __syncthreads();
-#endif
-// LDS of the forward / data-gradient launches: sX0 | ring slot 0 | ring slot 1 | staged operand rows [E][16][32 KS + 4] f32 (dead
+// LDS of the forward / data-gradient launches: sX0 | ring slot 0 | ring slot 1 | staged operand rows [CS_E][16][32 KS + 4] f32 (dead
 // once the operands are in registers; the waves' partial sums reuse it).  Where two 256-thread workgroups would not fit a CU
 // side by side (80 KiB each), slot 1 ALIASES the staged rows and is filled after they were consumed (one exposed L2 round
 // trip in the prologue).
-template <int NS, int KS, int E>
+template <int KS>
 struct CsLds {
-  static constexpr size_t X0 = (size_t)E * CS_FP * CS_D * 4, SLOT = (size_t)StageW<NS, KS, E>::SLOT * 2;
-  static constexpr size_t ROWS = cs_max((size_t)E * 16 * (32 * KS + 4) * 4, (size_t)E * 2 * 256 * 4);
-  static constexpr bool ALIAS = E == 4 && X0 + 2 * SLOT + ROWS > 80 * 1024;
+  static constexpr size_t X0 = (size_t)CS_E * CS_FP * CS_D * 4, SLOT = (size_t)StageW<KS>::SLOT * 2;
+  static constexpr size_t ROWS = cs_max((size_t)CS_E * 16 * (32 * KS + 4) * 4, (size_t)CS_E * 2 * 256 * 4);
+  static constexpr bool ALIAS = X0 + 2 * SLOT + ROWS > 80 * 1024;
   static constexpr size_t TOTAL = X0 + SLOT + (ALIAS ? cs_max(SLOT, ROWS) : SLOT + ROWS);
 };
 
@@ -283,24 +173,23 @@ struct CsLds {
 struct CsFwdArgs {
   const float* X0;      // [B, F, 16]
   const float* Xk;      // [B, H, 16]
-  const bf16_t* Wt16;   // NS planes, see cin_split_prep_k
+  const bf16_t* Wt16;   // the planes, see cin_split_prep_k / cin_split_prep_h2_k
   const float* c;       // [N]
   float* out;           // [B, N, 16]
   int B, F, H, N, N16, Hp;
   const float* winv;    // [F] inverse scales of the filter planes (mode 4)
 };
 
-// grid = (N16 / 16, ceil(B / E)), block = 64 E (E = 4: two workgroups per CU, their barriers independent -- one's MFMAs cover
-// the other's loads, LDS traffic and barrier waits; E = 8: one workgroup per CU, half the filter traffic from L2).
-// dyn LDS: CsLds.
-template <int NS, int KS, int E>
-__global__ __launch_bounds__(64 * E, E == 4 ? 2 : 1) void cin_split_fwd_k(const CsFwdArgs p) {
+// grid = (N16 / 16, ceil(B / 4)), block = 256 (two workgroups per CU, their barriers independent -- one's MFMAs cover the other's
+// loads, LDS traffic and barrier waits).  dyn LDS: CsLds.
+template <int KS>
+__global__ __launch_bounds__(64 * CS_E, 2) void cin_split_fwd_k(const CsFwdArgs p) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
-  constexpr int HP = 32 * KS + 4, SLOT = StageW<NS, KS, E>::SLOT;
+  constexpr int NS = 3, E = CS_E, HP = 32 * KS + 4, SLOT = StageW<KS>::SLOT;
   float* sX0 = lds;                                                   // [E][CS_FP*16]
   bf16_t* sW0 = reinterpret_cast<bf16_t*>(sX0 + E * CS_FP * CS_D);    // ring slot 0
   bf16_t* sW1 = sW0 + SLOT;                                           // ring slot 1
-  constexpr bool ALIAS = CsLds<NS, KS, E>::ALIAS;
+  constexpr bool ALIAS = CsLds<KS>::ALIAS;
   float* sXk = reinterpret_cast<float*>(ALIAS ? sW1 : sW1 + SLOT);    // [E][16][HP]
   float* sR = sXk;                                                    // [E waves][2][4][64] at the end
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
@@ -310,13 +199,13 @@ __global__ __launch_bounds__(64 * E, E == 4 ? 2 : 1) void cin_split_fwd_k(const 
   const bf16_t* wbase = p.Wt16 + (size_t)blockIdx.x * KS * 512;
   const size_t fstride = (size_t)p.N16 * p.Hp, plane = (size_t)p.F * fstride;
   const int nstep = (p.F + 1) / 2;
-  using GW = StageW<NS, KS, E>;
+  using GW = StageW<KS>;
   GW::issue(wbase, fstride, plane, 0, p.F, tid, sW0);
   if constexpr (!ALIAS) GW::issue(wbase, fstride, plane, 2, p.F, tid, sW1);
   StageX0<E> sx;
   sx.load(p.X0, b0, p.B, p.F, tid);
   {
-    StageRowsF32<KS, E> sr;
+    StageRowsF32<KS> sr;
     sr.load(tid, [&](int e, int h, int dq) {
       const bool ok = b0 + e < p.B && h < p.H;
       const int bc = b0 + e < p.B ? b0 + e : p.B - 1, hc = h < p.H ? h : p.H - 1;
@@ -334,7 +223,7 @@ __global__ __launch_bounds__(64 * E, E == 4 ? 2 : 1) void cin_split_fwd_k(const 
     for (int ks = 0; ks < KS; ++ks) {
       const float4* src = reinterpret_cast<const float4*>(sXk + ((size_t)(e0 + e) * 16 + i) * HP + 32 * ks + 8 * kq);
       bf16x8 t[NS];
-      split8<NS>(src[0], src[1], t);
+      split8(src[0], src[1], t);
 #pragma unroll
       for (int s = 0; s < NS; ++s) a[e][s][ks] = t[s];
     }
@@ -353,19 +242,19 @@ __global__ __launch_bounds__(64 * E, E == 4 ? 2 : 1) void cin_split_fwd_k(const 
   }
 #define CS_FWD_STEP(ST, W, WN)                                                                                        \
   {                                                                                                                   \
-    CS_DBG_LOAD(GW::issue(wbase, fstride, plane, 2 * ((ST) + 2), p.F, tid, ((ST) & 1) ? sW1 : sW0);)                  \
+    GW::issue(wbase, fstride, plane, 2 * ((ST) + 2), p.F, tid, ((ST) & 1) ? sW1 : sW0);                               \
     CS_READ_W((ST) + 1, WN)                                                                                           \
     const int f_ = 2 * (ST) + par;                                                                                    \
     const float m_ = f_ < CS_FP ? 1.f : 0.f;                                                                          \
     _Pragma("unroll") for (int e = 0; e < 2; ++e) {                                                                   \
-      const f32x4 T = split_mma<NS, KS>(a[e], W, (f32x4){0.f, 0.f, 0.f, 0.f});                                        \
+      const f32x4 T = split_mma<KS>(a[e], W, (f32x4){0.f, 0.f, 0.f, 0.f});                                            \
       const float4 x = *reinterpret_cast<const float4*>(sX0 + ((e0 + e) * CS_FP + (f_ < CS_FP ? f_ : CS_FP - 1)) * CS_D + kq * 4); \
       acc[e][0] = __builtin_fmaf(x.x * m_, T[0], acc[e][0]);                                                          \
       acc[e][1] = __builtin_fmaf(x.y * m_, T[1], acc[e][1]);                                                          \
       acc[e][2] = __builtin_fmaf(x.z * m_, T[2], acc[e][2]);                                                          \
       acc[e][3] = __builtin_fmaf(x.w * m_, T[3], acc[e][3]);                                                          \
     }                                                                                                                 \
-    CS_DBG_BARRIER /* (its fence waits for the step's LDS-DMA: vmcnt(0)) */                                           \
+    __syncthreads(); /* (its fence waits for the step's LDS-DMA: vmcnt(0)) */                                         \
   }
   bf16x8 w0[NS][KS], w1[NS][KS];
   CS_READ_W(0, w0)
@@ -399,9 +288,9 @@ __global__ __launch_bounds__(64 * E, E == 4 ? 2 : 1) void cin_split_fwd_k(const 
   }
 }
 
-// ------------------------------------------------------------------------ deep-ring kernels (the default): forward, dXk / dX0
-// What bounded cin_split_fwd_k / cin_split_dx_k (profiles/r05_y_cin_split_where.txt: 18 us with every MFMA replaced by one VALU
-// op, 12.8 us of MFMA issue at 2.4 GHz, 29 us together):
+// ---------------------------------------------------------------- deep-ring kernels (mode 4, the default): forward, dXk / dX0
+// What bounded cin_split_fwd_k / cin_split_dx_k (profiles/r05_y_cin_split_where.txt: 18 us with every MFMA replaced by one VALU op, 12.8 us of
+// MFMA issue at 2.4 GHz, 29 us together):
 //   * the compiler cannot tell an LDS-DMA's destination from the slot a ds_read reads and puts `s_waitcnt vmcnt(0)` in front of
 //     the first LDS read after every DMA issue: the prefetch distance of the ring was never more than the rest of ONE step;
 //   * the whole-step register double buffer (96 VGPRs of filter fragments) did not survive register allocation: the reads were
@@ -412,11 +301,11 @@ __global__ __launch_bounds__(64 * E, E == 4 ? 2 : 1) void cin_split_fwd_k(const 
 // slots, the DMA issued from inline assembly (invisible to the compiler's LDS alias check; addresses = SGPR base + lane * 16, all
 // scalar), the step's barrier waits for `vmcnt((R - 3) U)` -- a piece has R - 2 whole steps to land -- and the filter fragments go
 // through a ring of PF <= 6 register quads, each requested PF - 2 fragments ahead of its use (the next step's first ones before
-// the barrier).  A fragment's MFMAs go to one accumulator per (example, magnitude level): 2 NS independent chains; the levels
+// the barrier).  A fragment's MFMAs go to one accumulator per (example, magnitude level): 2 x 2 independent chains; the levels
 // are added smallest first at the end of the step.  Stamps + probe builds (scripts/stamp_probe_cin_split.py): the field loop is
 // MFMA issue now -- without DMA, barrier or fragment reads it is 4-14 % shorter, without the MFMAs half.
 //
-// MODE 4 ("h2"): the same contraction with TWO fp16 planes per operand (x = x1 + x2, 11 + 11 significand bits; the operand of
+// The operands (mode 4, "h2"): the same contraction with TWO fp16 planes per operand (x = x1 + x2, 11 + 11 significand bits; the operand of
 // one accumulation chain is scaled by a power of two so that its largest element sits at 2^14: per example for Xk / dpre, per
 // field for the filters, the scales divided out in fp32 after the chain) and the three products x1y1 + x1y2 + x2y1 -- HALF the
 // MFMAs of the three-plane bf16 form.  What it drops (x2y2, the planes' own rounding) is below 2^-22 of a product for every
@@ -425,28 +314,11 @@ __global__ __launch_bounds__(64 * E, E == 4 ? 2 : 1) void cin_split_fwd_k(const 
 // batch: no per-example scale can be divided out).
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
-constexpr int CS_H2 = 4;
 
-template <int MODE>
-struct SplitMode {                                   // MODE = 1..3: bf16 planes
-  static constexpr int NS = MODE;
-  static constexpr bool SCALED = false;
-  typedef bf16x8 quad;
-  static __device__ __forceinline__ f32x4 mma(quad a, quad b, f32x4 c) { return mfma_bf16(a, b, c); }
-  static __device__ __forceinline__ void split(float4 a, float4 b, quad (&out)[NS]) { split8<NS>(a, b, out); }
-};
-template <>
-struct SplitMode<CS_H2> {
+struct H2 {                                          // the scaled-fp16 pair
   static constexpr int NS = 2;
-  static constexpr bool SCALED = true;
   typedef f16x8 quad;
-  static __device__ __forceinline__ f32x4 mma(quad a, quad b, f32x4 c) {
-#ifdef RSX_CIN_H2_AS_BF16      // (probe builds only, WRONG results: is the fp16 MFMA itself slower than the bf16 one under load?)
-    return mfma_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c);
-#else
-    return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0);
-#endif
-  }
+  static __device__ __forceinline__ f32x4 mma(quad a, quad b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0); }
   static __device__ __forceinline__ void split2h(float lo, float hi, uint32_t (&out)[2]) {
     f16x2 p, q;
     p[0] = (_Float16)lo;
@@ -493,9 +365,9 @@ __device__ __forceinline__ void cs_wait_barrier() {
   asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)\n\ts_barrier" ::"n"(VM) : "memory");
 }
 
-template <int NS, int KS, int EXTRA>
+template <int KS, int EXTRA>
 struct Cs8 {
-  static constexpr int E = 8, NTHR = 512;
+  static constexpr int E = 8, NTHR = 512, NS = H2::NS;
   static constexpr int FR = NS * KS;                          // fragments of one field
   static constexpr int FRAGS = 2 * FR;                        // of one step (two fields)
   static constexpr int U = (FRAGS + 7) / 8;                   // DMA pieces per wave and step
@@ -525,12 +397,10 @@ struct Cs8 {
 
 // One step's MFMAs of a wave: the FR fragments of its field (ring slot `cur`, from the register ring w) against the split
 // operands of its two examples, T[e][level] += ...; WA: the filter fragment is the MFMA's first operand (data gradients).
-template <int MODE, int KS, int PF, bool WA>
-__device__ __forceinline__ void cs8_step_mma(const typename SplitMode<MODE>::quad (&a)[2][SplitMode<MODE>::NS][KS],
-                                             typename SplitMode<MODE>::quad (&w)[PF], const char* cur, const char* nxt,
-                                             f32x4 (&T)[2][SplitMode<MODE>::NS]) {
-  using M = SplitMode<MODE>;
-  constexpr int NS = M::NS, FR = NS * KS;
+template <int KS, int PF, bool WA>
+__device__ __forceinline__ void cs8_step_mma(const H2::quad (&a)[2][H2::NS][KS], H2::quad (&w)[PF], const char* cur, const char* nxt,
+                                             f32x4 (&T)[2][H2::NS]) {
+  constexpr int NS = H2::NS, FR = NS * KS;
 #pragma unroll
   for (int e = 0; e < 2; ++e)
 #pragma unroll
@@ -544,11 +414,7 @@ __device__ __forceinline__ void cs8_step_mma(const typename SplitMode<MODE>::qua
     for (int e = 0; e < 2; ++e)
 #pragma unroll
       for (int sa = 0; sa + s < NS; ++sa) {
-#if RSX_CIN_DBG == 1
-        T[e][s + sa][0] = __builtin_fmaf(__builtin_bit_cast(f32x4, a[e][sa][ks])[0], __builtin_bit_cast(f32x4, w[j % PF])[0], T[e][s + sa][0]);
-#else
-        T[e][s + sa] = WA ? M::mma(w[j % PF], a[e][sa][ks], T[e][s + sa]) : M::mma(a[e][sa][ks], w[j % PF], T[e][s + sa]);
-#endif
+        T[e][s + sa] = WA ? H2::mma(w[j % PF], a[e][sa][ks], T[e][s + sa]) : H2::mma(a[e][sa][ks], w[j % PF], T[e][s + sa]);
       }
     __builtin_amdgcn_sched_barrier(0);
     // the quad of fragment j - 1 (its MFMAs were issued a fragment ago) takes fragment j - 1 + PF: of this step, or the next one's
@@ -556,27 +422,16 @@ __device__ __forceinline__ void cs8_step_mma(const typename SplitMode<MODE>::qua
     const int jn = j - LAG + PF;
     const int jj = jn < FR ? jn : jn - FR;
     const char* src = (jn < FR ? cur : nxt) + ((jj % NS) * KS + jj / NS) * 1024;
-#if RSX_CIN_DBG != 4
-    w[jn % PF] = __builtin_bit_cast(typename M::quad, *reinterpret_cast<const uint4*>(src));
-#endif
+    w[jn % PF] = __builtin_bit_cast(H2::quad, *reinterpret_cast<const uint4*>(src));
     __builtin_amdgcn_sched_barrier(0);
   }
 }
-#if RSX_CIN_DBG == 2
-#define CS8_STEP_BARRIER(C8) cs_wait_barrier<0>()
-#elif RSX_CIN_DBG == 3
-#define CS8_STEP_BARRIER(C8) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory")
-#else
-#define CS8_STEP_BARRIER(C8) cs_wait_barrier<C8::VM>()
-#endif
-
-// grid = (N16 / 16, ceil(B / 8)), block = 512, dyn LDS = Cs8<NS, KS, SCALED ? 256 : 0>::TOTAL: sX0 [8][CS_FP * 16] f32 | R ring slots | the
-// filters' inverse scales [CS_FP] (MODE 4)
-template <int MODE, int KS>
+// grid = (N16 / 16, ceil(B / 8)), block = 512, dyn LDS = Cs8<KS, 256>::TOTAL: sX0 [8][CS_FP * 16] f32 | R ring slots | the filters'
+// inverse scales [CS_FP]
+template <int KS>
 __global__ __launch_bounds__(512, 1) void cin_split_fwd8_k(const CsFwdArgs p) {
-  using M = SplitMode<MODE>;
-  constexpr int NS = M::NS;
-  using C8 = Cs8<NS, KS, M::SCALED ? 256 : 0>;
+  constexpr int NS = H2::NS;
+  using C8 = Cs8<KS, 256>;
   constexpr int E = 8, R = C8::R, PF = C8::PF, FR = C8::FR, SLOTB = C8::SLOTB;
   extern __shared__ __attribute__((aligned(16))) float lds[];
   float* sX0 = lds;
@@ -597,9 +452,9 @@ __global__ __launch_bounds__(512, 1) void cin_split_fwd8_k(const CsFwdArgs p) {
   for (int s = 0; s < R - 1; ++s) C8::issue(img, fstrideB, planeB, s < nstep ? s : nstep - 1, p.F, wv, lane16, ring_lds + s * SLOTB);
   StageX0<E> sx;
   sx.load(p.X0, b0, p.B, p.F, tid);
-  if (M::SCALED && tid < CS_FP) sInv[tid] = tid < p.F ? p.winv[tid] : 0.f;
-  typename M::quad a[2][NS][KS];                   // Xk[b0 + e0 + e][h = 32 ks + 8 kq + j][d = i], split; straight from L2
-  float inv_x[2] = {1.f, 1.f};
+  if (tid < CS_FP) sInv[tid] = tid < p.F ? p.winv[tid] : 0.f;
+  H2::quad a[2][NS][KS];                   // Xk[b0 + e0 + e][h = 32 ks + 8 kq + j][d = i], split; straight from L2
+  float inv_x[2];                                  // the operands' scales, divided out after a chain
 #pragma unroll
   for (int e = 0; e < 2; ++e) {
     const int b = b0 + e0 + e;
@@ -622,14 +477,14 @@ __global__ __launch_bounds__(512, 1) void cin_split_fwd8_k(const CsFwdArgs p) {
 #pragma unroll
       for (int j = 0; j < 8; ++j) {
         v[ks][j] *= (32 * ks + 8 * kq + j) < p.H ? bm : 0.f;
-        if (M::SCALED) mx = fmaxf(mx, fabsf(v[ks][j]));
+        mx = fmaxf(mx, fabsf(v[ks][j]));
       }
-    float sc = 1.f;
-    if (M::SCALED) cs_pow2_scale(cs_wave_max(mx), sc, inv_x[e]);
+    float sc;
+    cs_pow2_scale(cs_wave_max(mx), sc, inv_x[e]);
 #pragma unroll
     for (int ks = 0; ks < KS; ++ks) {
-      typename M::quad t[NS];
-      M::split(make_float4(v[ks][0] * sc, v[ks][1] * sc, v[ks][2] * sc, v[ks][3] * sc),
+      H2::quad t[NS];
+      H2::split(make_float4(v[ks][0] * sc, v[ks][1] * sc, v[ks][2] * sc, v[ks][3] * sc),
                make_float4(v[ks][4] * sc, v[ks][5] * sc, v[ks][6] * sc, v[ks][7] * sc), t);
 #pragma unroll
       for (int s = 0; s < NS; ++s) a[e][s][ks] = t[s];
@@ -640,35 +495,35 @@ __global__ __launch_bounds__(512, 1) void cin_split_fwd8_k(const CsFwdArgs p) {
   cs_wait_barrier<0>();                            // sX0 and the first R - 1 slots
   RSX_STAMP(2, st0);
   const char* rd = ring + (size_t)par * FR * 1024 + lane16;      // this wave's fragments of slot 0
-  typename M::quad w[PF];                          // at a step's entry: its fragments 0 .. PF - 2 (requested during the step before)
+  H2::quad w[PF];                          // at a step's entry: its fragments 0 .. PF - 2 (requested during the step before)
 #pragma unroll
   for (int j = 0; j < PF; ++j)
-    w[j] = __builtin_bit_cast(typename M::quad, *reinterpret_cast<const uint4*>(rd + ((j % NS) * KS + j / NS) * 1024));
+    w[j] = __builtin_bit_cast(H2::quad, *reinterpret_cast<const uint4*>(rd + ((j % NS) * KS + j / NS) * 1024));
   f32x4 acc[2] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
   int sl = 0;                                      // ring slot of the current step
   for (int st = 0; st < nstep; ++st) {
     const int sln = sl + 1 == R ? 0 : sl + 1, slp = sl == 0 ? R - 1 : sl - 1;
     const int stn = st + R - 1 < nstep ? st + R - 1 : nstep - 1;
-    CS_DBG_LOAD(C8::issue(img, fstrideB, planeB, stn, p.F, wv, lane16, ring_lds + slp * SLOTB);)      // (slot of step st - 1: free since its barrier)
+    C8::issue(img, fstrideB, planeB, stn, p.F, wv, lane16, ring_lds + slp * SLOTB);      // (slot of step st - 1: free since its barrier)
     const int f_ = 2 * st + par;
     float4 x[2];
 #pragma unroll
     for (int e = 0; e < 2; ++e) x[e] = *reinterpret_cast<const float4*>(sX0 + ((e0 + e) * CS_FP + f_) * CS_D + kq * 4);
-    const float wi = M::SCALED ? sInv[f_] : 1.f;
+    const float wi = sInv[f_];
     f32x4 T[2][NS];
-    cs8_step_mma<MODE, KS, PF, false>(a, w, rd + (size_t)sl * SLOTB, rd + (size_t)sln * SLOTB, T);
+    cs8_step_mma<KS, PF, false>(a, w, rd + (size_t)sl * SLOTB, rd + (size_t)sln * SLOTB, T);
 #pragma unroll
     for (int e = 0; e < 2; ++e) {
       f32x4 t = T[e][NS - 1];
 #pragma unroll
       for (int l = NS - 2; l >= 0; --l) t += T[e][l];
-      if (M::SCALED) x[e] = f4_scale(wi * inv_x[e], x[e]);
+      x[e] = f4_scale(wi * inv_x[e], x[e]);
       acc[e][0] = __builtin_fmaf(x[e].x, t[0], acc[e][0]);
       acc[e][1] = __builtin_fmaf(x[e].y, t[1], acc[e][1]);
       acc[e][2] = __builtin_fmaf(x[e].z, t[2], acc[e][2]);
       acc[e][3] = __builtin_fmaf(x[e].w, t[3], acc[e][3]);
     }
-    CS8_STEP_BARRIER(C8);
+    cs_wait_barrier<C8::VM>();
     sl = sln;
   }
   RSX_STAMP(3, st0);
@@ -770,7 +625,7 @@ __global__ __launch_bounds__(256) void cin_split_prep_h2_k(const CsPrepArgs p) {
       const int q = q0 + u * 256 * CS_H2_PARTS;                                                                      \
       if (q < (NQ)) {                                                                                                \
         f16x8 o[2];                                                                                                  \
-        SplitMode<CS_H2>::split(make_float4(v[u][0], v[u][1], v[u][2], v[u][3]), make_float4(v[u][4], v[u][5], v[u][6], v[u][7]), o); \
+        H2::split(make_float4(v[u][0], v[u][1], v[u][2], v[u][3]), make_float4(v[u][4], v[u][5], v[u][6], v[u][7]), o); \
         bf16_t* dst = (DSTBASE) + ((size_t)f * (NQ) + q) * 8;   /* (quad index inside a plane of the layout) */          \
         _Pragma("unroll") for (int s2 = 0; s2 < 2; ++s2) *reinterpret_cast<f16x8*>(dst + (size_t)s2 * (PLANE)) = o[s2]; \
       }                                                                                                              \
@@ -785,14 +640,14 @@ __global__ __launch_bounds__(256) void cin_split_prep_h2_k(const CsPrepArgs p) {
 struct CsDxArgs {
   const float* X0;      // [B, F, 16]
   const float* Xk;      // [B, H, 16]
-  const bf16_t* W16;    // NS planes, see cin_split_prep_k
+  const bf16_t* W16;    // the planes, see cin_split_prep_k / cin_split_prep_h2_k
   const float* out;     // [B, N, 16] this layer's relu output
   const float* dout;    // [B, N, 16] gradient wrt the relu output (nullable when gs is given)
   const float* gs;      // [B] nullable: direct-connect gradient gs[b] * wout[n], broadcast over d, added to dout
   const float* wout;    // [N]
   float* dXk;           // [B, H, 16]
   float* dx0_parts;     // [HT][B][F*16] out: tile ht's share of dX0
-  bf16_t* dpre16;       // [NS][ceil(B/2)][N16/16][64][8] out (workgroups of tile 0): the dW kernel's B fragments, split
+  bf16_t* dpre16;       // [3][ceil(B/2)][N16/16][64][8] out (workgroups of tile 0): the dW kernel's B fragments, split
   float* dc_part;       // [B][N16] out (workgroups of tile 0): per-example column sums of dpre
   int acc_dxk;
   int B, F, H, N, H16, N16, Np;
@@ -800,24 +655,24 @@ struct CsDxArgs {
   int dw_planes;        // bf16 planes of dpre16 (what the weight-gradient launch multiplies)
 };
 
-// grid = (H16 / 16, ceil(B / E)), block = 64 E: workgroup = E examples x the 16 inputs h of tile blockIdx.x; waves as in the
+// grid = (H16 / 16, ceil(B / 4)), block = 256: workgroup = 4 examples x the 16 inputs h of tile blockIdx.x; waves as in the
 // forward (field parity x example pair).  U_f^T[h, d] = sum_n W_f[h, n] dpre[b, n, d]: A = W16 fragments (through the LDS ring),
 // B = dpre[b]^T (k = n, column = d) of the wave's two examples, split, in registers.
 //   dXk[b, h, d] += X0[b, f, d] U_f^T[h, d]   summed over the wave's fields in registers, the two parities through LDS
 //   dX0[b, f, d]  = sum_h Xk[b, h, d] U_f^T[h, d] over this tile's 16 h: four rows per lane, the four lane quarters by two
 //                   butterfly exchanges, collected in LDS, written to dx0_parts[tile] at the end (rsx_cin_dx0_reduce adds the tiles)
 // dyn LDS: CsLds.
-template <int NS, int KSN, int E>
-__global__ __launch_bounds__(64 * E, E == 4 ? 2 : 1) void cin_split_dx_k(const CsDxArgs p) {
+template <int KSN>
+__global__ __launch_bounds__(64 * CS_E, 2) void cin_split_dx_k(const CsDxArgs p) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
-  constexpr int NP = 32 * KSN + 4, SLOT = StageW<NS, KSN, E>::SLOT, NTHR = 64 * E;
+  constexpr int NS = 3, E = CS_E, NP = 32 * KSN + 4, SLOT = StageW<KSN>::SLOT, NTHR = 64 * E;
   float* sX0 = lds;                                                   // [E][CS_FP*16]
   bf16_t* sW0 = reinterpret_cast<bf16_t*>(sX0 + E * CS_FP * CS_D);    // ring slot 0
   bf16_t* sW1 = sW0 + SLOT;                                           // ring slot 1
-  constexpr bool ALIAS = CsLds<NS, KSN, E>::ALIAS;
+  constexpr bool ALIAS = CsLds<KSN>::ALIAS;
   float* sDp = reinterpret_cast<float*>(ALIAS ? sW1 : sW1 + SLOT);    // [E][16][NP]
   float* sR = sDp;                                                    // [E waves][2][4][64] at the end
-  float* sP = reinterpret_cast<float*>(reinterpret_cast<char*>(lds) + CsLds<NS, KSN, E>::TOTAL);   // [E][CS_FP][16]: dX0 of this tile
+  float* sP = reinterpret_cast<float*>(reinterpret_cast<char*>(lds) + CsLds<KSN>::TOTAL);   // [E][CS_FP][16]: dX0 of this tile
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
   const int i = lane & 15, kq = lane >> 4;
   const int par = wv & 1, e0 = (wv >> 1) * 2;
@@ -829,7 +684,7 @@ __global__ __launch_bounds__(64 * E, E == 4 ? 2 : 1) void cin_split_dx_k(const C
   const float* gsrc = p.gs ? p.gs : p.out;
   const float* wsrc = p.gs ? p.wout : p.out;
   const float dmul = p.dout ? 1.f : 0.f, gmul = p.gs ? 1.f : 0.f;
-  using GW = StageW<NS, KSN, E>;
+  using GW = StageW<KSN>;
   GW::issue(wbase, fstride, plane, 0, p.F, tid, sW0);
   if constexpr (!ALIAS) GW::issue(wbase, fstride, plane, 2, p.F, tid, sW1);
   StageX0<E> sx;
@@ -846,7 +701,7 @@ __global__ __launch_bounds__(64 * E, E == 4 ? 2 : 1) void cin_split_dx_k(const C
   }
   {
     // dpre = relu'(out) * (dout + gs * wout) of the E examples -> LDS, transposed (fp32: each wave splits its own two)
-    StageRowsF32<KSN, E> sr;
+    StageRowsF32<KSN> sr;
     sr.load(tid, [&](int e, int n, int dq) {
       const int b = b0 + e;
       const bool ok = b < p.B && n < p.N;
@@ -871,7 +726,7 @@ __global__ __launch_bounds__(64 * E, E == 4 ? 2 : 1) void cin_split_dx_k(const C
     for (int ks = 0; ks < KSN; ++ks) {
       const float4* src = reinterpret_cast<const float4*>(sDp + ((size_t)(e0 + e) * 16 + i) * NP + 32 * ks + 8 * kq);
       bf16x8 t[NS];
-      split8<NS>(src[0], src[1], t);
+      split8(src[0], src[1], t);
 #pragma unroll
       for (int s = 0; s < NS; ++s) bd[e][s][ks] = t[s];
     }
@@ -905,8 +760,8 @@ __global__ __launch_bounds__(64 * E, E == 4 ? 2 : 1) void cin_split_dx_k(const C
         // fragment of the dW kernel: lane (i = n & 15, kq = 2 (b & 1) + (d >> 3)), elements j = d & 7
         const size_t fr = ((((size_t)(b >> 1) * (p.N16 >> 4) + (n >> 4)) * 64 + (2 * (b & 1) + (dq >> 1)) * 16 + (n & 15)) * 8) + (dq & 1) * 4;
         uint32_t q0[NS], q1[NS];
-        split2<NS>(v.x, v.y, q0);
-        split2<NS>(v.z, v.w, q1);
+        split2(v.x, v.y, q0);
+        split2(v.z, v.w, q1);
 #pragma unroll
         for (int sp = 0; sp < NS; ++sp) *reinterpret_cast<uint2*>(p.dpre16 + (size_t)sp * dplane + fr) = make_uint2(q0[sp], q1[sp]);
       }
@@ -924,7 +779,7 @@ __global__ __launch_bounds__(64 * E, E == 4 ? 2 : 1) void cin_split_dx_k(const C
     const int fc_ = f_ < CS_FP ? f_ : CS_FP - 1;                                                                      \
     const float m_ = f_ < CS_FP ? 1.f : 0.f;                                                                          \
     _Pragma("unroll") for (int e = 0; e < 2; ++e) {                                                                   \
-      const f32x4 U = split_mma_ba<NS, KSN>(bd[e], W, (f32x4){0.f, 0.f, 0.f, 0.f});                                   \
+      const f32x4 U = split_mma<KSN, true>(bd[e], W, (f32x4){0.f, 0.f, 0.f, 0.f});                                    \
       const float x = sX0[((e0 + e) * CS_FP + fc_) * CS_D + i] * m_;                                                  \
       dxk[e][0] = __builtin_fmaf(x, U[0], dxk[e][0]);                                                                 \
       dxk[e][1] = __builtin_fmaf(x, U[1], dxk[e][1]);                                                                 \
@@ -980,13 +835,12 @@ __global__ __launch_bounds__(64 * E, E == 4 ? 2 : 1) void cin_split_dx_k(const C
 // grid = (H16 / 16, ceil(B / 8)), block = 512: workgroup = 8 examples x the 16 inputs h of tile blockIdx.x, waves = (field
 // parity, example pair) and the ring / register pipeline of cin_split_fwd8_k.  U_f^T[h, d] = sum_n W_f[h, n] dpre[b, n, d]:
 // A = W16 fragments, B = dpre[b]^T of the wave's two examples, formed from out / dout / gs * wout straight from L2 and split.
-// dyn LDS = Cs8<NS, KSN, 20480 + 256>::TOTAL: sX0 | ring | sP [8][CS_FP][16] (this tile's dX0) | inverse filter scales.
-template <int MODE, int KSN>
+// dyn LDS = Cs8<KSN, 20480 + 256>::TOTAL: sX0 | ring | sP [8][CS_FP][16] (this tile's dX0) | inverse filter scales.
+constexpr int CS8_DX_EXTRA = 8 * CS_FP * CS_D * 4 + 256;
+template <int KSN>
 __global__ __launch_bounds__(512, 1) void cin_split_dx8_k(const CsDxArgs p) {
-  using M = SplitMode<MODE>;
-  constexpr int NS = M::NS;
-  constexpr int PB = 8 * CS_FP * CS_D * 4;
-  using C8 = Cs8<NS, KSN, PB + (M::SCALED ? 256 : 0)>;
+  constexpr int NS = H2::NS;
+  using C8 = Cs8<KSN, CS8_DX_EXTRA>;
   constexpr int E = 8, R = C8::R, PF = C8::PF, FR = C8::FR, SLOTB = C8::SLOTB, NTHR = 512;
   extern __shared__ __attribute__((aligned(16))) float lds[];
   float* sX0 = lds;
@@ -1024,7 +878,7 @@ __global__ __launch_bounds__(512, 1) void cin_split_dx8_k(const CsDxArgs p) {
   const float dmul = p.dout ? 1.f : 0.f, gmul = p.gs ? 1.f : 0.f;
   StageX0<E> sx;
   sx.load(p.X0, b0, p.B, p.F, tid);
-  if (M::SCALED && tid < CS_FP) sInv[tid] = tid < p.F ? p.winv[tid] : 0.f;
+  if (tid < CS_FP) sInv[tid] = tid < p.F ? p.winv[tid] : 0.f;
   float xkv[2][4];                                 // Xk[b0 + e0 + e][h = 16 ht + 4 kq + r][d = i]
 #pragma unroll
   for (int e = 0; e < 2; ++e) {
@@ -1035,8 +889,8 @@ __global__ __launch_bounds__(512, 1) void cin_split_dx8_k(const CsDxArgs p) {
       xkv[e][r] = p.Xk[((size_t)(b < p.B ? b : p.B - 1) * p.H + (h < p.H ? h : p.H - 1)) * CS_D + i] * ((b < p.B && h < p.H) ? 1.f : 0.f);
     }
   }
-  typename M::quad bd[2][NS][KSN];                 // dpre[b0 + e0 + e][n = 32 ks + 8 kq + j][d = i], split
-  float inv_d[2] = {1.f, 1.f};
+  H2::quad bd[2][NS][KSN];                 // dpre[b0 + e0 + e][n = 32 ks + 8 kq + j][d = i], split
+  float inv_d[2];
   {
     // dpre = relu'(out) * (dout + gs * wout) of the wave's two examples: whole rows by coalesced float4 loads (32 KSN per lane,
     // all requested together), transposed through 8 KiB of LDS per wave (the ring's last 64 KiB: the filter DMA of those slots
@@ -1083,14 +937,14 @@ __global__ __launch_bounds__(512, 1) void cin_split_dx8_k(const CsDxArgs p) {
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
           v[ks][j] = scr[(32 * ks + 8 * kq + j) * CS_D + i];
-          if (M::SCALED) mx = fmaxf(mx, fabsf(v[ks][j]));
+          mx = fmaxf(mx, fabsf(v[ks][j]));
         }
-      float sc = 1.f;
-      if (M::SCALED) cs_pow2_scale(cs_wave_max(mx), sc, inv_d[e]);
+      float sc;
+      cs_pow2_scale(cs_wave_max(mx), sc, inv_d[e]);
 #pragma unroll
       for (int ks = 0; ks < KSN; ++ks) {
-        typename M::quad t[NS];
-        M::split(make_float4(v[ks][0] * sc, v[ks][1] * sc, v[ks][2] * sc, v[ks][3] * sc),
+        H2::quad t[NS];
+        H2::split(make_float4(v[ks][0] * sc, v[ks][1] * sc, v[ks][2] * sc, v[ks][3] * sc),
                  make_float4(v[ks][4] * sc, v[ks][5] * sc, v[ks][6] * sc, v[ks][7] * sc), t);
 #pragma unroll
         for (int s = 0; s < NS; ++s) bd[e][s][ks] = t[s];
@@ -1125,8 +979,8 @@ __global__ __launch_bounds__(512, 1) void cin_split_dx8_k(const CsDxArgs p) {
         // fragment of the dW kernel: lane (i = n & 15, kq = 2 (b & 1) + (d >> 3)), elements j = d & 7
         const size_t fr = ((((size_t)(b >> 1) * (p.N16 >> 4) + (n >> 4)) * 64 + (2 * (b & 1) + (dq >> 1)) * 16 + (n & 15)) * 8) + (dq & 1) * 4;
         uint32_t q0[3], q1[3];
-        split2<3>(v.x, v.y, q0);
-        split2<3>(v.z, v.w, q1);
+        split2(v.x, v.y, q0);
+        split2(v.z, v.w, q1);
 #pragma unroll
         for (int sp = 0; sp < 3; ++sp)
           if (sp < p.dw_planes) *reinterpret_cast<uint2*>(p.dpre16 + (size_t)sp * dplane + fr) = make_uint2(q0[sp], q1[sp]);
@@ -1142,29 +996,29 @@ __global__ __launch_bounds__(512, 1) void cin_split_dx8_k(const CsDxArgs p) {
   cs_wait_barrier<(NE >= 2 ? (R - 1 - NE) * C8::U : 0)>();
   RSX_STAMP(34, st0);
   const char* rd = ring + (size_t)par * FR * 1024 + lane16;
-  typename M::quad w[PF];
+  H2::quad w[PF];
 #pragma unroll
   for (int j = 0; j < PF; ++j)
-    w[j] = __builtin_bit_cast(typename M::quad, *reinterpret_cast<const uint4*>(rd + ((j % NS) * KSN + j / NS) * 1024));
+    w[j] = __builtin_bit_cast(H2::quad, *reinterpret_cast<const uint4*>(rd + ((j % NS) * KSN + j / NS) * 1024));
   f32x4 dxk[2] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
   int sl = 0;
   for (int st = 0; st < nstep; ++st) {
     const int sln = sl + 1 == R ? 0 : sl + 1, slp = sl == 0 ? R - 1 : sl - 1;
     const int stn = st + R - 1 < nstep ? st + R - 1 : nstep - 1;
-    CS_DBG_LOAD(C8::issue(img, fstrideB, planeB, sbase + stn, p.F, wv, lane16, ring_lds + slp * SLOTB);)
+    C8::issue(img, fstrideB, planeB, sbase + stn, p.F, wv, lane16, ring_lds + slp * SLOTB);
     const int f_ = 2 * (sbase + st) + par;
     float x[2];
 #pragma unroll
     for (int e = 0; e < 2; ++e) x[e] = sX0[((e0 + e) * CS_FP + f_) * CS_D + i];
-    const float wi = M::SCALED ? sInv[f_] : 1.f;
+    const float wi = sInv[f_];
     f32x4 T[2][NS];
-    cs8_step_mma<MODE, KSN, PF, true>(bd, w, rd + (size_t)sl * SLOTB, rd + (size_t)sln * SLOTB, T);
+    cs8_step_mma<KSN, PF, true>(bd, w, rd + (size_t)sl * SLOTB, rd + (size_t)sln * SLOTB, T);
 #pragma unroll
     for (int e = 0; e < 2; ++e) {
       f32x4 U = T[e][NS - 1];
 #pragma unroll
       for (int l = NS - 2; l >= 0; --l) U += T[e][l];
-      if (M::SCALED) U *= wi * inv_d[e];
+      U *= wi * inv_d[e];
       dxk[e][0] = __builtin_fmaf(x[e], U[0], dxk[e][0]);
       dxk[e][1] = __builtin_fmaf(x[e], U[1], dxk[e][1]);
       dxk[e][2] = __builtin_fmaf(x[e], U[2], dxk[e][2]);
@@ -1174,7 +1028,7 @@ __global__ __launch_bounds__(512, 1) void cin_split_dx8_k(const CsDxArgs p) {
       q += __shfl_xor(q, 32);
       sP[((e0 + e) * CS_FP + f_) * CS_D + i] = q;  // (the four lane quarters hold the same sum and store it four times)
     }
-    CS8_STEP_BARRIER(C8);
+    cs_wait_barrier<C8::VM>();
     sl = sln;
   }
   RSX_STAMP(35, st0);
@@ -1215,107 +1069,60 @@ __global__ __launch_bounds__(512, 1) void cin_split_dx8_k(const CsDxArgs p) {
   RSX_STAMP(37, st0); RSX_STAMP_MAX(49, KSN == 4);
 }
 
-template <typename K>
-int opt_in_lds(K kernel, size_t lds) {
-  if (lds > 160 * 1024) return RSX_EUNSUPPORTED;
-  if (lds > 64 * 1024 &&
-      hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-    return RSX_ELAUNCH;
-  return RSX_OK;
-}
-
-// examples per workgroup of the first form: 4 (two independent 256-thread workgroups per CU; 8 measured slower, round 5)
-
-template <int NS, int KS, int E>
+// Launchers: the k-steps of the contraction (Hp / 32 in the forward, Np / 32 in the data gradients) pick the instantiation.
 int launch_fwd(const CsFwdArgs& a, hipStream_t stream) {
-  const dim3 grid((unsigned)(a.N16 / 16), (unsigned)((a.B + E - 1) / E));
-  const size_t lds = CsLds<NS, KS, E>::TOTAL;
-  const int rc = opt_in_lds(cin_split_fwd_k<NS, KS, E>, lds);
-  if (rc != RSX_OK) return rc;
-  RSX_LAUNCH((cin_split_fwd_k<NS, KS, E>), grid, dim3(64 * E), lds, stream, a);
-  RSX_CHECK_LAUNCH();
-  return RSX_OK;
+  return dispatch_ks(a.Hp / 32, [&](auto ks) -> int {
+    constexpr int KS = decltype(ks)::value;
+    const dim3 grid((unsigned)(a.N16 / 16), (unsigned)((a.B + CS_E - 1) / CS_E));
+    const size_t lds = CsLds<KS>::TOTAL;
+    const int rc = opt_in_lds(cin_split_fwd_k<KS>, lds);
+    if (rc != RSX_OK) return rc;
+    RSX_LAUNCH(cin_split_fwd_k<KS>, grid, dim3(64 * CS_E), lds, stream, a);
+    RSX_CHECK_LAUNCH();
+    return RSX_OK;
+  });
 }
-template <int NS, int E>
-int launch_fwd_ns(const CsFwdArgs& a, hipStream_t stream) {
-  switch (a.Hp / 32) {
-    case 1: return launch_fwd<NS, 1, E>(a, stream);
-    case 2: return launch_fwd<NS, 2, E>(a, stream);
-    case 3: return launch_fwd<NS, 3, E>(a, stream);
-    default: return launch_fwd<NS, 4, E>(a, stream);
-  }
+int launch_fwd8(const CsFwdArgs& a, hipStream_t stream) {
+  return dispatch_ks(a.Hp / 32, [&](auto ks) -> int {
+    constexpr int KS = decltype(ks)::value;
+    const dim3 grid((unsigned)(a.N16 / 16), (unsigned)((a.B + 7) / 8));
+    const size_t lds = Cs8<KS, 256>::TOTAL;
+    const int rc = opt_in_lds(cin_split_fwd8_k<KS>, lds);
+    if (rc != RSX_OK) return rc;
+    RSX_LAUNCH(cin_split_fwd8_k<KS>, grid, dim3(512), lds, stream, a);
+    RSX_CHECK_LAUNCH();
+    return RSX_OK;
+  });
+}
+int launch_dx(const CsDxArgs& a, hipStream_t stream) {
+  return dispatch_ks(a.Np / 32, [&](auto ks) -> int {
+    constexpr int KSN = decltype(ks)::value;
+    const dim3 grid((unsigned)(a.H16 / 16), (unsigned)((a.B + CS_E - 1) / CS_E));
+    const size_t lds = CsLds<KSN>::TOTAL + (size_t)CS_E * CS_FP * CS_D * 4;
+    const int rc = opt_in_lds(cin_split_dx_k<KSN>, lds);
+    if (rc != RSX_OK) return rc;
+    RSX_LAUNCH(cin_split_dx_k<KSN>, grid, dim3(64 * CS_E), lds, stream, a);
+    RSX_CHECK_LAUNCH();
+    return RSX_OK;
+  });
+}
+int launch_dx8(const CsDxArgs& a, hipStream_t stream) {
+  return dispatch_ks(a.Np / 32, [&](auto ks) -> int {
+    constexpr int KSN = decltype(ks)::value;
+    const dim3 grid((unsigned)(a.H16 / 16) * (a.acc_dxk == 2 ? 2u : 1u), (unsigned)((a.B + 7) / 8));
+    const size_t lds = Cs8<KSN, CS8_DX_EXTRA>::TOTAL;
+    const int rc = opt_in_lds(cin_split_dx8_k<KSN>, lds);
+    if (rc != RSX_OK) return rc;
+    RSX_LAUNCH(cin_split_dx8_k<KSN>, grid, dim3(512), lds, stream, a);
+    RSX_CHECK_LAUNCH();
+    return RSX_OK;
+  });
 }
 
-// Which kernels run a mode: 1 = the first form (4 examples per 256-thread workgroup, two workgroups per CU), 2 = the deep-ring
-// form (8 examples per 512-thread workgroup).  Measured inside xdeepfm.py's step (profiles/r05_y_*): for the bf16 modes 1..3 the
-// first form is the faster one (0.2550 against 0.2638 ms per step at ns = 3: two independent workgroups per CU cover each
-// other's barriers and prologues), mode 4 exists in the deep-ring form only.  RSX_CIN_SPLIT_V=1|2 forces one (A/B runs).
-// Round 6 (pruned): the losing forms are no longer instantiated -- ns = 3 runs the first form with 4 examples per workgroup, mode
-// 4 the deep-ring form; ns = 1 / 2 (A/B arithmetic of round 5: plain bf16 / 2^-16-grade) are gone (RSX_EUNSUPPORTED; the plain
-// bf16-operand path is csrc/cin_bf16.hip).
-int cs_version(int ns) { return ns == CS_H2 ? 2 : 1; }
-template <int MODE, int KS>
-int launch_fwd8(const CsFwdArgs& a, hipStream_t stream) {
-  using M = SplitMode<MODE>;
-  const dim3 grid((unsigned)(a.N16 / 16), (unsigned)((a.B + 7) / 8));
-  const size_t lds = Cs8<M::NS, KS, M::SCALED ? 256 : 0>::TOTAL;
-  const int rc = opt_in_lds(cin_split_fwd8_k<MODE, KS>, lds);
-  if (rc != RSX_OK) return rc;
-  RSX_LAUNCH((cin_split_fwd8_k<MODE, KS>), grid, dim3(512), lds, stream, a);
-  RSX_CHECK_LAUNCH();
-  return RSX_OK;
-}
-template <int MODE>
-int launch_fwd8_ns(const CsFwdArgs& a, hipStream_t stream) {
-  switch (a.Hp / 32) {
-    case 1: return launch_fwd8<MODE, 1>(a, stream);
-    case 2: return launch_fwd8<MODE, 2>(a, stream);
-    case 3: return launch_fwd8<MODE, 3>(a, stream);
-    default: return launch_fwd8<MODE, 4>(a, stream);
-  }
-}
-template <int MODE, int KSN>
-int launch_dx8(const CsDxArgs& a, hipStream_t stream) {
-  using M = SplitMode<MODE>;
-  const dim3 grid((unsigned)(a.H16 / 16) * (a.acc_dxk == 2 ? 2u : 1u), (unsigned)((a.B + 7) / 8));
-  const size_t lds = Cs8<M::NS, KSN, 8 * CS_FP * CS_D * 4 + (M::SCALED ? 256 : 0)>::TOTAL;
-  const int rc = opt_in_lds(cin_split_dx8_k<MODE, KSN>, lds);
-  if (rc != RSX_OK) return rc;
-  RSX_LAUNCH((cin_split_dx8_k<MODE, KSN>), grid, dim3(512), lds, stream, a);
-  RSX_CHECK_LAUNCH();
-  return RSX_OK;
-}
-template <int MODE>
-int launch_dx8_ns(const CsDxArgs& a, hipStream_t stream) {
-  switch (a.Np / 32) {
-    case 1: return launch_dx8<MODE, 1>(a, stream);
-    case 2: return launch_dx8<MODE, 2>(a, stream);
-    case 3: return launch_dx8<MODE, 3>(a, stream);
-    default: return launch_dx8<MODE, 4>(a, stream);
-  }
-}
 inline int cs_planes(int ns) { return ns == CS_H2 ? 2 : ns; }          // 16-bit planes of the filter images
 inline int cs_dw_planes(int ns) { return ns == CS_H2 ? 3 : ns; }       // bf16 planes the weight-gradient launch multiplies
-
-template <int NS, int KSN, int E>
-int launch_dx(const CsDxArgs& a, hipStream_t stream) {
-  const dim3 grid((unsigned)(a.H16 / 16), (unsigned)((a.B + E - 1) / E));
-  const size_t lds = CsLds<NS, KSN, E>::TOTAL + (size_t)E * CS_FP * CS_D * 4;
-  const int rc = opt_in_lds(cin_split_dx_k<NS, KSN, E>, lds);
-  if (rc != RSX_OK) return rc;
-  RSX_LAUNCH((cin_split_dx_k<NS, KSN, E>), grid, dim3(64 * E), lds, stream, a);
-  RSX_CHECK_LAUNCH();
-  return RSX_OK;
-}
-template <int NS, int E>
-int launch_dx_ns(const CsDxArgs& a, hipStream_t stream) {
-  switch (a.Np / 32) {
-    case 1: return launch_dx<NS, 1, E>(a, stream);
-    case 2: return launch_dx<NS, 2, E>(a, stream);
-    case 3: return launch_dx<NS, 3, E>(a, stream);
-    default: return launch_dx<NS, 4, E>(a, stream);
-  }
-}
+// ns of a launching entry point: 1..4 are modes, 3 (three bf16 planes, the first form) and 4 (the deep-ring kernels) are built
+inline int cs_check_ns(int ns) { return ns < 1 || ns > CS_H2 ? RSX_EINVAL : (ns < 3 ? RSX_EUNSUPPORTED : RSX_OK); }
 
 size_t image_elems(int F, int H, int N) {        // one plane of both layouts
   return (size_t)F * rup(H, 16) * rup(N, 32) + (size_t)F * rup(N, 16) * rup(H, 32);
@@ -1325,7 +1132,7 @@ size_t image_elems(int F, int H, int N) {        // one plane of both layouts
 
 // ------------------------------------------------------------------------------------------------------ entry points
 extern "C" size_t rsx_cin_split_weight_elems(int F, int H, int N, int ns) {
-  if (F <= 0 || H <= 0 || N <= 0 || ns < 1 || ns > CS_H2) return 0;
+  if (F <= 0 || H <= 0 || N <= 0 || cs_check_ns(ns) == RSX_EINVAL) return 0;
   return (size_t)cs_planes(ns) * image_elems(F, H, N) + (ns == CS_H2 ? 2 * CS_FP : 0);     // (+ the fields' inverse scales, fp32)
 }
 
@@ -1346,8 +1153,8 @@ extern "C" int rsx_cin_split_prep_gather(const float* const* W_h, void* const* w
 }
 static int cs_launch_prep(const float* const* W_h, void* const* w16_h, const int32_t* H_h, const int32_t* N_h, int L, int F, int ns,
                           const rsx_gather_two_job* g, rsx_stream_t stream) {
-  if (!W_h || !w16_h || !H_h || !N_h || L <= 0 || F <= 0 || ns < 1 || ns > CS_H2) return RSX_EINVAL;
-  if (ns < 3) return RSX_EUNSUPPORTED;       // (round 6: only ns = 3 and mode 4 are built)
+  if (!W_h || !w16_h || !H_h || !N_h || L <= 0 || F <= 0) return RSX_EINVAL;
+  if (const int rc = cs_check_ns(ns); rc != RSX_OK) return rc;
   if (L > CS_MAXJ || (ns == CS_H2 && F > CS_FP)) return RSX_EUNSUPPORTED;
   const int np = cs_planes(ns);
   CsPrepArgs a{};
@@ -1377,15 +1184,15 @@ static int cs_launch_prep(const float* const* W_h, void* const* w16_h, const int
     return RSX_OK;
   }
   const unsigned blocks = (unsigned)a.n_gather + (unsigned)((tot + 255) / 256 < 4096 ? (tot + 255) / 256 : 4096);
-  RSX_LAUNCH(cin_split_prep_k<3>, dim3(blocks), dim3(256), 0, rsx_s(stream), a);
+  RSX_LAUNCH(cin_split_prep_k, dim3(blocks), dim3(256), 0, rsx_s(stream), a);
   RSX_CHECK_LAUNCH();
   return RSX_OK;
 }
 
 extern "C" int rsx_cin_split_fwd(const float* X0, const float* Xk, const void* w16, const float* c, float* out, int B, int F,
                                  int H, int N, int D, int ns, rsx_stream_t stream) {
-  if (B < 0 || F <= 0 || H <= 0 || N <= 0 || ns < 1 || ns > CS_H2) return RSX_EINVAL;
-  if (ns < 3) return RSX_EUNSUPPORTED;       // (round 6: only ns = 3 and mode 4 are built)
+  if (B < 0 || F <= 0 || H <= 0 || N <= 0) return RSX_EINVAL;
+  if (const int rc = cs_check_ns(ns); rc != RSX_OK) return rc;
   if (B == 0) return RSX_OK;
   if (!X0 || !Xk || !w16 || !c || !out) return RSX_EINVAL;
   if (D != CS_D || H > 128 || N > 128 || F > CS_FP) return RSX_EUNSUPPORTED;
@@ -1394,41 +1201,39 @@ extern "C" int rsx_cin_split_fwd(const float* X0, const float* Xk, const void* w
   const bf16_t* wt = static_cast<const bf16_t*>(w16) + (size_t)np * F * H16 * Np;
   const float* winv = reinterpret_cast<const float*>(static_cast<const bf16_t*>(w16) + (size_t)np * image_elems(F, H, N));
   const CsFwdArgs a{X0, Xk, wt, c, out, B, F, H, N, N16, Hp, winv};
-  if (ns == CS_H2) return launch_fwd8_ns<CS_H2>(a, rsx_s(stream));
-  return launch_fwd_ns<3, 4>(a, rsx_s(stream));
+  return ns == CS_H2 ? launch_fwd8(a, rsx_s(stream)) : launch_fwd(a, rsx_s(stream));
 }
 
 // ws: [ns planes of dpre fragments | B x N16 bias-gradient partials]
 extern "C" size_t rsx_cin_split_bwd_workspace_bytes(int B, int N, int ns) {
-  if (B <= 0 || N <= 0 || ns < 1 || ns > CS_H2) return 0;
+  if (B <= 0 || N <= 0 || cs_check_ns(ns) == RSX_EINVAL) return 0;
   return (size_t)cs_dw_planes(ns) * ((B + 1) / 2) * 2 * rup(N, 16) * CS_D * 2 + (size_t)B * rup(N, 16) * sizeof(float);
 }
 
 extern "C" int rsx_cin_split_bwd_dx(const float* X0, const float* Xk, const void* w16, const float* out, const float* dout,
                                     const float* gs, const float* wout, float* dXk, int acc_dxk, float* dx0_parts, void* ws,
                                     int B, int F, int H, int N, int D, int ns, rsx_stream_t stream) {
-  if (B < 0 || F <= 0 || H <= 0 || N <= 0 || ns < 1 || ns > CS_H2) return RSX_EINVAL;
-  if (ns < 3) return RSX_EUNSUPPORTED;       // (round 6: only ns = 3 and mode 4 are built)
+  if (B < 0 || F <= 0 || H <= 0 || N <= 0) return RSX_EINVAL;
+  if (const int rc = cs_check_ns(ns); rc != RSX_OK) return rc;
   if (B == 0) return RSX_OK;
   if (!X0 || !Xk || !w16 || !out || !dXk || !dx0_parts || !ws) return RSX_EINVAL;
   if ((!dout && !gs) || (gs && !wout)) return RSX_EINVAL;
   if (D != CS_D || H > 128 || N > 128 || F > CS_FP) return RSX_EUNSUPPORTED;
   if (acc_dxk < 0 || acc_dxk > 2) return RSX_EINVAL;
   // acc_dxk = 2: the fields split over two workgroups per tile, the second half's dXk in dx0_parts tile ceil(H/16) (H == F, deep-ring kernels)
-  if (acc_dxk == 2 && (H != F || cs_version(ns) != 2)) return RSX_EUNSUPPORTED;
+  if (acc_dxk == 2 && (H != F || ns != CS_H2)) return RSX_EUNSUPPORTED;
   const int H16 = rup(H, 16), N16 = rup(N, 16), Np = rup(N, 32);
   const int dwp = cs_dw_planes(ns);
   float* dc_part = reinterpret_cast<float*>(static_cast<char*>(ws) + (size_t)dwp * ((B + 1) / 2) * 2 * N16 * CS_D * 2);
   const float* winv = reinterpret_cast<const float*>(static_cast<const bf16_t*>(w16) + (size_t)cs_planes(ns) * image_elems(F, H, N));
   const CsDxArgs a{X0, Xk, static_cast<const bf16_t*>(w16), out, dout, gs, wout, dXk, dx0_parts, static_cast<bf16_t*>(ws),
                    dc_part, acc_dxk, B, F, H, N, H16, N16, Np, winv, dwp};
-  if (ns == CS_H2) return launch_dx8_ns<CS_H2>(a, rsx_s(stream));
-  return launch_dx_ns<3, 4>(a, rsx_s(stream));
+  return ns == CS_H2 ? launch_dx8(a, rsx_s(stream)) : launch_dx(a, rsx_s(stream));
 }
 
 // ------------------------------------------------------------------------------------------------ backward: dW, dc
 // dW_f[h, n] = sum over (b, d) of Z[b, f, h, d] * dpre[b, n, d], Z = X0 * Xk rounded once to fp32 (as cin.hip forms it) and
-// split into NS planes on the fly; dpre's planes come from the data-gradient launch (fragments of example pairs).
+// split into three planes on the fly; dpre's planes come from the data-gradient launch (fragments of example pairs).
 // One launch for all layers.  Workgroup = 8 waves that split the k-steps (example pairs) of ONE tile = FT fields x 16 h x 64
 // n, partial tiles added in fixed order through LDS; FT is a per-job choice (so that the tiles of all layers together fill
 // the CUs in one round: 4 x 40 + ... see cs_launch_dw).  The X0 slab of the tile's fields sits in LDS (cin_bf16.hip: X0L).
@@ -1437,7 +1242,7 @@ namespace {
 constexpr int CS_NT = 4;
 struct CsDwJob {
   const float* Xk;        // [B, H, 16]
-  const bf16_t* dpre16;   // NS planes of fragments, see CsDxArgs
+  const bf16_t* dpre16;   // three planes of fragments, see CsDxArgs
   const float* dc_part;   // [B][N16]
   float* dW;              // [F*H, N]
   float* dc;              // [N]
@@ -1463,9 +1268,9 @@ struct CsDwArgs {
 
 // (A tile of 6 fields x 3 n tiles -- 42 % fewer dpre bytes per MFMA -- measured SLOWER: xdeepfm.py 0.265 against 0.238 ms; the
 // launch is bound by forming and splitting the Z operand on the VALU, which grows with the fields per tile.)
-template <int NS, int FT, bool X0L>
+template <int FT, bool X0L>
 __device__ __forceinline__ void cs_dw_tile(const CsDwArgs& p, const CsDwJob& jb, int local, float4* dw_lds) {
-  constexpr int NT = CS_NT;
+  constexpr int NS = 3, NT = CS_NT;
   float (*red)[FT * NT][256] = reinterpret_cast<float (*)[FT * NT][256]>(dw_lds);
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
   const int bx = local % jb.gx, by = (local / jb.gx) % jb.HT, bz = local / (jb.gx * jb.HT);
@@ -1536,7 +1341,7 @@ __device__ __forceinline__ void cs_dw_tile(const CsDwArgs& p, const CsDwJob& jb,
       bf16x8 a[NS][1];
       {
         bf16x8 t[NS];
-        split8<NS>(f4_mul(x0[0], k0), f4_mul(x0[1], k1), t);
+        split8(f4_mul(x0[0], k0), f4_mul(x0[1], k1), t);
 #pragma unroll
         for (int s = 0; s < NS; ++s) a[s][0] = t[s];
       }
@@ -1545,7 +1350,7 @@ __device__ __forceinline__ void cs_dw_tile(const CsDwArgs& p, const CsDwJob& jb,
         bf16x8 b[NS][1];
 #pragma unroll
         for (int s = 0; s < NS; ++s) b[s][0] = __builtin_bit_cast(bf16x8, L.dp[s][nt]);
-        acc[ft][nt] = split_mma<NS, 1>(a, b, acc[ft][nt]);
+        acc[ft][nt] = split_mma<1>(a, b, acc[ft][nt]);
         if (ft == FT - 1) {
           const int t = ntg + nt < NT16 ? ntg + nt : NT16 - 1;
 #pragma unroll
@@ -1613,7 +1418,6 @@ __device__ __forceinline__ void cs_dw_tile(const CsDwArgs& p, const CsDwJob& jb,
 }
 
 // grid = njobs (the bias gradients: per-example partials added in order) + the jobs' tiles, block = 512
-template <int NS>
 __global__ __launch_bounds__(512) void cin_split_dw_k(const CsDwArgs p) {
   extern __shared__ float4 dw_lds[];
   const int tid = threadIdx.x;
@@ -1654,10 +1458,10 @@ __global__ __launch_bounds__(512) void cin_split_dw_k(const CsDwArgs p) {
   const CsDwJob& jb = p.job[ji];
   const int local = tile - (ji ? p.job[ji - 1].tile_end : 0);
   if (p.x0l) {
-    if (jb.ft == 4) cs_dw_tile<NS, 4, true>(p, jb, local, dw_lds);
-    else cs_dw_tile<NS, 3, true>(p, jb, local, dw_lds);
+    if (jb.ft == 4) cs_dw_tile<4, true>(p, jb, local, dw_lds);
+    else cs_dw_tile<3, true>(p, jb, local, dw_lds);
   } else {
-    cs_dw_tile<NS, 3, false>(p, jb, local, dw_lds);
+    cs_dw_tile<3, false>(p, jb, local, dw_lds);
   }
 }
 
@@ -1683,8 +1487,8 @@ extern "C" int rsx_cin_split_bwd_dw_dx0(const float* X0, const rsx_cin_dw_job* j
 static int cs_launch_dw(const float* X0, const rsx_cin_dw_job* jobs_h, int njobs, int B, int F, int D, int ns,
                         const float* const* parts_h, const int32_t* tiles_h, int nparts, float* dX0, int acc_dx0,
                         rsx_stream_t stream) {
-  if (!X0 || !jobs_h || njobs <= 0 || B < 0 || F <= 0 || ns < 1 || ns > CS_H2) return RSX_EINVAL;
-  if (ns < 3) return RSX_EUNSUPPORTED;       // (round 6: only ns = 3 and mode 4 are built)
+  if (!X0 || !jobs_h || njobs <= 0 || B < 0 || F <= 0) return RSX_EINVAL;
+  if (const int rc = cs_check_ns(ns); rc != RSX_OK) return rc;
   if (njobs > CS_MAXJ || D != CS_D || F > CS_FP) return RSX_EUNSUPPORTED;
   if (B == 0) return RSX_OK;
   ns = cs_dw_planes(ns);                            // (mode 4: the data-gradient launch left three bf16 planes of dpre)
@@ -1744,14 +1548,9 @@ static int cs_launch_dw(const float* X0, const rsx_cin_dw_job* jobs_h, int njobs
     w.red_blocks = (unsigned long long)rb < need ? rb : (int)need;
   }
   const unsigned grid = (unsigned)tiles + (unsigned)njobs + (unsigned)w.red_blocks;
-#define RSX_CS_DW(NS_)                                                       \
-  {                                                                          \
-    const int rc = opt_in_lds(cin_split_dw_k<NS_>, lds);                     \
-    if (rc != RSX_OK) return rc;                                             \
-    RSX_LAUNCH(cin_split_dw_k<NS_>, dim3(grid), dim3(512), lds, rsx_s(stream), w); \
-  }
-  RSX_CS_DW(3);
-#undef RSX_CS_DW
+  const int rc = opt_in_lds(cin_split_dw_k, lds);
+  if (rc != RSX_OK) return rc;
+  RSX_LAUNCH(cin_split_dw_k, dim3(grid), dim3(512), lds, rsx_s(stream), w);
   RSX_CHECK_LAUNCH();
   return RSX_OK;
 }

@@ -18,7 +18,6 @@
 #include "split_device.h"
 RSX_STAMP_DECL
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ f32x4 att_mfma(float a, float b, f32x4 c) {
   return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
 }
@@ -259,8 +258,8 @@ __global__ __launch_bounds__(64 * FSP_WAVES) void din_attn_fwd_split_k(const Att
   extern __shared__ __attribute__((aligned(16))) float lds[];
   constexpr int K = 16 * KB, KS0 = 2 * KB, NT1 = 5, NT2 = 3, KS1 = 3;
   constexpr int FT = 64 * FSP_WAVES;
-  sp_bf16x8* sW0 = reinterpret_cast<sp_bf16x8*>(lds);              // [3][KS0][NT1][64]
-  sp_bf16x8* sW1 = sW0 + 3 * KS0 * NT1 * 64;                       // [3][KS1][NT2][64]
+  bf16x8* sW0 = reinterpret_cast<bf16x8*>(lds);              // [3][KS0][NT1][64]
+  bf16x8* sW1 = sW0 + 3 * KS0 * NT1 * 64;                       // [3][KS1][NT2][64]
   float* sb0 = reinterpret_cast<float*>(sW1 + 3 * KS1 * NT2 * 64); // [80]
   float* sb1 = sb0 + 16 * NT1;                                     // [48]
   float* sw2 = sb1 + 16 * NT2;                                     // [48]
@@ -277,8 +276,8 @@ __global__ __launch_bounds__(64 * FSP_WAVES) void din_attn_fwd_split_k(const Att
 #pragma unroll
       for (int j = 0; j < 8; ++j) v[j] = 0.f;
     }
-    sp_bf16x8 pl[3];
-    sp_split8(v, pl);
+    bf16x8 pl[3];
+    split8(make_float4(v[0], v[1], v[2], v[3]), make_float4(v[4], v[5], v[6], v[7]), pl);
 #pragma unroll
     for (int s = 0; s < 3; ++s) sW0[((s * KS0 + ks) * NT1 + nt) * 64 + l] = pl[s];
   }
@@ -293,8 +292,8 @@ __global__ __launch_bounds__(64 * FSP_WAVES) void din_attn_fwd_split_k(const Att
       const float x = p.W1[(size_t)(k < p.N1 ? k : 0) * p.N2 + (n < p.N2 ? n : 0)];
       v[j] = ok ? x : 0.f;
     }
-    sp_bf16x8 pl[3];
-    sp_split8(v, pl);
+    bf16x8 pl[3];
+    split8(make_float4(v[0], v[1], v[2], v[3]), make_float4(v[4], v[5], v[6], v[7]), pl);
 #pragma unroll
     for (int s = 0; s < 3; ++s) sW1[((s * KS1 + ks) * NT2 + nt) * 64 + l] = pl[s];
   }
@@ -309,7 +308,7 @@ __global__ __launch_bounds__(64 * FSP_WAVES) void din_attn_fwd_split_k(const Att
   __syncthreads();
   const int Mv = p.count ? p.count[0] : p.M;
   const int nblk = (Mv + 16 * FSP_WAVES - 1) / (16 * FSP_WAVES);
-  const sp_f32x4 zf = {0.f, 0.f, 0.f, 0.f};
+  const f32x4 zf = {0.f, 0.f, 0.f, 0.f};
   for (int blk = blockIdx.x; blk < nblk; blk += gridDim.x) {      // persistent: the weights are staged once per workgroup
     const int jr = (blk * FSP_WAVES + wv) * 16 + i;               // position in the (possibly compacted) row list
     const bool mok = jr < Mv;
@@ -323,7 +322,7 @@ __global__ __launch_bounds__(64 * FSP_WAVES) void din_attn_fwd_split_k(const Att
     const float hv[8] = {h0.x, h0.y, h0.z, h0.w, h1.x, h1.y, h1.z, h1.w};
     const float qv[8] = {q0.x, q0.y, q0.z, q0.w, q1.x, q1.y, q1.z, q1.w};
     // ---- layer 0: z1^T = W0^T . [h, q, h*q, h-q]^T ------------------------------------------------------------
-    sp_f32x4 acc1[NT1];
+    f32x4 acc1[NT1];
 #pragma unroll
     for (int nt = 0; nt < NT1; ++nt) acc1[nt] = zf;
 #pragma unroll
@@ -335,14 +334,14 @@ __global__ __launch_bounds__(64 * FSP_WAVES) void din_attn_fwd_split_k(const Att
         const float pr = hv[j] * qv[j], df = hv[j] - qv[j];
         a[j] = seg == 0 ? hv[j] : (seg == 1 ? qv[j] : (seg == 2 ? pr : df));
       }
-      sp_bf16x8 ap[3];
-      sp_split8(a, ap);
+      bf16x8 ap[3];
+      split8(make_float4(a[0], a[1], a[2], a[3]), make_float4(a[4], a[5], a[6], a[7]), ap);
 #pragma unroll
       for (int nt = 0; nt < NT1; ++nt) {
-        sp_bf16x8 wp[3];
+        bf16x8 wp[3];
 #pragma unroll
         for (int s = 0; s < 3; ++s) wp[s] = sW0[((s * KS0 + ks) * NT1 + nt) * 64 + lane];
-        acc1[nt] = sp_mma3(wp, ap, acc1[nt]);
+        acc1[nt] = split_mma(wp, ap, acc1[nt]);
         // (without the fence the scheduler hoists the fragment reads of ALL 20 (k-step, tile) pairs -- 240 registers -- to the top)
         if ((nt & 1) == 1) __builtin_amdgcn_sched_barrier(0);
       }
@@ -364,21 +363,20 @@ __global__ __launch_bounds__(64 * FSP_WAVES) void din_attn_fwd_split_k(const Att
 #pragma unroll
     for (int r = 0; r < 4; ++r) a1d[NT1][r] = 0.f;                // (column tile 5: the padding half of layer 1's last k-step)
     // ---- layer 1: z2^T = W1^T . a1d^T ---------------------------------------------------------------------------
-    sp_f32x4 acc2[NT2];
+    f32x4 acc2[NT2];
 #pragma unroll
     for (int nt = 0; nt < NT2; ++nt) acc2[nt] = zf;
 #pragma unroll
     for (int ks = 0; ks < KS1; ++ks) {
-      const float a[8] = {a1d[2 * ks][0], a1d[2 * ks][1], a1d[2 * ks][2], a1d[2 * ks][3],
-                          a1d[2 * ks + 1][0], a1d[2 * ks + 1][1], a1d[2 * ks + 1][2], a1d[2 * ks + 1][3]};
-      sp_bf16x8 ap[3];
-      sp_split8(a, ap);
+      bf16x8 ap[3];
+      split8(make_float4(a1d[2 * ks][0], a1d[2 * ks][1], a1d[2 * ks][2], a1d[2 * ks][3]),
+             make_float4(a1d[2 * ks + 1][0], a1d[2 * ks + 1][1], a1d[2 * ks + 1][2], a1d[2 * ks + 1][3]), ap);
 #pragma unroll
       for (int nt = 0; nt < NT2; ++nt) {
-        sp_bf16x8 wp[3];
+        bf16x8 wp[3];
 #pragma unroll
         for (int s = 0; s < 3; ++s) wp[s] = sW1[((s * KS1 + ks) * NT2 + nt) * 64 + lane];
-        acc2[nt] = sp_mma3(wp, ap, acc2[nt]);
+        acc2[nt] = split_mma(wp, ap, acc2[nt]);
       }
       __builtin_amdgcn_sched_barrier(0);
     }

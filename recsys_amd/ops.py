@@ -1468,70 +1468,197 @@ class CinLayerFn(torch.autograd.Function):
         return dX0, dXk, dW, dc, None
 
 
+class _CinF32:
+    """CinNet's fp32 MFMA path (csrc/cin.hip): one forward and ONE backward launch per layer, each may carry a sweep slice."""
+    carries_sweeps = True
+
+    def __init__(self, net, capacity, dev):
+        self.backward_launches = net.L
+        hs = [net.F] + net.sizes[:-1]
+        self.dpre = torch.empty(max(int(lib().rsx_cin_bwd_workspace_floats(capacity, net.F, h, n)) for h, n in zip(hs, net.sizes)), device=dev)
+
+    def prep(self, net, P, gather_job):
+        assert gather_job is None, "CinNet.forward: a lookup can only ride in the split-operand prep launch (gather_ride_ok)"
+
+    def layer_fwd(self, net, k, X0, Xk, H, P, B, sw):
+        check(lib().rsx_cin_layer_fwd(_ptr(X0), _ptr(Xk), _ptr(P[f"cin.W{k}"]), _ptr(P[f"cin.c{k}"]), _ptr(net.outs[k]), B,
+                                      net.F, H, net.sizes[k], net.D, sw, _stream()), "rsx_cin_layer_fwd")
+
+    def begin_bwd(self, net, sweeps):
+        pass
+
+    def layer_bwd(self, net, k, X0, Xk, H, P, B, dout, wout_k, dxk, acc_dxk, dX0, acc_dx0, sw):
+        check(lib().rsx_cin_layer_bwd(_ptr(X0), _ptr(Xk), _ptr(P[f"cin.W{k}"]), _ptr(net.outs[k]), dout, _ptr(net.gs), wout_k,
+                                      _ptr(dxk), acc_dxk, _ptr(dX0), acc_dx0, _ptr(P[f"cin.W{k}"].grad), _ptr(P[f"cin.c{k}"].grad),
+                                      _ptr(self.dpre), B, net.F, H, net.sizes[k], net.D, sw, _stream()), "rsx_cin_layer_bwd")
+
+    def end_bwd(self, net, X0, P, B, dX0, sweeps):
+        pass
+
+
+class _Cin16:
+    """What CinNet's two 16-bit-operand paths share: per-layer operand images of the filters (one prep launch per forward fills
+    them; the backward of the same step reuses them, the filters do not change in between), one backward workspace PER LAYER
+    (the L data-gradient launches fill them, ONE launch then computes every layer's weight gradient: L + 1 backward launches),
+    and dX0 as one partial per 16-wide tile of h that a closing reduce adds, last layer first."""
+
+    def __init__(self, net, dev, weight_elems, ws_bytes):
+        self.backward_launches = net.L + 1
+        self.hs = [net.F] + net.sizes[:-1]
+        self.w16 = [torch.empty(int(weight_elems(h, n)), dtype=torch.int16, device=dev) for h, n in zip(self.hs, net.sizes)]
+        self.ws16 = [torch.empty(int(ws_bytes(n)), dtype=torch.uint8, device=dev) for n in net.sizes]
+        self._w16_h = (C.c_void_p * net.L)(*[w.data_ptr() for w in self.w16])
+        self._H_h = (C.c_int32 * net.L)(*self.hs)
+
+    def _alloc_parts(self, net, capacity, dev, extra_tiles0=0):
+        """extra_tiles0: further [capacity, F, D] partials of layer 0"""
+        extra = [extra_tiles0 if k == 0 else 0 for k in range(net.L)]
+        self.dx0_parts = [torch.empty(int(lib().rsx_cin_bf16_dx0_parts_floats(capacity, net.F, h)) + x * capacity * net.F * net.D,
+                                      device=dev) for h, x in zip(self.hs, extra)]
+        self._tiles_h = (C.c_int32 * net.L)(*[(h + 15) // 16 + x for h, x in zip(self.hs, extra)][::-1])
+
+    def _W_h(self, net, P):
+        return (C.c_void_p * net.L)(*[P[f"cin.W{k}"].data_ptr() for k in range(net.L)])
+
+    def _parts_h(self, net):
+        return (C.c_void_p * net.L)(*[p.data_ptr() for p in self.dx0_parts[::-1]])
+
+    def _dw_jobs(self, net, X0, P, dc_rows):
+        jobs = (_lib.CinDwJob * net.L)()
+        for k in range(net.L):
+            Xk, H = (X0, net.F) if k == 0 else (net.outs[k - 1], net.sizes[k - 1])
+            jobs[k] = _lib.CinDwJob(Xk.data_ptr(), self.ws16[k].data_ptr(), P[f"cin.W{k}"].grad.data_ptr(),
+                                    P[f"cin.c{k}"].grad.data_ptr(), H, net.sizes[k], dc_rows)
+        return jobs
+
+
+class _CinBf16(_Cin16):
+    """bf16 operands, fp32 accumulation (csrc/cin_bf16.hip: Xk / W / dpre rounded to bf16 -- NOT the parity path).  Data
+    gradients with two examples per workgroup, or eight (csrc/cin_bf16_wide.hip, RSX_CIN_WIDE=0: off) when no sweep slice rides
+    in them; every launch but the wide ones may carry a slice."""
+    carries_sweeps = True
+
+    def __init__(self, net, capacity, dev):
+        super().__init__(net, dev, lambda h, n: lib().rsx_cin_bf16_weight_elems(net.F, h, n),
+                         lambda n: lib().rsx_cin_bf16_bwd_workspace_bytes(capacity, n))
+        self.wide = net.F <= 40 and _lib.form("cin_wide") != "0"
+        if self.wide:
+            self._alloc_parts(net, capacity, dev)
+
+    def prep(self, net, P, gather_job):
+        assert gather_job is None, "CinNet.forward: a lookup can only ride in the split-operand prep launch (gather_ride_ok)"
+        check(lib().rsx_cin_prep_bf16_multi(self._W_h(net, P), self._w16_h, self._H_h, net._sizes_h, net.L, net.F, _stream()),
+              "rsx_cin_prep_bf16_multi")
+
+    def layer_fwd(self, net, k, X0, Xk, H, P, B, sw):
+        check(lib().rsx_cin_layer_fwd_bf16(_ptr(X0), _ptr(Xk), _ptr(self.w16[k]), _ptr(P[f"cin.c{k}"]), _ptr(net.outs[k]),
+                                           B, net.F, H, net.sizes[k], net.D, sw, _stream()), "rsx_cin_layer_fwd_bf16")
+
+    def begin_bwd(self, net, sweeps):
+        self._wide_now = self.wide and (sweeps is None or all(x is None for x in sweeps[:net.L]))
+
+    def layer_bwd(self, net, k, X0, Xk, H, P, B, dout, wout_k, dxk, acc_dxk, dX0, acc_dx0, sw):
+        if self._wide_now:
+            # (layer 0: dXk IS dX0 and nothing has been written there yet -- the other layers' shares arrive with the reduce)
+            check(lib().rsx_cin_layer_bwd_dx_bf16_parts(_ptr(X0), _ptr(Xk), _ptr(self.w16[k]), _ptr(net.outs[k]), dout, _ptr(net.gs),
+                                                        wout_k, _ptr(dxk), 0, _ptr(self.dx0_parts[k]), _ptr(self.ws16[k]), B, net.F,
+                                                        H, net.sizes[k], net.D, _stream()), "rsx_cin_layer_bwd_dx_bf16_parts")
+            return
+        check(lib().rsx_cin_layer_bwd_dx_bf16(_ptr(X0), _ptr(Xk), _ptr(self.w16[k]), _ptr(net.outs[k]), dout, _ptr(net.gs), wout_k,
+                                              _ptr(dxk), acc_dxk, _ptr(dX0), acc_dx0, _ptr(self.ws16[k]), B, net.F, H, net.sizes[k],
+                                              net.D, sw, _stream()), "rsx_cin_layer_bwd_dx_bf16")
+
+    def end_bwd(self, net, X0, P, B, dX0, sweeps):
+        if self._wide_now:      # dX0 = layer 0's dXk (already there) + every layer's tile partials
+            check(lib().rsx_cin_dx0_reduce(self._parts_h(net), self._tiles_h, net.L, _ptr(dX0), 1, B, net.F, net.D, _stream()),
+                  "rsx_cin_dx0_reduce")
+        jobs = self._dw_jobs(net, X0, P, B if self._wide_now else 0)
+        sw = None if sweeps is None or sweeps[net.L] is None else C.byref(sweeps[net.L])
+        check(lib().rsx_cin_bwd_dw_bf16(_ptr(X0), jobs, net.L, B, net.F, net.D, sw, _stream()), "rsx_cin_bwd_dw_bf16")
+
+
+class _CinSplit(_Cin16):
+    """The contraction on the 16-bit matrix cores at fp32 grade (csrc/cin_split.hip).  ns = 3: every operand kept as three bf16
+    planes (every product exact to 2^-23: the parity path on those cores); ns = 4: forward / data gradients with TWO scaled
+    fp16 planes per operand (three MFMAs per k-step instead of six, products to 2^-22), weight gradients on three bf16
+    planes.  Its launches carry no sweep slices; the caller's lookup may ride in the prep launch."""
+    carries_sweeps = False
+
+    def __init__(self, net, capacity, dev, ns):
+        self.ns = ns
+        super().__init__(net, dev, lambda h, n: lib().rsx_cin_split_weight_elems(net.F, h, n, ns),
+                         lambda n: lib().rsx_cin_split_bwd_workspace_bytes(capacity, n, ns))
+        # layer 0 in mode 4 (dXk IS dX0; a few tiles of h only): its data-gradient launch splits the FIELDS over two workgroups
+        # per tile when both fit the CUs in one round; the second half's dXk is one more tile partial (RSX_CIN_DX_FSPLIT=0: off)
+        ht0 = (self.hs[0] + 15) // 16
+        self.fsplit0 = (ns == 4 and _lib.form("cin_dx_fsplit") != "0" and 2 * ht0 * ((capacity + 7) // 8) <= 256)
+        self._alloc_parts(net, capacity, dev, extra_tiles0=1 if self.fsplit0 else 0)
+
+    def prep(self, net, P, gather_job):     # the split operand images of all layers' filters: one launch (+ the caller's lookup as its rider)
+        if gather_job is not None:
+            check(lib().rsx_cin_split_prep_gather(self._W_h(net, P), self._w16_h, self._H_h, net._sizes_h, net.L, net.F, self.ns,
+                                                  C.byref(gather_job), _stream()), "rsx_cin_split_prep_gather")
+        else:
+            check(lib().rsx_cin_split_prep(self._W_h(net, P), self._w16_h, self._H_h, net._sizes_h, net.L, net.F, self.ns, _stream()),
+                  "rsx_cin_split_prep")
+
+    def layer_fwd(self, net, k, X0, Xk, H, P, B, sw):
+        assert sw is None, "the split-operand CIN launches carry no sweep slices"
+        check(lib().rsx_cin_split_fwd(_ptr(X0), _ptr(Xk), _ptr(self.w16[k]), _ptr(P[f"cin.c{k}"]), _ptr(net.outs[k]),
+                                      B, net.F, H, net.sizes[k], net.D, self.ns, _stream()), "rsx_cin_split_fwd")
+
+    def begin_bwd(self, net, sweeps):
+        assert sweeps is None or all(x is None for x in sweeps), "the split-operand CIN launches carry no sweep slices"
+
+    def layer_bwd(self, net, k, X0, Xk, H, P, B, dout, wout_k, dxk, acc_dxk, dX0, acc_dx0, sw):
+        check(lib().rsx_cin_split_bwd_dx(_ptr(X0), _ptr(Xk), _ptr(self.w16[k]), _ptr(net.outs[k]), dout, _ptr(net.gs), wout_k,
+                                         _ptr(dxk), 2 if (k == 0 and self.fsplit0) else 0, _ptr(self.dx0_parts[k]), _ptr(self.ws16[k]),
+                                         B, net.F, H, net.sizes[k], net.D, self.ns, _stream()), "rsx_cin_split_bwd_dx")
+
+    def end_bwd(self, net, X0, P, B, dX0, sweeps):
+        parts_h = self._parts_h(net)
+        jobs = self._dw_jobs(net, X0, P, B)
+        if _lib.form("cin_dx0_ride") != "0":   # the dX0 reduce rides in the weight-gradient launch (the same sums in the same order)
+            check(lib().rsx_cin_split_bwd_dw_dx0(_ptr(X0), jobs, net.L, B, net.F, net.D, self.ns, parts_h, self._tiles_h, net.L,
+                                                 _ptr(dX0), 1, _stream()), "rsx_cin_split_bwd_dw_dx0")
+            return
+        check(lib().rsx_cin_dx0_reduce(parts_h, self._tiles_h, net.L, _ptr(dX0), 1, B, net.F, net.D, _stream()), "rsx_cin_dx0_reduce")   # (0: A/B)
+        check(lib().rsx_cin_split_bwd_dw(_ptr(X0), jobs, net.L, B, net.F, net.D, self.ns, _stream()), "rsx_cin_split_bwd_dw")
+
+
 class CinNet:
-    """'cin_net' of the training step (xdeepfm/xdeepfm.py:135-182) without autograd or glue kernels: L rsx_cin_layer_fwd +
-    rsx_cin_out_fwd forward; rsx_cin_out_bwd + L rsx_cin_layer_bwd backward.  The concat / reduce_sum / dense head and the
+    """'cin_net' of the training step (xdeepfm/xdeepfm.py:135-182) without autograd or glue kernels: L layer launches +
+    rsx_cin_out_fwd forward; rsx_cin_out_bwd + the layers' backward launches.  The concat / reduce_sum / dense head and the
     broadcast of its gradient back into every layer map happen inside those kernels; the gradients of X^0 from all layers
-    (and from its second role as X^k of layer 0) accumulate in one buffer; weight gradients land in the dense arena."""
+    (and from its second role as X^k of layer 0) accumulate in one buffer; weight gradients land in the dense arena.
+    What runs a layer is one of three paths (_CinF32, _CinBf16, _CinSplit): this class keeps what they share -- the maps, the
+    head, and the layer loops' bookkeeping.  (A path is handed the net in every call and keeps no reference to it: net.path ->
+    net would be a cycle, and the net's device buffers would wait for the cycle collector instead of dying with the net.)"""
 
     def __init__(self, F, D, sizes, capacity, device="cuda", bf16=False, split=0):
         dev = _require_cuda(device)
         self.F, self.D, self.sizes, self.L = F, D, [int(n) for n in sizes], len(sizes)
-        # split = 3: the contraction on the bf16 matrix cores with every operand kept as three bf16 planes
-        # (csrc/cin_split.hip: every product exact to 2^-23 -- fp32-grade, the parity path on those cores);
-        # split = 4: forward / data gradients with TWO scaled fp16 planes per operand (three MFMAs per k-step instead of six,
-        # products to 2^-22), weight gradients on three bf16 planes
         self.split = int(split or 0)
         if self.split and not (3 <= self.split <= 4 and F <= 40 and D == 16 and max(sizes) <= 128 and self.L <= 4):
             raise _lib.RsxError("CinNet: split operands need split in (3, 4), F <= 40, D = 16, layers <= 128 wide, <= 4 layers")
-        if self.split:
-            bf16 = False
-            hs16 = [F] + self.sizes[:-1]
-            ns = self.split
-            self.w16 = [torch.empty(int(lib().rsx_cin_split_weight_elems(F, h, n, ns)), dtype=torch.int16, device=dev)
-                        for h, n in zip(hs16, self.sizes)]
-            self.ws16 = [torch.empty(int(lib().rsx_cin_split_bwd_workspace_bytes(capacity, n, ns)), dtype=torch.uint8, device=dev)
-                         for n in self.sizes]
-            self._w16_h = (C.c_void_p * self.L)(*[w.data_ptr() for w in self.w16])
-            self._H_h = (C.c_int32 * self.L)(*hs16)
-            # layer 0 in mode 4 (dXk IS dX0; a few tiles of h only): its data-gradient launch splits the FIELDS over two workgroups
-            # per tile when both fit the CUs in one round; the second half's dXk is one more tile partial (RSX_CIN_DX_FSPLIT=0: off)
-            ht0 = (hs16[0] + 15) // 16
-            self.fsplit0 = (ns == 4 and _lib.form("cin_dx_fsplit") != "0" and
-                            2 * ht0 * ((capacity + 7) // 8) <= 256)
-            extra = [capacity * F * D if (k == 0 and self.fsplit0) else 0 for k in range(self.L)]
-            self.dx0_parts = [torch.empty(int(lib().rsx_cin_bf16_dx0_parts_floats(capacity, F, h)) + x, device=dev)
-                              for h, x in zip(hs16, extra)]
-            self._tiles_h = (C.c_int32 * self.L)(*[(h + 15) // 16 + (1 if (k == 0 and self.fsplit0) else 0)
-                                                   for k, h in enumerate(hs16)][::-1])
-        # bf16=True: the contraction runs on the bf16 MFMA path (csrc/cin_bf16.hip: Xk / W / dpre rounded to bf16, fp32
-        # accumulation) -- NOT the parity path; fp32 (False) is the default everywhere
-        self.bf16 = bool(bf16)
-        if self.bf16:
-            hs16 = [F] + self.sizes[:-1]
-            self.w16 = [torch.empty(int(lib().rsx_cin_bf16_weight_elems(F, h, n)), dtype=torch.int16, device=dev)
-                        for h, n in zip(hs16, self.sizes)]
-            # one backward workspace PER LAYER: the dX launches fill them layer by layer, ONE launch then computes every
-            # layer's weight gradient from them
-            self.ws16 = [torch.empty(int(lib().rsx_cin_bf16_bwd_workspace_bytes(capacity, n)), dtype=torch.uint8, device=dev)
-                         for n in self.sizes]
-            self._w16_h = (C.c_void_p * self.L)(*[w.data_ptr() for w in self.w16])
-            self._H_h = (C.c_int32 * self.L)(*hs16)
-            # eight examples per workgroup (csrc/cin_bf16_wide.hip): the data-gradient launches leave dX0 as one partial per
-            # 16-wide tile of h, ONE reduce launch adds the tiles of all layers
-            self.wide = F <= 40 and _lib.form("cin_wide") != "0"
-            if self.wide:
-                self.dx0_parts = [torch.empty(int(lib().rsx_cin_bf16_dx0_parts_floats(capacity, F, h)), device=dev) for h in hs16]
-                self._tiles_h = (C.c_int32 * self.L)(*[(h + 15) // 16 for h in hs16][::-1])
+        self.bf16 = bool(bf16) and not self.split       # fp32 (neither) is the default everywhere
+        self._sizes_h = (C.c_int32 * self.L)(*self.sizes)
         self.outs = [torch.empty(capacity, n, D, device=dev) for n in self.sizes]
         self.dmap = [torch.empty(capacity, n, D, device=dev) for n in self.sizes[:-1]]   # gradient wrt map k (from layer k+1)
-        hs = [F] + self.sizes[:-1]
-        self.dpre = torch.empty(max(int(lib().rsx_cin_bwd_workspace_floats(capacity, F, h, n)) for h, n in zip(hs, self.sizes)), device=dev)
         self.dX0 = torch.empty(capacity, F, D, device=dev)
         self.y, self.gs = torch.empty(capacity, device=dev), torch.empty(capacity, device=dev)
-        self._sizes_h = (C.c_int32 * self.L)(*self.sizes)
         self._outs_h = (C.c_void_p * self.L)(*[o.data_ptr() for o in self.outs])
         self.offs = [sum(self.sizes[:k]) for k in range(self.L)]
+        self.path = (_CinSplit(self, capacity, dev, self.split) if self.split else
+                     _CinBf16(self, capacity, dev) if self.bf16 else _CinF32(self, capacity, dev))
+        # what a caller that schedules sweep slices needs to know: the number of backward launches after the head's (L, or the L
+        # data-gradient launches + ONE with every layer's weight gradient), and whether the layer launches carry slices at all
+        self.backward_launches, self.carries_sweeps = self.path.backward_launches, self.path.carries_sweeps
+
+    def backward_sweeps(self, in_launch_order):
+        """Slices for the backward launches, given in LAUNCH order (layer L-1 .. 0, then the weight-gradient launch if there is
+        one) -> the order backward() takes them in (layer 0 .. L-1, then that launch)."""
+        return in_launch_order[:self.L][::-1] + in_launch_order[self.L:]
 
     def gather_ride_ok(self):
         """xdeepfm.py's lookup (rsx_gather_two_fwd) can ride in this net's filter-preparation launch (RSX_CIN_GATHER_RIDE=0: two
@@ -1543,35 +1670,10 @@ class CinNet:
         optimizer sweep carried by layer k's forward launch."""
         B = X0.shape[0]
         Xk, H = X0, self.F
-        if self.split:    # the split operand images of all layers' filters: one launch (+ the caller's lookup as its rider)
-            W_h = (C.c_void_p * self.L)(*[P[f"cin.W{k}"].data_ptr() for k in range(self.L)])
-            if gather_job is not None:
-                check(lib().rsx_cin_split_prep_gather(W_h, self._w16_h, self._H_h, self._sizes_h, self.L, self.F, self.split,
-                                                      C.byref(gather_job), _stream()), "rsx_cin_split_prep_gather")
-            else:
-                check(lib().rsx_cin_split_prep(W_h, self._w16_h, self._H_h, self._sizes_h, self.L, self.F, self.split, _stream()),
-                      "rsx_cin_split_prep")
-        else:
-            assert gather_job is None, "CinNet.forward: a lookup can only ride in the split-operand prep launch (gather_ride_ok)"
-        if self.bf16:     # the bf16 operand images of all layers' filters: one launch
-            W_h = (C.c_void_p * self.L)(*[P[f"cin.W{k}"].data_ptr() for k in range(self.L)])
-            check(lib().rsx_cin_prep_bf16_multi(W_h, self._w16_h, self._H_h, self._sizes_h, self.L, self.F, _stream()),
-                  "rsx_cin_prep_bf16_multi")
+        self.path.prep(self, P, gather_job)
         for k, n in enumerate(self.sizes):
             sw = None if sweeps is None or sweeps[k] is None else C.byref(sweeps[k])
-            if self.split:
-                assert sw is None, "the split-operand CIN launches carry no sweep slices"
-                check(lib().rsx_cin_split_fwd(_ptr(X0), _ptr(Xk), _ptr(self.w16[k]), _ptr(P[f"cin.c{k}"]), _ptr(self.outs[k]),
-                                              B, self.F, H, n, self.D, self.split, _stream()), "rsx_cin_split_fwd")
-                Xk, H = self.outs[k], n
-                continue
-            if self.bf16:
-                check(lib().rsx_cin_layer_fwd_bf16(_ptr(X0), _ptr(Xk), _ptr(self.w16[k]), _ptr(P[f"cin.c{k}"]), _ptr(self.outs[k]),
-                                                   B, self.F, H, n, self.D, sw, _stream()), "rsx_cin_layer_fwd_bf16")
-                Xk, H = self.outs[k], n
-                continue
-            check(lib().rsx_cin_layer_fwd(_ptr(X0), _ptr(Xk), _ptr(P[f"cin.W{k}"]), _ptr(P[f"cin.c{k}"]), _ptr(self.outs[k]), B,
-                                          self.F, H, n, self.D, sw, _stream()), "rsx_cin_layer_fwd")
+            self.path.layer_fwd(self, k, X0, Xk, H, P, B, sw)
             Xk, H = self.outs[k], n
         check(lib().rsx_cin_out_fwd(self._outs_h, self._sizes_h, self.L, _ptr(P["cin.Wout"]), _ptr(P["cin.bout"]), _ptr(self.y),
                                     B, self.D, _stream()), "rsx_cin_out_fwd")
@@ -1579,10 +1681,10 @@ class CinNet:
 
     def backward(self, X0, P, gy, sweeps=None, dX0_out=None, lin=None):
         """gy [B]: gradient wrt cin_y.  Writes the cin.* gradients into P[...].grad and returns dX0 [B,F,D] (internal
-        buffer, or dX0_out: a caller-owned contiguous [B,F,D] buffer).  sweeps[k]: slice of the untouched-row optimizer sweep
-        carried by layer k's backward launch; on the bf16 path (L data-gradient launches, then ONE launch with all layers'
-        weight gradients) sweeps has L + 1 entries: [dx of layer 0 .. L-1, the weight-gradient launch]."""
+        buffer, or dX0_out: a caller-owned contiguous [B,F,D] buffer).  sweeps: `backward_launches` slices of the untouched-row
+        optimizer sweep, see backward_sweeps: [k] rides in layer k's backward launch, [L] in the weight-gradient launch."""
         B, L = X0.shape[0], self.L
+        assert sweeps is None or len(sweeps) == self.backward_launches, "CinNet.backward: one sweep slot per backward launch"
         dX0 = self.dX0 if dX0_out is None else dX0_out
         # lin = (logx [B, n], g_lin [B], dwnum [n]): the numeric linear_net gradient rides in the head's backward launch
         lx, gl, dwn = lin if lin is not None else (None, None, None)
@@ -1590,7 +1692,7 @@ class CinNet:
                                         _ptr(P["cin.Wout"].grad), _ptr(P["cin.bout"].grad), _ptr(lx), _ptr(gl), _ptr(dwn),
                                         0 if lx is None else lx.shape[1], B, self.D, _stream()), "rsx_cin_out_bwd_lin")
         wout = P["cin.Wout"].data_ptr()
-        wide = self.bf16 and self.wide and (sweeps is None or all(x is None for x in sweeps[:L]))
+        self.path.begin_bwd(self, sweeps)
         for k in range(L - 1, -1, -1):
             Xk, H = (X0, self.F) if k == 0 else (self.outs[k - 1], self.sizes[k - 1])
             dout = None if k == L - 1 else _ptr(self.dmap[k])
@@ -1598,53 +1700,7 @@ class CinNet:
                 dxk, acc_dxk, acc_dx0 = dX0, 1 if L > 1 else 0, 1
             else:
                 dxk, acc_dxk, acc_dx0 = self.dmap[k - 1], 0, 0 if k == L - 1 else 1
-            if self.split:
-                assert sweeps is None or all(x is None for x in sweeps), "the split-operand CIN launches carry no sweep slices"
-                check(lib().rsx_cin_split_bwd_dx(_ptr(X0), _ptr(Xk), _ptr(self.w16[k]), _ptr(self.outs[k]), dout, _ptr(self.gs),
-                                                 C.c_void_p(wout + 4 * self.offs[k]), _ptr(dxk), 2 if (k == 0 and self.fsplit0) else 0,
-                                                 _ptr(self.dx0_parts[k]),
-                                                 _ptr(self.ws16[k]), B, self.F, H, self.sizes[k], self.D, self.split, _stream()),
-                      "rsx_cin_split_bwd_dx")
-                continue
-            if self.bf16 and wide:
-                # (layer 0: dXk IS dX0 and nothing has been written there yet -- the other layers' shares arrive with the reduce)
-                check(lib().rsx_cin_layer_bwd_dx_bf16_parts(_ptr(X0), _ptr(Xk), _ptr(self.w16[k]), _ptr(self.outs[k]), dout,
-                                                            _ptr(self.gs), C.c_void_p(wout + 4 * self.offs[k]), _ptr(dxk), 0,
-                                                            _ptr(self.dx0_parts[k]), _ptr(self.ws16[k]), B, self.F, H,
-                                                            self.sizes[k], self.D, _stream()), "rsx_cin_layer_bwd_dx_bf16_parts")
-                continue
-            if self.bf16:       # w16[k] was prepared by this step's forward (the filters do not change in between)
-                check(lib().rsx_cin_layer_bwd_dx_bf16(_ptr(X0), _ptr(Xk), _ptr(self.w16[k]), _ptr(self.outs[k]), dout, _ptr(self.gs),
-                                                      C.c_void_p(wout + 4 * self.offs[k]), _ptr(dxk), acc_dxk, _ptr(dX0), acc_dx0,
-                                                      _ptr(self.ws16[k]), B, self.F, H, self.sizes[k], self.D,
-                                                      None if sweeps is None or sweeps[k] is None else C.byref(sweeps[k]),
-                                                      _stream()), "rsx_cin_layer_bwd_dx_bf16")
-                continue
             sw = None if sweeps is None or sweeps[k] is None else C.byref(sweeps[k])
-            check(lib().rsx_cin_layer_bwd(_ptr(X0), _ptr(Xk), _ptr(P[f"cin.W{k}"]), _ptr(self.outs[k]), dout, _ptr(self.gs),
-                                          C.c_void_p(wout + 4 * self.offs[k]), _ptr(dxk), acc_dxk, _ptr(dX0), acc_dx0,
-                                          _ptr(P[f"cin.W{k}"].grad), _ptr(P[f"cin.c{k}"].grad), _ptr(self.dpre), B, self.F, H,
-                                          self.sizes[k], self.D, sw, _stream()), "rsx_cin_layer_bwd")
-        fuse_red = bool(self.split) and _lib.form("cin_dx0_ride") != "0"     # (0: the reduce as its own launch, A/B)
-        if wide or self.split:  # dX0 = layer 0's dXk (already there) + every layer's tile partials, last layer first
-            parts_h = (C.c_void_p * L)(*[self.dx0_parts[k].data_ptr() for k in range(L - 1, -1, -1)])
-            if not fuse_red:
-                check(lib().rsx_cin_dx0_reduce(parts_h, self._tiles_h, L, _ptr(dX0), 1, B, self.F, self.D, _stream()),
-                      "rsx_cin_dx0_reduce")
-        if self.bf16 or self.split:     # every layer's weight gradient in ONE launch
-            jobs = (_lib.CinDwJob * L)()
-            for k in range(L):
-                Xk, H = (X0, self.F) if k == 0 else (self.outs[k - 1], self.sizes[k - 1])
-                jobs[k] = _lib.CinDwJob(Xk.data_ptr(), self.ws16[k].data_ptr(), P[f"cin.W{k}"].grad.data_ptr(),
-                                        P[f"cin.c{k}"].grad.data_ptr(), H, self.sizes[k], B if (wide or self.split) else 0)
-            assert sweeps is None or len(sweeps) == L + 1, "bf16 CinNet.backward: L + 1 sweep slots"
-            if self.split and fuse_red:   # the dX0 reduce rides in the weight-gradient launch (the same sums in the same order)
-                check(lib().rsx_cin_split_bwd_dw_dx0(_ptr(X0), jobs, L, B, self.F, self.D, self.split, parts_h, self._tiles_h, L,
-                                                     _ptr(dX0), 1, _stream()), "rsx_cin_split_bwd_dw_dx0")
-                return dX0[:B]
-            if self.split:
-                check(lib().rsx_cin_split_bwd_dw(_ptr(X0), jobs, L, B, self.F, self.D, self.split, _stream()), "rsx_cin_split_bwd_dw")
-                return dX0[:B]
-            sw = None if sweeps is None or sweeps[L] is None else C.byref(sweeps[L])
-            check(lib().rsx_cin_bwd_dw_bf16(_ptr(X0), jobs, L, B, self.F, self.D, sw, _stream()), "rsx_cin_bwd_dw_bf16")
+            self.path.layer_bwd(self, k, X0, Xk, H, P, B, dout, C.c_void_p(wout + 4 * self.offs[k]), dxk, acc_dxk, dX0, acc_dx0, sw)
+        self.path.end_bwd(self, X0, P, B, dX0, sweeps)
         return dX0[:B]

@@ -136,12 +136,12 @@ def _sweep_weights(store):
     w = [float(store.cin_sizes[k]) * (a1.F if k == 0 else store.cin_sizes[k - 1]) for k in range(L)]
     tw = sum(w)
     env = os.environ.get("RSX_XDFM_SWEEP_WEIGHTS")
-    nd = L + 1 if (store.cin.bf16 or store.cin.split) else L
+    nd = store.cin.backward_launches
     if env:
         wts = [float(x) for x in env.split(",")]
-    elif store.cin.split:      # (the split-operand CIN launches carry nothing)
-        wts = [0.0] * L + [0.0] * nl + [1.0] + [2.0] * nl + [0.0] * (L + 1) + [2.0]
-    elif store.cin.bf16:
+    elif not store.cin.carries_sweeps:      # (the split-operand CIN launches carry nothing)
+        wts = [0.0] * L + [0.0] * nl + [1.0] + [2.0] * nl + [0.0] * nd + [2.0]
+    elif nd == L + 1:                       # (bf16 operands)
         wts = [0.0] * L + [0.0] * nl + [1.0] + [2.0] * nl + [0.0] * L + [2.0] + [2.0]
     else:
         wts = [0.5 * x / tw for x in w] + [0.0] * (2 * nl + 1) + [0.5 * x / tw for x in w][::-1] + [0.0]
@@ -173,8 +173,7 @@ def _train_fused(store, a1, a2, ids, logx, labels, params, masks):
                 nl = len(store.tower.widths)
                 sl_all = plan.sweeps
                 bw = sl_all[L + 2 * nl + 1:L + 2 * nl + 1 + nd]
-                # CinNet.forward: fwd_k; CinNet.backward: layer order (bf16: dx_0..dx_{L-1}, then the dW launch)
-                sweeps = sl_all[:L] + (bw[:L][::-1] + bw[L:] if (store.cin.bf16 or store.cin.split) else bw[::-1])
+                sweeps = sl_all[:L] + store.cin.backward_sweeps(bw)      # CinNet.forward: fwd_k; CinNet.backward: its own order
                 tower_sweeps = sl_all[L:L + 2 * nl + 1]
                 ride = ride and all(x is None for x in sl_all[:L + 1])    # no slice before the launch that carries the sort
             if not ride:

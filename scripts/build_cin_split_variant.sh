@@ -1,5 +1,5 @@
 #!/bin/bash
-# usage: scripts/build_cin_split_variant.sh <name> [extra hipcc flags]   e.g.  stamps -DRSX_STAMPS   |   dbg1 -DRSX_CIN_DBG=1
+# usage: scripts/build_cin_split_variant.sh <name> [extra hipcc flags]   e.g.  stamps -DRSX_STAMPS
 # A probe build of ONE translation unit (csrc/cin_split.hip) linked with the product build's other objects (recsys_amd/_obj, run
 # `python -m recsys_amd.build` first) -> scripts/_build/librsx_cs_<name>.so: seconds instead of the minutes of build_stamps.sh.
 root=$(cd "$(dirname "$0")/.." && pwd)

@@ -1,8 +1,6 @@
 """Split-operand bf16 MFMA path of the CIN layer (csrc/cin_split.hip): ns planes per contraction operand.
   ns = 3 is the parity path: every product exact to 2^-23, so the kernels are compared with the PLAIN fp64 evaluation
   (the oracle's formula, oracle/models.py cin_layer_fwd / cin_layer_bwd) at fp32-accumulation tolerance;
-  ns = 1 is compared with the fp64 evaluation in which the operands are rounded to bf16 first (as tests/test_gpu_cin_bf16.py);
-  ns = 2 sits in between (2^-16-grade products);
   ns = 4: forward / data gradients with two scaled fp16 planes per operand (three MFMAs per k-step, products to 2^-22), weight
   gradients on three bf16 planes -- held to the SAME tolerances as ns = 3, plus a test with operands spread over 2^40."""
 import ctypes as C
@@ -12,12 +10,6 @@ import pytest
 
 pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
-
-
-def bf16_round(x):
-    u = np.ascontiguousarray(x, np.float32).view(np.uint32).astype(np.uint64)
-    r = ((u + 0x7FFF + ((u >> 16) & 1)) >> 16) << 16
-    return r.astype(np.uint32).view(np.float32).reshape(np.shape(x))
 
 
 def _rel(a, b):
@@ -63,8 +55,7 @@ def test_cin_split_forward(B, F, H, N, first, ns):
     torch.cuda.synchronize()
     got = out.cpu().numpy()
     f8 = np.float64
-    Xr, Wr = (bf16_round(Xk), bf16_round(W)) if ns == 1 else (Xk, W)
-    pre = np.einsum("bfd,bhd,fhn->bnd", X0.astype(f8), Xr.astype(f8), Wr.astype(f8).reshape(F, H, N), optimize=True) + c[None, :, None]
+    pre = np.einsum("bfd,bhd,fhn->bnd", X0.astype(f8), Xk.astype(f8), W.astype(f8).reshape(F, H, N), optimize=True) + c[None, :, None]
     ref = np.maximum(pre, 0)
     assert np.isfinite(got).all()
     err = _rel(got, ref)
@@ -88,8 +79,7 @@ BTOL = {4: 3e-6, 3: 3e-6}
 @pytest.mark.parametrize("ns", [4, 3])
 @pytest.mark.parametrize("B,F,H,N,first,gs,acc", BWD_SHAPES)
 def test_cin_split_backward(B, F, H, N, first, gs, acc, ns):
-    """dXk, dX0 (tile partials + the reduce launch), dW, dc.  ns = 3 / 2: against the plain fp64 gradients of the oracle's
-    formula; ns = 1: against fp64 with the operands (W, dpre, the products X0 * Xk) rounded to bf16 first."""
+    """dXk, dX0 (tile partials + the reduce launch), dW, dc against the plain fp64 gradients of the oracle's formula."""
     from recsys_amd import _lib
     from recsys_amd.ops import _ptr, _stream, check, lib
     if first:
@@ -123,13 +113,12 @@ def test_cin_split_backward(B, F, H, N, first, gs, acc, ns):
     torch.cuda.synchronize()
     got = dict(out=out.cpu().numpy(), dX0=dX0.cpu().numpy(), dXk=dXk.cpu().numpy(), dW=dW.cpu().numpy(), dc=dc.cpu().numpy())
     f8 = np.float64
-    rd = bf16_round if ns == 1 else (lambda x: x)
-    W3 = rd(W).astype(f8).reshape(F, H, N)
+    W3 = W.astype(f8).reshape(F, H, N)
     g = dout.astype(f8) + (gsv[:, None, None] * wout[None, :, None] if gs else 0.0)
     dpre = g * (got["out"] > 0)                        # the kernel masks with ITS forward output
-    dpre_r = rd(dpre.astype(np.float32)).astype(f8)
+    dpre_r = dpre.astype(np.float32).astype(f8)
     Z = (X0[:, :, None, :] * Xk[:, None, :, :]).astype(np.float32)          # fp32 product, rounded once
-    dW_r = np.einsum("bfhd,bnd->fhn", rd(Z).astype(f8), dpre_r, optimize=True).reshape(F * H, N)
+    dW_r = np.einsum("bfhd,bnd->fhn", Z.astype(f8), dpre_r, optimize=True).reshape(F * H, N)
     dc_r = dpre.sum((0, 2))
     dXk_r = np.einsum("bfd,fhn,bnd->bhd", X0.astype(f8), W3, dpre_r, optimize=True)
     dX0_r = np.einsum("bhd,fhn,bnd->bfd", Xk.astype(f8), W3, dpre_r, optimize=True)

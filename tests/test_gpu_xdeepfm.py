@@ -171,9 +171,11 @@ def test_xdeepfm_hip_graph(cin_split):
     assert err < 1e-5 and max(perr.values()) < 5e-5, (err, perr)
 
 
+@pytest.mark.parametrize("split", [0, 3, 4])
 @pytest.mark.parametrize("B,F,sizes", [(7, 39, (128, 128)), (5, 6, (20, 10, 10)), (3, 9, (33,)), (64, 39, (40, 8))])
-def test_cin_net_fused_head(B, F, sizes):
-    """CinNet (layers + the concat / reduce_sum / dense(relu) head, xdeepfm.py:135-182) against the fp64 oracle chain."""
+def test_cin_net_fused_head(B, F, sizes, split):
+    """CinNet (layers + the concat / reduce_sum / dense(relu) head, xdeepfm.py:135-182) against the fp64 oracle chain: the fp32
+    path (split = 0) and the two split-operand modes, held to the same bars (capacity B + 3: mode 4 splits layer 0's fields)."""
     from recsys_amd.ops import CinNet, DenseArena
     rng = np.random.default_rng(B + 10 * len(sizes))
     D = 16
@@ -204,7 +206,7 @@ def test_cin_net_fused_head(B, F, sizes):
         d0, dnext, g_o[f"cin.W{k}"], g_o[f"cin.c{k}"] = models.cin_layer_bwd(X64, Xs[k], V[f"cin.W{k}"], Xs[k + 1], dout)
         dX0_o += d0
     dX0_o += dnext
-    net = CinNet(F, D, sizes, B + 3)
+    net = CinNet(F, D, sizes, B + 3, split=split)
     tx = torch.from_numpy(X0).cuda()
     y = net.forward(tx, P)
     np.testing.assert_allclose(y.cpu().numpy(), y_o.reshape(-1), rtol=2e-5, atol=2e-5)
