@@ -1183,6 +1183,57 @@ int rsx_log_thresholds_h(const float* boundaries_h, int nb, float* thr_h);
 int rsx_bucketize_thr_h(const float* x_h, int64_t n, const float* thr_h, int nb, float shift, int32_t* out_h);
 uint64_t rsx_fingerprint64_dev_h(const uint8_t* s_h, size_t n);
 
+/* ---------------------------------------------------------------------------------------------
+ * Device parse of the input_fn stream (since rsx_version() 103): framed TFRecord records of the Criteo-39 schema -> label and
+ * ids of SEVERAL batches in ONE launch, in the packing Estimator.train / evaluate / predict consume (estimator.PackedBatch), so
+ * that `criteo_input_fn(device_parse=True)` ships raw shard bytes and the host neither walks the protobuf, hashes, takes a logf
+ * nor computes a payload CRC.  Same contract as above -- DECLINE, NEVER GUESS -- with the label REQUIRED (rsx_criteo_parse_h
+ * without bit 16 of `threads`) and the CRC that verify_crc promises.  For any bytes, status[r] is
+ *   RSX_PARSE_OK               label and ids of record r are exactly what rsx_criteo_parse_h writes, at
+ *                                label (fp32 bits)  out + (r / rows_per_batch) * batch_stride + 4 * (r % rows_per_batch)
+ *                                ids[F] (int32)     out + (r / rows_per_batch) * batch_stride + ids_off + 4 * F * (r % rows_per_batch)
+ *   anything else              NEITHER was written (not one byte of `out` for this record); the caller parses on the host.
+ * Decided in this order, the first failure is the status:
+ *   RSX_PARSE_BAD_OFFSETS      rec_off[r] < 12, rec_len[r] < 0 or rec_off[r] + rec_len[r] + 4 > buf_bytes: no byte was read
+ *   RSX_PARSE_BAD_SPEC         as above
+ *   RSX_PARSE_TOO_LONG         rec_len[r] > RSX_PARSE_MAX_RECORD
+ *   RSX_PARSE_CRC              (verify_crc != 0 only) the framing's 8-byte length differs from rec_len[r], the masked CRC-32C of
+ *                              those 8 bytes differs from the 4 bytes behind them, or the payload's from the 4 bytes behind it
+ *   RSX_PARSE_MALFORMED, RSX_PARSE_MISSING_NUMERIC   as above
+ *   RSX_PARSE_MISSING_LABEL    `_c0` has no value (RSX_EDATA on the host)
+ * buf: the staged shard bytes WITH their framing (u64 length | u32 masked crc | payload | u32 masked crc per record), 4-byte
+ * aligned, buf_bytes a multiple of 4 that the caller owns in full; rec_off[n] / rec_len[n] int32: the payload of record r is
+ * buf[rec_off[r], rec_off[r] + rec_len[r]), its framing the 12 bytes in front and the 4 behind (records may lie anywhere, in any
+ * order; rsx_tfrecord_index_h finds them).  out: 4-byte aligned, the caller owns ceil(n / rows_per_batch) * batch_stride bytes;
+ * a final partial batch is a launch of its own with its own rows_per_batch.
+ * One workgroup of one wave per record: the record AND its framing are staged into LDS once, the CRC (64 lanes: a chunk each,
+ * combined in GF(2), csrc/parse_device.h) and the parse both read from there.  No atomics, no workspace, no sync.
+ * Every argument is refused before any device call -- RSX_EINVAL: a NULL buf / rec_off / rec_len / spec / out / status or spec
+ * member, n <= 0, F <= 0, rows_per_batch <= 0, buf_bytes <= 0, above 2^31 - 4 or no multiple of 4, a pointer, ids_off or
+ * batch_stride not 4-byte aligned, ids_off < 4 * rows_per_batch, batch_stride < ids_off + 4 * F * rows_per_batch;
+ * RSX_EUNSUPPORTED outside rsx_criteo_parse_records_supported(n, F): F > 64.
+ * rsx_criteo_parse_records_dev_h is the HOST TWIN (host pointers, the same routines and decisions, the CRC through the same 64
+ * virtual lanes); rsx_masked_crc32c_dev_h is that 64-lane CRC alone (== rsx_masked_crc32c_h; n < 2^31).  For tests; the
+ * product path calls neither.
+ * ------------------------------------------------------------------------------------------- */
+enum {
+  RSX_PARSE_MISSING_LABEL = 6,
+  RSX_PARSE_CRC = 7
+};
+int rsx_criteo_parse_records_supported(int n, int F);
+int rsx_criteo_parse_records(const uint8_t* buf, int64_t buf_bytes, const int32_t* rec_off, const int32_t* rec_len, int n,
+                             const rsx_parse_spec* spec_h, int verify_crc, void* out, int rows_per_batch, int64_t batch_stride,
+                             int64_t ids_off, int32_t* status, rsx_stream_t stream);
+int rsx_criteo_parse_records_dev_h(const uint8_t* buf_h, int64_t buf_bytes, const int32_t* rec_off_h, const int32_t* rec_len_h,
+                                   int n, const rsx_parse_spec* spec_h, int verify_crc, void* out_h, int rows_per_batch,
+                                   int64_t batch_stride, int64_t ids_off, int32_t* status_h);
+uint32_t rsx_masked_crc32c_dev_h(const uint8_t* p_h, size_t n);
+/* The producer thread of the device-parse stream copies, launches and waits on a stream of its own while the training thread
+ * may be capturing a HIP graph in the default (global) capture mode, under which those calls from ANOTHER thread are refused
+ * ("operation not permitted when stream is capturing").  This puts the CALLING thread into hipStreamCaptureModeRelaxed; it
+ * touches no stream that is being captured.  -> RSX_OK, or RSX_ELAUNCH when the runtime refuses.                          */
+int rsx_thread_capture_relaxed_h(void);
+
 /* bf16 MFMA path of the CIN layer (north_star: "MFMA only on the CIN feature-map contraction where it is genuinely a
  * dense bf16 GEMM"; xdeepfm/xdeepfm.py:145-169).  Same contract as rsx_cin_layer_fwd / rsx_cin_layer_bwd, with the
  * filter W replaced by a bf16 image prepared once per step:

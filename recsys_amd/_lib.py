@@ -226,6 +226,7 @@ class ParseSpec(C.Structure):
 
 PARSE_MAX_RECORD = 8192               # include/rsx.h RSX_PARSE_MAX_RECORD
 (PARSE_OK, PARSE_MALFORMED, PARSE_MISSING_NUMERIC, PARSE_TOO_LONG, PARSE_BAD_OFFSETS, PARSE_BAD_SPEC) = range(6)
+PARSE_MISSING_LABEL, PARSE_CRC = 6, 7  # rsx_criteo_parse_records only
 
 ADAM_STATE_WORDS = 4 + 32 * 32        # include/rsx.h RSX_ADAM_STATE_WORDS
 
@@ -388,6 +389,11 @@ _SIGS = {
     "rsx_criteo_parse_examples_supported": (_I, [_I, _I]),
     "rsx_criteo_parse_examples": (_I, [_P, C.c_int64, _P, _I, C.POINTER(ParseSpec), _P, _P, _P]),
     "rsx_criteo_parse_dev_h": (_I, [_P, C.c_int64, _P, _I, C.POINTER(ParseSpec), _P, _P]),
+    "rsx_criteo_parse_records_supported": (_I, [_I, _I]),
+    "rsx_criteo_parse_records": (_I, [_P, C.c_int64, _P, _P, _I, C.POINTER(ParseSpec), _I, _P, _I, C.c_int64, C.c_int64, _P, _P]),
+    "rsx_criteo_parse_records_dev_h": (_I, [_P, C.c_int64, _P, _P, _I, C.POINTER(ParseSpec), _I, _P, _I, C.c_int64, C.c_int64, _P]),
+    "rsx_masked_crc32c_dev_h": (C.c_uint32, [_P, C.c_size_t]),
+    "rsx_thread_capture_relaxed_h": (_I, []),
     "rsx_log_thresholds_h": (_I, [_P, _I, _P]),
     "rsx_bucketize_thr_h": (_I, [_P, C.c_int64, _P, _I, _F, _P]),
     "rsx_fingerprint64_dev_h": (C.c_uint64, [_P, C.c_size_t]),

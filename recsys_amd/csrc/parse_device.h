@@ -327,3 +327,108 @@ PD_FN int32_t pd_slot_id(const pd_spec& sp, int s, bool have, uint64_t bits) {
   }
   return (int32_t)((have ? bits : sp.null_hash) % (uint64_t)sp.slot_rows[s]);
 }
+
+// ===== TFRecord records of the input_fn stream (parse_records.hip and its host twin rsx_criteo_parse_records_dev_h) ==========
+
+// ---- one map entry, label aware ---------------------------------------------------------------------------------------------
+// pd_parse_entry with `_c0` counted: 1 with j == 0 gives the bit pattern of the label's first float (packed or unpacked, through
+// pd_first_float, like `_c1` .. `_c13`); everything else as pd_parse_entry.  The training stream REQUIRES the label (the host
+// reader answers RSX_EDATA for a record without it), so the caller declines a record whose field 0 got no value.
+PD_FN int pd_parse_entry_label(const uint8_t* rec, uint32_t off, uint32_t len, int& j, uint64_t& bits) {
+  uint32_t p = off, fno = 0, wt = 0, vo = 0, vl = 0;
+  const uint32_t e = off + len;
+  bool hk = false, hf = false;
+  uint32_t ko = 0, kl = 0, fo = 0, fl = 0;
+  int r;
+  while ((r = pd_next_field(rec, p, e, fno, wt, vo, vl)) > 0) {
+    if (fno == 1 && wt == 2) {
+      hk = true;
+      ko = vo;
+      kl = vl;
+    } else if (fno == 2 && wt == 2) {
+      hf = true;
+      fo = vo;
+      fl = vl;
+    }
+  }
+  if (r < 0) return -1;
+  if (!hk) return 0;
+  j = pd_key_cN(rec, ko, kl);
+  if (j < 0 || !hf) return 0;
+  if (j <= 13) {
+    uint32_t b;
+    if (!pd_first_float(rec, fo, fl, b)) return 0;
+    bits = b;
+    return 1;
+  }
+  uint32_t so, sl;
+  if (!pd_first_bytes(rec, fo, fl, so, sl)) return 0;
+  bits = pd_fp64(rec + so, sl);
+  return 1;
+}
+
+// ---- masked CRC-32C of the TFRecord framing, computed by 64 lanes -------------------------------------------------------------
+// CRC-32C (Castagnoli, reflected, polynomial 0x82F63B78), as rsx_crc32c_h: register 0xFFFFFFFF at the start, complemented at the
+// end.  A value is a polynomial over GF(2) of degree < 32 whose coefficient of x^k is bit 31 - k (x^0 = 0x80000000).
+//
+// With a ZERO start register the CRC is linear in the message: crc0(A || B) = crc0(A) * x^(8|B|) mod P  ^  crc0(B), and zero
+// bytes in front of a message do not change it.  The start register 0xFFFFFFFF is the same as complementing the first 4
+// message bytes (n >= 4).  So the message, right-aligned into 64 chunks of L = ceil(n / 64) bytes (the first chunks are the
+// zero bytes in front), is split over 64 lanes: lane i takes chunk i with the bitwise byte step (pd_crc_chunk), multiplies its
+// value by x^(8 L (63 - i)) (pd_crc_shift: the six squarings of x^(8L) are the same in every lane, at most six multiplies
+// are the lane's own) and the 64 values are xor-ed.  No table: 8 shift-and-xor steps per byte, 32 per multiply.
+#define PD_CRC_POLY 0x82F63B78u
+PD_FN uint32_t pd_crc_byte(uint32_t c, uint32_t b) {
+  c ^= b;
+  for (int k = 0; k < 8; ++k) c = (c >> 1) ^ (PD_CRC_POLY & (0u - (c & 1u)));
+  return c;
+}
+// a * b mod P: a 32-step carry-less multiply
+PD_FN uint32_t pd_crc_mul(uint32_t a, uint32_t b) {
+  uint32_t p = 0;
+  for (int k = 0; k < 32; ++k) {
+    p ^= b & (0u - ((a >> (31 - k)) & 1u));
+    b = (b >> 1) ^ (PD_CRC_POLY & (0u - (b & 1u)));
+  }
+  return p;
+}
+// x^(8L) mod P, L >= 1 (square and multiply over the bits of L; the same in every lane)
+PD_FN uint32_t pd_crc_xpow8(uint32_t L) {
+  uint32_t r = 0x80000000u, sq = 0x00800000u;          // x^0, x^8
+  for (; L; L >>= 1) {
+    if (L & 1u) r = pd_crc_mul(r, sq);
+    sq = pd_crc_mul(sq, sq);
+  }
+  return r;
+}
+// Chunk routine of lane `lane` (0 .. 63): the zero-start CRC of bytes [lane * L, (lane + 1) * L) of the right-aligned message
+// (64 * L - n zero bytes, then rec[0, n) with its first 4 bytes complemented).  n >= 4, L = ceil(n / 64); reads rec[i], i < n only.
+PD_FN uint32_t pd_crc_chunk(const uint8_t* rec, uint32_t n, uint32_t L, int lane) {
+  const uint32_t pad = 64u * L - n;                     // < 64
+  const uint32_t v0 = (uint32_t)lane * L, v1 = v0 + L;
+  uint32_t c = 0;
+  for (uint32_t v = v0 < pad ? pad : v0; v < v1; ++v) {
+    const uint32_t i = v - pad;
+    c = pd_crc_byte(c, (uint32_t)rec[i] ^ (i < 4u ? 0xffu : 0u));
+  }
+  return c;
+}
+// Combine step of lane `lane`: c * x^(8 L (63 - lane)) mod P, given xL = x^(8L) -- the chunk's value moved in front of the
+// 63 - lane chunks behind it.  The xor of the 64 results is the zero-start CRC of the whole right-aligned message.
+PD_FN uint32_t pd_crc_shift(uint32_t c, uint32_t xL, int lane) {
+  const uint32_t e = 63u - (uint32_t)lane;
+  uint32_t sq = xL;
+  for (int k = 0; k < 6; ++k) {
+    if ((e >> k) & 1u) c = pd_crc_mul(c, sq);
+    sq = pd_crc_mul(sq, sq);
+  }
+  return c;
+}
+// Messages shorter than 4 bytes (the start register does not fit into them): the plain serial CRC.
+PD_FN uint32_t pd_crc_short(const uint8_t* rec, uint32_t n) {
+  uint32_t c = 0xffffffffu;
+  for (uint32_t i = 0; i < n; ++i) c = pd_crc_byte(c, rec[i]);
+  return c ^ 0xffffffffu;
+}
+// TFRecord's mask of a CRC (rsx_masked_crc32c_h)
+PD_FN uint32_t pd_crc_mask(uint32_t c) { return ((c >> 15) | (c << 17)) + 0xa282ead8u; }

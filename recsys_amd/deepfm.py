@@ -7,6 +7,7 @@ mode, params)`, `main`.  The embedding gather + first-order + FM term, the row-w
 and the TF-1 Adam sweep are librsx.so kernels; the 624-100-100-1 tower is rocBLAS via torch.
 """
 import argparse
+import os
 
 import torch
 
@@ -213,6 +214,10 @@ def define_flags(p=None):
     p.add_argument("--l1_regularization_strength", type=float, default=0.0, help="ftrl")
     p.add_argument("--l2_regularization_strength", type=float, default=0.0, help="ftrl")
     p.add_argument("--l2_shrinkage_regularization_strength", type=float, default=0.0, help="ftrl")
+    p.add_argument("--device_parse", type=lambda s: s.lower() in ("1", "true", "yes"), default=False,
+                   help="parse the TFRecord shards on the GPU (input_pipeline.criteo_input_fn(device_parse=True)): the host ships "
+                        "raw shard bytes; same batches, same bits.  Single-replica fm.py / deepfm.py / dcn.py with the Criteo "
+                        "feature set only")
     p.add_argument("--feature_set", default="criteo", choices=["criteo", "uid_iid"],
                    help="criteo: the 39-field pipeline of fm.py (BASELINE configs); uid_iid: deepfm.py as committed "
                         "(int64 u_id / i_id hashed into 500000 / 100000 buckets, int64 label)")
@@ -220,14 +225,17 @@ def define_flags(p=None):
 
 
 def input_fn(filenames, batch_size, num_epochs=-1, need_shuffle=False, num_parallel=8, layout=None, shard=None,
-             shard_tail=False):
+             shard_tail=False, device_parse=False):
+    if device_parse:                   # refused before anything is opened: see input_pipeline.check_device_parse
+        from .input_pipeline import check_device_parse
+        check_device_parse(layout=layout, world=1 if shard is None else shard[1])
     if layout is not None and layout.columns[0].key in ("i_id", "u_id"):     # --feature_set uid_iid (the script as committed)
         from .input_pipeline import uid_iid_input_fn
         assert shard is None or shard[1] == 1, "--feature_set uid_iid: single replica only"
         return uid_iid_input_fn(filenames, batch_size, num_epochs, need_shuffle, layout)
     from .input_pipeline import criteo_input_fn
     return criteo_input_fn(filenames, batch_size, num_epochs, need_shuffle, num_parallel, layout, shard=shard,
-                           shard_tail=shard_tail)
+                           shard_tail=shard_tail, device_parse=device_parse)
 
 
 def make_params(FLAGS, linear="indicator_all"):
@@ -264,6 +272,21 @@ def run_main(model_fn, FLAGS, make_params_fn):
     directory.  The reference's deepfm.py exports after EVERY task because its `main` falls through to the export lines
     (deepfm/deepfm.py:220-234); here a model is exported only when asked."""
     optimizer, optimizer_hparams = optimizer_config(FLAGS)
+    device_parse = bool(getattr(FLAGS, "device_parse", False))
+    if device_parse:                   # what the device parse does not serve ends here, before anything is built or spawned
+        import sys
+        from .input_pipeline import check_device_parse
+        module = model_fn.__module__
+        if module == "__main__":
+            spec = getattr(sys.modules["__main__"], "__spec__", None)
+            module = spec.name if spec is not None else module
+        check_device_parse(model=module)
+        if getattr(FLAGS, "feature_set", "criteo") != "criteo":
+            check_device_parse(layout=CriteoLayout.from_columns(make_params_fn(FLAGS)["embedding_feature_columns"]))
+        if FLAGS.mirror and optimizer == "adam":
+            from . import dist
+            world = int(os.environ.get("WORLD_SIZE", "0") or 0) or dist.local_replica_count()
+            check_device_parse(world=max(1, world))
     if optimizer != "adam" and FLAGS.mirror:
         # data-parallel training exists for the Adam step only (VariableStore.build refuses a data-parallel store)
         print("INFO:--optimizer %s: one replica in this process (data-parallel training supports --optimizer adam only)"
@@ -295,14 +318,18 @@ def run_main(model_fn, FLAGS, make_params_fn):
             shard = (dp.rank, dp.world)
     layout = CriteoLayout.from_columns(params["embedding_feature_columns"])
     if FLAGS.task_type == "train":
-        tr = TrainSpec(lambda: input_fn(train_files, FLAGS.batch_size, FLAGS.num_epochs, True, FLAGS.num_parallel, layout, shard))
-        ev = EvalSpec(lambda: input_fn(eval_files, FLAGS.batch_size, 1, False, FLAGS.num_parallel, layout, shard, True), steps=200)
+        tr = TrainSpec(lambda: input_fn(train_files, FLAGS.batch_size, FLAGS.num_epochs, True, FLAGS.num_parallel, layout, shard,
+                                        device_parse=device_parse))
+        ev = EvalSpec(lambda: input_fn(eval_files, FLAGS.batch_size, 1, False, FLAGS.num_parallel, layout, shard, True,
+                                       device_parse=device_parse), steps=200)
         return train_and_evaluate(est, tr, ev)
     if FLAGS.task_type == "eval":
-        return est.evaluate(lambda: input_fn(eval_files, FLAGS.batch_size, 1, False, FLAGS.num_parallel, layout, shard, True), steps=200)
+        return est.evaluate(lambda: input_fn(eval_files, FLAGS.batch_size, 1, False, FLAGS.num_parallel, layout, shard, True,
+                                             device_parse=device_parse), steps=200)
     if FLAGS.task_type == "infer":
         out = []
-        for i, p in enumerate(est.predict(lambda: input_fn(eval_files, FLAGS.batch_size, 1, False, FLAGS.num_parallel, layout))):
+        for i, p in enumerate(est.predict(lambda: input_fn(eval_files, FLAGS.batch_size, 1, False, FLAGS.num_parallel, layout,
+                                                           device_parse=device_parse))):
             if est._is_chief():
                 print(p)
             out.append(p)

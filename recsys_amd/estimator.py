@@ -84,6 +84,23 @@ class PackedBatch:
     _flat_layouts = {}      # (key of a FlatFeatures batch) -> (layout, nbytes): batches of one stream share them
 
     def __init__(self, features, labels, device=None, pin=False):
+        dev_flat = getattr(features, "dev_flat", None)
+        if isinstance(dev_flat, torch.Tensor) and dev_flat.is_cuda and device is None and not pin:
+            # the device-parse stream wrote the batch on the device in this packing (input_pipeline.DeviceFeatures): adopt its
+            # buffer.  It was allocated on the producer's stream: tell the allocator which stream reads it from here on.
+            ids = features.get("ids")
+            if len(features) == 1 and isinstance(ids, torch.Tensor) and isinstance(labels, torch.Tensor) and \
+                    ids.dtype == torch.int32 and labels.dtype == torch.float32 and labels.data_ptr() == dev_flat.data_ptr():
+                o_ids = (labels.numel() * 4 + 15) & ~15
+                nb_ids = ids.numel() * 4
+                if ids.data_ptr() == dev_flat.data_ptr() + o_ids and dev_flat.numel() == (o_ids + nb_ids + 15) & ~15 and \
+                        ids.is_contiguous() and labels.is_contiguous():
+                    self.layout = [("__label__", labels.dtype, tuple(labels.shape), 0, labels.numel() * 4),
+                                   ("ids", ids.dtype, tuple(ids.shape), o_ids, nb_ids)]
+                    self.nbytes = dev_flat.numel()
+                    self.flat = dev_flat
+                    dev_flat.record_stream(torch.cuda.current_stream(dev_flat.device))
+                    return
         flat_np = getattr(features, "flat", None)
         if flat_np is not None and device is None and not pin:
             # the input pipeline's reader already assembled the batch in this packing (input_pipeline.FlatFeatures): O(1)

@@ -9,6 +9,7 @@ The host half of `input_layer` (FarmHash % bucket, bucketize(log(x+shift))) runs
 pipeline yields `features = {'ids': int32 [B,39], 'cont_log': float32 [B,13]}` and `labels` float32 [B,1].
 """
 import ctypes as C
+import os
 import queue
 import threading
 
@@ -250,6 +251,317 @@ def _criteo_batches(filenames, batch_size, num_epochs, layout, threads, shard, v
         rd.close()
 
 
+# ---- device parse of the batch stream (opt-in; csrc/parse_records.hip) -------------------------------------------
+DEVICE_PARSE_ONLY = "device parse is single-replica Criteo fm / deepfm / dcn only"
+# what the stream did in this process (scripts/e2e_train_bench.py, tests): kernel launches, records, bytes shipped, batches that
+# went back to the host parser
+device_parse_stats = {"launches": 0, "records": 0, "bytes": 0, "fallback_batches": 0}
+
+
+def check_device_parse(layout=None, world=1, model=None):
+    """Raises RsxError for what the device parse does not serve: data-parallel sharding of the stream, xdeepfm.py (its linear
+    part consumes the logf values themselves, which the device batches do not carry) and the uid_iid / din feature sets."""
+    if int(world) > 1:
+        raise RsxError("%s (the stream of %d replicas is sharded by the host reader)" % (DEVICE_PARSE_ONLY, world))
+    if model is not None and str(model).split(".")[-1] not in ("fm", "deepfm", "dcn"):
+        raise RsxError("%s (not %s)" % (DEVICE_PARSE_ONLY, str(model).split(".")[-1]))
+    if layout is not None:
+        for c in layout.columns:
+            k = str(c.key)
+            if not (k.startswith("_c") and k[2:].isdigit() and 1 <= int(k[2:]) <= 39):
+                raise RsxError("%s (feature %r is no Criteo field)" % (DEVICE_PARSE_ONLY, k))
+
+
+class DeviceFeatures(dict):
+    """The device counterpart of FlatFeatures: the features dict of one batch whose `ids` (and the labels) are views of ONE
+    flat DEVICE buffer in estimator.PackedBatch's own packing (label | ids, 16-byte aligned parts); `dev_flat` is that buffer
+    (torch.uint8), which PackedBatch adopts without a copy.  It carries no `cont_log`."""
+    __slots__ = ("dev_flat", "pack_key")
+
+
+def _device_packing(rows, F):
+    """-> (offset of the ids, bytes) of a [rows]-batch packed like PackedBatch packs ({'ids': int32 [rows, F]}, fp32 [rows, 1])."""
+    o_ids = (rows * 4 + 15) & ~15
+    return o_ids, (o_ids + rows * F * 4 + 15) & ~15
+
+
+def _stream_error(filenames, code):
+    return RsxError("%s: %s" % (filenames[0] if len(filenames) == 1 else "TFRecord stream", lib().rsx_strerror(int(code)).decode()))
+
+
+def _map_shard(path):
+    """-> (mapping uint8, payload offsets int64 [n], lengths int64 [n]): the shard memory-mapped and indexed with the framing's
+    CRCs NOT verified (the device verifies them); a truncated shard raises here, as in read_shard."""
+    if os.path.getsize(path) == 0:
+        return np.zeros(0, np.uint8), np.zeros(0, np.int64), np.zeros(0, np.int64)
+    mm = np.memmap(path, dtype=np.uint8, mode="r")
+    L = lib()
+    n = L.rsx_tfrecord_index_h(_p(mm), mm.size, None, None, 0, 0)
+    if n < 0:
+        raise RsxError("%s: %s" % (path, L.rsx_strerror(int(n)).decode()))
+    offs, lens = np.empty(n, np.int64), np.empty(n, np.int64)
+    n2 = L.rsx_tfrecord_index_h(_p(mm), mm.size, _p(offs), _p(lens), n, 0)
+    if n2 < 0:
+        raise RsxError("%s: %s" % (path, L.rsx_strerror(int(n2)).decode()))
+    return mm, offs, lens
+
+
+def _batch_descriptors(filenames, batch_size, num_epochs):
+    """The batch stream of the C++ reader as DESCRIPTORS: (rows, spans), a span = (mapping, offsets, lengths) of consecutive
+    records of one file.  Consecutive files form one record stream, the final partial batch of an epoch is kept, num_epochs
+    is honoured.  A descriptor holds its mappings alive and nothing else: a shuffle buffer of them costs no memory."""
+    epoch = 0
+    while num_epochs < 0 or epoch < num_epochs:
+        spans, have, any_batch = [], 0, False
+        for path in filenames:
+            mm, offs, lens = _map_shard(path)
+            s, n = 0, len(offs)
+            while s < n:
+                take = min(batch_size - have, n - s)
+                spans.append((mm, offs[s:s + take], lens[s:s + take]))
+                have, s = have + take, s + take
+                if have == batch_size:
+                    yield have, spans
+                    spans, have, any_batch = [], 0, True
+        if have:
+            yield have, spans
+        elif not any_batch:
+            return                                      # (no record at all: an endless epoch loop would spin)
+        epoch += 1
+
+
+def _host_batch(spans, rows, parser, verify_crc, filenames):
+    """One batch parsed on the host, what the stream falls back to when the device declined one of its records -> flat uint8 in
+    the device packing.  The framing's CRCs are verified here (verify_crc); a corrupt or malformed record raises the RsxError of
+    the default path."""
+    L = lib()
+    o_ids, nbytes = _device_packing(rows, parser.F)
+    flat = np.zeros(nbytes, np.uint8)
+    label = flat[:rows * 4].view(np.float32).reshape(rows, 1)
+    ids = flat[o_ids:o_ids + rows * parser.F * 4].view(np.int32).reshape(rows, parser.F)
+    k = 0
+    for mm, offs, lens in spans:
+        if verify_crc:
+            for o, n in zip(offs.tolist(), lens.tolist()):
+                head, rec = mm[o - 12:o], mm[o:o + n + 4]
+                if int(head[8:12].view("<u4")[0]) != L.rsx_masked_crc32c_h(_p(head), 8) or \
+                        int(rec[n:n + 4].copy().view("<u4")[0]) != L.rsx_masked_crc32c_h(_p(rec), n):
+                    raise _stream_error(filenames, -4)
+        feats, lab = parser(mm, offs, lens)
+        m = len(offs)
+        label[k:k + m], ids[k:k + m] = lab, feats["ids"]
+        k += m
+    return flat
+
+
+class _DeviceParseStep:
+    """The product's chunk parse: ONE H2D copy of the staged chunk (offset table, then bytes) from a pinned buffer, ONE
+    rsx_criteo_parse_records launch, the status words copied back -- all on a stream of its own, waited for through an event of
+    its own.  The output buffer is allocated per chunk (the yielded batches are views of it and own it); the input buffer is
+    only read by the kernel and is reused after the wait."""
+
+    def __init__(self, layout, device):
+        import torch
+        from ._lib import ParseSpec
+        self.torch = torch
+        dev = torch.device(device if device is not None else "cuda")
+        self.dev = torch.device("cuda", torch.cuda.current_device()) if dev.index is None else dev
+        arrays = criteo_parse_spec(layout)
+        self._spec_dev = {k: torch.from_numpy(arrays[k]).to(self.dev) for k in ("slot_src", "slot_rows", "thr", "thr_off", "shift")}
+        self.spec = ParseSpec()
+        for k, t in self._spec_dev.items():
+            setattr(self.spec, k, t.data_ptr())
+        self.spec.F, self.spec.null_hash = arrays["F"], arrays["null_hash"]
+        torch.cuda.synchronize(self.dev)                                 # (the spec arrays are there before the first launch)
+        self.stream = torch.cuda.Stream(self.dev)
+        self.event = torch.cuda.Event()
+        self.pin = self.dev_in = self.status_pin = None
+        self._relaxed = False
+
+    def staging(self, nbytes):
+        self._thread_setup()
+        if self.pin is None or self.pin.numel() < nbytes:
+            self.pin = self.torch.empty(max(nbytes, 2 * (self.pin.numel() if self.pin is not None else 0)),
+                                        dtype=self.torch.uint8).pin_memory()
+        return self.pin.numpy()[:nbytes]
+
+    def _thread_setup(self):
+        # this thread's copies, launches and waits must stay legal while the training thread captures a HIP graph
+        if not self._relaxed:
+            check(lib().rsx_thread_capture_relaxed_h(), "rsx_thread_capture_relaxed_h")
+            self._relaxed = True
+
+    def __call__(self, stage, n, tab, buf_bytes, verify_crc, rows, n_batches, stride, ids_off):
+        torch = self.torch
+        total = tab + buf_bytes
+        self._thread_setup()
+        with torch.cuda.device(self.dev), torch.cuda.stream(self.stream):
+            if self.dev_in is None or self.dev_in.numel() < total:
+                self.dev_in = torch.empty(max(total, 2 * (self.dev_in.numel() if self.dev_in is not None else 0)),
+                                          dtype=torch.uint8, device=self.dev)
+            if self.status_pin is None or self.status_pin.numel() < n:
+                self.status_pin = torch.empty(max(n, 4096), dtype=torch.int32).pin_memory()
+            self.dev_in[:total].copy_(self.pin[:total], non_blocking=True)
+            out = torch.empty(n_batches * stride, dtype=torch.uint8, device=self.dev)
+            status = torch.empty(n, dtype=torch.int32, device=self.dev)
+            base = self.dev_in.data_ptr()
+            check(lib().rsx_criteo_parse_records(base + tab, buf_bytes, base, base + 4 * n, n, C.byref(self.spec), int(verify_crc),
+                                                 out.data_ptr(), rows, stride, ids_off, status.data_ptr(),
+                                                 self.stream.cuda_stream), "rsx_criteo_parse_records")
+            self.status_pin[:n].copy_(status, non_blocking=True)
+            self.event.record(self.stream)
+        self.event.synchronize()
+        device_parse_stats["launches"] += 1
+        return out, self.status_pin.numpy()[:n].copy()
+
+    def put(self, out, off, flat):
+        """A host-parsed batch into its place of the chunk's output (the fallback)."""
+        torch = self.torch
+        self._thread_setup()
+        with torch.cuda.device(self.dev), torch.cuda.stream(self.stream):
+            out[off:off + flat.size].copy_(torch.from_numpy(flat).pin_memory(), non_blocking=True)
+            self.event.record(self.stream)
+        self.event.synchronize()
+
+    def close(self):
+        self.pin = self.dev_in = self.status_pin = self._spec_dev = None
+
+
+def _chunk_batches(chunk, F, parser, verify_crc, filenames, parse_step):
+    """One chunk of descriptors (all of `rows` rows) -> its batches, in order: stage the spans (int32 rec_off [n] | int32
+    rec_len [n] | the spans' bytes with their framing, each span 4-byte aligned), run the parse step, and hand out views of its
+    output; a batch with a declined record is parsed on the host instead."""
+    rows, nb = chunk[0][0], len(chunk)
+    n = rows * nb
+    o_ids, nbytes = _device_packing(rows, F)
+    stride = (nbytes + 255) & ~255
+    tab = (8 * n + 15) & ~15
+    total, plan = tab, []
+    for _, spans in chunk:
+        for mm, offs, lens in spans:
+            a, b = int(offs[0]) - 12, int(offs[-1] + lens[-1]) + 4
+            plan.append((mm, a, b, total, offs, lens))
+            total += (b - a + 3) & ~3
+    staging = getattr(parse_step, "staging", None)
+    stage = staging(total) if staging is not None else np.empty(total, np.uint8)
+    rec_off, rec_len = stage[:4 * n].view(np.int32), stage[4 * n:8 * n].view(np.int32)
+    k = 0
+    for mm, a, b, dst, offs, lens in plan:
+        stage[dst:dst + (b - a)] = mm[a:b]               # the ONE host copy of every byte
+        m = len(offs)
+        rec_off[k:k + m] = offs - (a - (dst - tab))
+        rec_len[k:k + m] = np.minimum(lens, 0x7fffffff)
+        k += m
+    out, status = parse_step(stage, n, tab, total - tab, verify_crc, rows, nb, stride, o_ids)
+    device_parse_stats["records"] += n
+    device_parse_stats["bytes"] += total
+    status = np.asarray(status).reshape(nb, rows)
+    host = isinstance(out, np.ndarray)
+    pack_key = ("criteo-device", rows, F)
+    for i, (_, spans) in enumerate(chunk):
+        if status[i].any():
+            flat = _host_batch(spans, rows, parser, verify_crc, filenames)
+            device_parse_stats["fallback_batches"] += 1
+            if host:
+                out[i * stride:i * stride + nbytes] = flat
+            else:
+                parse_step.put(out, i * stride, flat)
+        flat = out[i * stride:i * stride + nbytes]
+        if host:
+            label = flat[:rows * 4].view(np.float32).reshape(rows, 1)
+            ids = flat[o_ids:o_ids + rows * F * 4].view(np.int32).reshape(rows, F)
+        else:
+            import torch
+            label = flat[:rows * 4].view(torch.float32).view(rows, 1)
+            ids = flat[o_ids:o_ids + rows * F * 4].view(torch.int32).view(rows, F)
+        feats = DeviceFeatures(ids=ids)
+        feats.dev_flat, feats.pack_key = flat, pack_key
+        yield feats, label
+
+
+def _device_parse_batches(filenames, batch_size, num_epochs, layout, verify_crc, prefetch, chunk_batches, device, parse_step,
+                          shuffle):
+    """criteo_input_fn(device_parse=True): the default path's batch stream with the parse on the device.
+    The stream is defined by descriptors (_batch_descriptors; `shuffle` = (buffer, seed) runs _shuffled over THEM, so the
+    order of batches is the default path's).  A producer thread takes up to `chunk_batches` descriptors of equal row count (a
+    partial batch is a chunk of its own), stages and parses them (_chunk_batches) and hands the batches over, at most
+    `prefetch` of them ahead of the consumer.  When the consumer stops -- exhaustion, an error, close() or garbage collection of
+    this generator -- the `finally` below stops the thread, which drops the descriptors (their mappings) and the parse step's
+    buffers: nothing outlives the consumer."""
+    F = layout.F
+    parser = _CriteoParser(layout, 1)
+    own_step = parse_step is None
+    if own_step:
+        parse_step = _DeviceParseStep(layout, device)
+    chunk_batches = max(1, min(chunk_batches, prefetch))
+    desc = _batch_descriptors(filenames, batch_size, num_epochs)
+    if shuffle is not None:
+        desc = _shuffled(desc, shuffle[0], shuffle[1])
+    q = queue.Queue()
+    end = object()
+    stop = threading.Event()
+    credits = threading.Semaphore(prefetch)            # one per batch that is parsed (or being parsed) and not yet consumed
+
+    def acquire(k):
+        for _ in range(k):
+            while not credits.acquire(timeout=0.05):
+                if stop.is_set():
+                    return False
+        return not stop.is_set()
+
+    def work():
+        try:
+            pend, done = None, False
+            while not stop.is_set() and not (done and pend is None):
+                chunk, pend = ([pend] if pend is not None else []), None
+                while not done and len(chunk) < chunk_batches:
+                    d = next(desc, None)
+                    if d is None:
+                        done = True
+                    elif chunk and d[0] != chunk[0][0]:
+                        pend = d
+                        break
+                    else:
+                        chunk.append(d)
+                if not chunk:
+                    continue
+                if not acquire(len(chunk)):
+                    return
+                for b in _chunk_batches(chunk, F, parser, verify_crc, filenames, parse_step):
+                    q.put(b)
+                del chunk
+            q.put(end)
+        except BaseException as e:  # surfaced in the consumer
+            q.put(e)
+        finally:
+            desc.close()
+            if own_step:
+                parse_step.close()
+
+    t = threading.Thread(target=work, daemon=True, name="rsx-device-parse")
+    t.start()
+    try:
+        while True:
+            x = q.get()
+            if x is end:
+                return
+            if isinstance(x, BaseException):
+                raise x
+            credits.release()
+            flat = x[0].dev_flat
+            if not isinstance(flat, np.ndarray):
+                # allocated on the producer's stream, about to be read on the consumer's: the allocator must not hand the memory
+                # out again before that stream is done with it (PackedBatch records the stream that adopts it as well)
+                import torch
+                flat.record_stream(torch.cuda.current_stream(flat.device))
+            yield x
+    finally:
+        stop.set()
+        t.join(timeout=5.0)
+        while not q.empty():                            # batches parsed ahead go with the consumer
+            q.get_nowait()
+
+
 RSX_SHARD_TAIL = 2      # include/rsx.h: value of drop_remainder
 
 
@@ -264,15 +576,25 @@ def _shard_tail(shard_tail, num_epochs, need_shuffle):
 
 
 def criteo_input_fn(filenames, batch_size, num_epochs=-1, need_shuffle=False, num_parallel=8, layout=None,
-                    shuffle_buffer=1000, prefetch=16, seed=0, shard=None, verify_crc=True, shard_tail=False):
+                    shuffle_buffer=1000, prefetch=16, seed=0, shard=None, verify_crc=True, shard_tail=False,
+                    device_parse=False, device=None, parse_chunk_batches=8, parse_step=None):
     """fm/fm.py:106-112.  Returns an iterator of (features, labels).
     shard=(rank, world): this replica's share of the batch stream (see csrc/tfrecord_reader.cpp); each replica then
     shuffles its own sub-stream with its own seed.  `prefetch` = batches the C++ reader keeps in flight.
-    shard_tail (default False; evaluation passes True): see _shard_tail."""
+    shard_tail (default False; evaluation passes True): see _shard_tail.
+    device_parse (default False: nothing changes): the shards' raw bytes go to `device` and rsx_criteo_parse_records parses
+    `parse_chunk_batches` batches per launch (see _device_parse_batches); the batches are device tensors, `ids` and labels
+    only (no `cont_log`), in the same order and with the same bits as the default path.  Single replica only.
+    parse_step: the chunk parse as a callable (tests run the stream on numpy buffers with the kernel's host twin)."""
     if layout is None:
         from .feature_columns import CriteoLayout, build_feature_columns
         layout = CriteoLayout.from_columns(build_feature_columns(16)[1])
     rank, world = _shard_from_env(shard)
+    if device_parse:
+        check_device_parse(layout=layout, world=world)
+        return _device_parse_batches(list(filenames), int(batch_size), int(num_epochs), layout, bool(verify_crc),
+                                     max(1, int(prefetch)), max(1, int(parse_chunk_batches)), device, parse_step,
+                                     (shuffle_buffer, seed) if need_shuffle else None)
     it = _criteo_batches(list(filenames), batch_size, num_epochs, layout, num_parallel, (rank, world), verify_crc,
                          max(2, prefetch), drop_remainder=_shard_tail(shard_tail, num_epochs, need_shuffle) if world > 1 else 0)
     if need_shuffle:

@@ -13,7 +13,8 @@ import torch
 from . import fused_step
 from . import layers as L
 from .deepfm import define_flags as _deepfm_flags
-from .deepfm import input_fn, run_main  # noqa: F401
+from .deepfm import input_fn as _deepfm_input_fn
+from .deepfm import run_main  # noqa: F401
 from .estimator import EstimatorSpec, ModeKeys, get_variable_store
 from .feature_columns import CriteoLayout, build_feature_columns
 from . import _lib
@@ -281,6 +282,15 @@ def model_fn(features, labels, mode, params):
             store.minimize(loss)
         return EstimatorSpec(mode, predictions=predictions, loss=loss, train_op=train_op)
     return EstimatorSpec(mode, predictions=predictions, loss=loss, eval_metric_ops={"AUC": None, "Accuracy": None})
+
+
+def input_fn(*args, device_parse=False, **kwargs):
+    """deepfm.input_fn; the device parse is refused: the linear part consumes the `cont_log` values themselves, which the
+    device batches do not carry."""
+    if device_parse:
+        from .input_pipeline import check_device_parse
+        check_device_parse(model="xdeepfm")
+    return _deepfm_input_fn(*args, **kwargs)
 
 
 def default_cin_split():
