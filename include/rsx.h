@@ -798,6 +798,32 @@ int rsx_predict_din_rank(const rsx_predict_din_model* model_h, const int32_t* hi
                          rsx_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Top-k over rows of fp32 scores, merged with a running list kept on the device: for each of U rows, the k best of the
+ * row's n scores and of the row's list from earlier calls, written as (value, index) pairs in final order.  Generic over
+ * score rows (serving: behind rsx_predict_din_rank, once per chunk of a long request).
+ * ORDER -- a total order, and the contract: a higher score comes first; equal scores go by the lower index, -0.0 and +0.0
+ * compare equal; every NaN ranks below every number, NaNs by lower index among themselves.  This is
+ * np.lexsort((index, -score)).  The values written are the input's bits (a -0.0 stays -0.0, a NaN keeps its payload).
+ * STATE on the device, no per-call host argument (replayable from a hipGraph, like the optimizer's step word): per row
+ * state[u] = {filled, next_index}.  The call treats the first `filled` entries of out_val[u] / out_idx[u] as the running list,
+ * gives the n new scores the indices next_index .. next_index + n - 1, writes the best min(k, filled + n) of the union, and
+ * stores filled = min(k, filled + n), next_index += n.  Entries past `filled` are unspecified.  The host zeroes `state` when a
+ * request starts; k must stay the same over the calls of a request, and next_index + n below 2^31 - 1.  A `filled` outside
+ * [0, k] is clamped into it.
+ * ONE workgroup per row: it reads the row's running list before it writes, so the update is in place without a workspace, a
+ * grid-wide step or floating-point atomics, and a row's output depends on its scores and its state only -- not on U or on the
+ * other rows.  Method: 64-bit keys (order-preserving image of the score | ~index) in LDS, an MSB-first radix select of the
+ * k-th key over integer LDS histograms, the survivors ranked by counting.  Deterministic.
+ * scores: row u at scores + u * ld (ld >= n; the padding is never read).  out_val / out_idx: [U, k].
+ * RSX_EINVAL (before any HIP call): a NULL pointer, U / n / k <= 0, ld < n.  Envelope (rsx_topk_rows_supported;
+ * RSX_EUNSUPPORTED outside, before any HIP call): 1 <= k <= 1024 and n + k <= 16384 (a longer row is fed in slices: the running
+ * list carries over).
+ * ------------------------------------------------------------------------------------------- */
+int rsx_topk_rows_supported(int n, int k);
+int rsx_topk_rows(const float* scores, int ld, int U, int n, int k, float* out_val, int32_t* out_idx, int32_t* state,
+                  rsx_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
  * DCN cross layers, dcn/dcn.py:132-142: x_{l+1} = (x_l . w_l) * x0 + x_l + b_l, all L
  * layers fused per example.  dim % 4 == 0, dim <= 1024, L <= 8.
  * ------------------------------------------------------------------------------------------- */

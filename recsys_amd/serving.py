@@ -36,6 +36,11 @@ The reference exports a SavedModel whose serving signature parses serialized `tf
                                 rebuilt Estimator's store keeps them; the history is shipped and fetched once, not C times.
               rank_path == "layers": outside that kernel's envelope -- the request expanded on the host to the training-shaped
                                 batch (`expand_rank_request`) and answered through `predict`.
+              `rank_candidates(..., top_k=k)` returns the k best candidates only, {"prob", "index"} in the order of
+              `topk_rows_host`.  topk_path_for(k) == "device" (rank_path == "fused", k <= 1024): rsx_topk_rows (csrc/topk.hip) behind
+              every chunk's rank launch keeps the running list on the device, one copy of k pairs ends the request;
+              "host": the probabilities as without top_k, then `topk_rows_host`.  The same bits either way.  (`topk_path`
+              records where the latest such request selected.)
 """
 import ctypes as C
 import importlib
@@ -455,6 +460,33 @@ def check_rank_request(u_iid_seq, u_icat_seq, i_id, i_cate, hist_len, n_item, n_
     return U, C, Pq, nd == 1
 
 
+TOPK_MAX_K = 1024                     # include/rsx.h rsx_topk_rows: the largest k selected on the device
+
+
+def check_top_k(top_k):
+    """`rank_candidates`' top_k argument -> int; RsxError unless it is an integer (Python or numpy, no bool) >= 1."""
+    if isinstance(top_k, (bool, np.bool_)) or not isinstance(top_k, (int, np.integer)) or int(top_k) < 1:
+        raise _lib.RsxError("rank_candidates: top_k must be an integer >= 1, not %r" % (top_k,))
+    return int(top_k)
+
+
+def topk_rows_host(prob, k):
+    """The k best entries of every row of `prob` ([C] or [U, C], float32) in the order of rsx_topk_rows (include/rsx.h): a
+    higher value first, equal values (-0.0 == +0.0) by the lower index, every NaN after every number and NaNs by index --
+    np.lexsort((index, -value)).  -> {'prob': float32 [k'] / [U, k'] (the input's bits), 'index': int32, same shape},
+    k' = min(k, C).  Pure numpy: the host form of `rank_candidates(top_k=k)` and the checker of the device form."""
+    k = check_top_k(k)
+    a = np.asarray(prob, np.float32)
+    if a.ndim not in (1, 2) or a.shape[-1] < 1:
+        raise _lib.RsxError("topk_rows_host: expected scores [C] or [U, C] with C >= 1, got %s" % (a.shape,))
+    rows = np.atleast_2d(a)
+    kk = min(k, rows.shape[1])
+    index = np.broadcast_to(np.arange(rows.shape[1], dtype=np.int64), rows.shape)
+    order = np.lexsort((index, -rows), axis=-1)[:, :kk]
+    out = {"prob": np.take_along_axis(rows, order, 1), "index": order.astype(np.int32)}
+    return out if a.ndim == 2 else {key: v[0] for key, v in out.items()}
+
+
 # ---- Predictor ---------------------------------------------------------------------------------------------------------------
 class Predictor:
     """An exported model ready to answer requests.  See the module docstring for the two paths.  `table_dtype` is the
@@ -514,9 +546,11 @@ class Predictor:
         if device_parse:
             self._device_parse_setup(int(parse_row_bytes))
         self.rank_path = None
+        self.topk_path = None               # where the latest `rank_candidates(top_k=k)` selected (before any: a small k)
         self._rank = None
         if self.script == "din":
             self.rank_path = "fused" if self._rank_supported() else "layers"
+            self.topk_path = "device" if self.rank_path == "fused" else "host"
         return self
 
     # -- the one-launch path ----------------------------------------------------------------------------------------------
@@ -765,19 +799,90 @@ class Predictor:
             # request buffers of one chunk: the histories [U, P], the candidates and their probabilities [U, max_candidates]
             # (a request of fewer users or candidates uses leading parts of them; graphs captured over smaller buffers go)
             dev, i32 = self.device, torch.int32
-            for k in [k for k in self._graphs if isinstance(k, tuple) and k[0] == "rank"]:
-                del self._graphs[k]
-                self._n_graphs -= 1
+            self._drop_graphs("rank", "rank_topk")
+            r.pop("topk", None)
             r["hist"] = [torch.zeros(U * P, dtype=i32, device=dev) for _ in range(2)]
             r["cand"] = [torch.zeros(U * self.max_candidates, dtype=i32, device=dev) for _ in range(2)]
             r["prob"] = torch.zeros(U * self.max_candidates, dtype=torch.float32, device=dev)
             r["U"] = U
         return r
 
-    def rank_buffer_bytes(self, U=1):
-        """Bytes of the static request buffers `rank_candidates` holds for U users."""
+    def _drop_graphs(self, *kinds):
+        """Forgets the captured graphs of these key kinds (their static buffers are about to be replaced)."""
+        for k in [k for k in self._graphs if isinstance(k, tuple) and k[0] in kinds]:
+            del self._graphs[k]
+            self._n_graphs -= 1
+
+    def rank_buffer_bytes(self, U=1, top_k=None):
+        """Bytes of the static request buffers `rank_candidates` holds for U users; with top_k, those of a request that
+        selects on the device included (out_val and out_idx [U, k], state [U, 2])."""
         P = self._din_sizes()[0]
-        return 4 * (2 * U * P + 3 * U * self.max_candidates)
+        n = 4 * (2 * U * P + 3 * U * self.max_candidates)
+        if top_k is not None and self._topk_on_device(check_top_k(top_k)):
+            n += 4 * (2 * U * int(top_k) + 2 * U)
+        return n
+
+    # -- top-k of a ranking request, selected on the device (csrc/topk.hip) ---------------------------------------------------
+    def _topk_on_device(self, k):
+        return self.rank_path == "fused" and k <= TOPK_MAX_K and bool(_lib.lib().rsx_topk_rows_supported(1, k))
+
+    def topk_path_for(self, top_k):
+        """Where `rank_candidates(..., top_k=top_k)` selects on this Predictor: "device" or "host" (None for a bundle that
+        ranks no candidates).  A pure function of the bundle and k; `topk_path` only records what the latest request took."""
+        if self.script != "din":
+            return None
+        return "device" if self._topk_on_device(check_top_k(top_k)) else "host"
+
+    def _topk_setup(self, U, k):
+        """The static buffers of the selection beside the rank buffers: one flat buffer that holds out_val [U, k] and, behind
+        it, out_idx [U, k] of the request at hand (so both come back in ONE copy), and state [U, 2].  Reallocated like the
+        rank buffers: when a request needs more than they hold (the graphs captured over the smaller ones go)."""
+        import torch
+        r = self._rank
+        t = r.get("topk")
+        if t is None or r["U"] * k > t["pairs"]:
+            self._drop_graphs("rank_topk")
+            t = r["topk"] = {"pairs": r["U"] * k,
+                             "buf": torch.zeros(2 * r["U"] * k, dtype=torch.float32, device=self.device),
+                             "state": torch.zeros(2 * r["U"], dtype=torch.int32, device=self.device)}
+        return t
+
+    def _rank_topk_launch(self, U, n, k):
+        """The rank launch of one chunk, then the selection over its probabilities: one launch, or -- when n + k is beyond
+        rsx_topk_rows' envelope (n + k > 16 384) -- one per slice of the chunk, the chunk halved until a slice fits (the running
+        list carries over; n = 16 000 with k = 1 024: two slices of 8 000, three launches for the chunk)."""
+        import torch
+        self._rank_launch(U, n)
+        r = self._rank
+        t, L = r["topk"], _lib.lib()
+        step = n
+        while not L.rsx_topk_rows_supported(step, k):
+            step = (step + 1) // 2
+        for s in range(0, n, step):
+            _lib.check(L.rsx_topk_rows(r["prob"].data_ptr() + 4 * s, int(n), int(U), min(step, n - s), int(k), t["buf"].data_ptr(),
+                                       t["buf"].data_ptr() + 4 * U * k, t["state"].data_ptr(),
+                                       torch.cuda.current_stream().cuda_stream), "rsx_topk_rows")
+
+    def _rank_topk_device(self, U, Cn, P, Pq, k, u_iid_seq, u_icat_seq, i_id, i_cate):
+        """-> (prob [U, k'], index [U, k']): per chunk the rank launch and the selection in one graph, nothing fetched until
+        the request's last chunk is in."""
+        import torch
+        kk = min(k, Cn)
+        with torch.no_grad():
+            r = self._rank_setup(U)
+            t = self._topk_setup(U, k)
+            self._rank_histories(r, U, P, Pq, u_iid_seq, u_icat_seq)
+            t["state"].zero_()
+            ci, cc = self._dev32(i_id, U), self._dev32(i_cate, U)
+            for s in range(0, Cn, self.max_candidates):
+                e = min(Cn, s + self.max_candidates)
+                n = e - s
+                r["cand"][0][:U * n].view(U, n).copy_(ci[:, s:e], non_blocking=True)
+                r["cand"][1][:U * n].view(U, n).copy_(cc[:, s:e], non_blocking=True)
+                self._run(("rank_topk", U, n, k), lambda: self._rank_topk_launch(U, n, k))
+            h = t["buf"][:2 * U * k].cpu().numpy()                     # the ONE device-to-host copy of the request
+        return (np.ascontiguousarray(h[:U * k].reshape(U, k)[:, :kk]),
+                np.ascontiguousarray(h[U * k:].view(np.int32).reshape(U, k)[:, :kk]))
 
     def _rank_launch(self, U, n):
         import torch
@@ -797,37 +902,60 @@ class Predictor:
         self._run(("rank", U, n), lambda: self._rank_launch(U, n))
         return r["prob"][:U * n].view(U, n)
 
-    def rank_candidates(self, u_iid_seq, u_icat_seq, i_id, i_cate):
+    @staticmethod
+    def _dev32(x, rows):
+        import torch
+        if isinstance(x, torch.Tensor):
+            return x.reshape(rows, -1).to(torch.int32)
+        return torch.from_numpy(np.ascontiguousarray(np.asarray(x).reshape(rows, -1), np.int32))
+
+    def _rank_histories(self, r, U, P, Pq, u_iid_seq, u_icat_seq):
+        """The request's histories into the static buffers, zero padded to the bundle's hist_len."""
+        for buf, x in zip(r["hist"], (u_iid_seq, u_icat_seq)):
+            hv = buf[:U * P].view(U, P)
+            if Pq:
+                hv[:, :Pq].copy_(self._dev32(x, U), non_blocking=True)
+            if Pq < P:
+                hv[:, Pq:].zero_()
+
+    def rank_candidates(self, u_iid_seq, u_icat_seq, i_id, i_cate, top_k=None):
         """din.py bundles: score C candidate items against ONE user's behaviour history -- histories [P'], candidates [C] ->
         {'prob': float32 numpy [C]} -- or U users with C candidates each: histories [U, P'], candidates [U, C] -> prob [U, C].
-        P' <= the bundle's hist_len (shorter histories are zero padded).  numpy or torch, host or device, any integer dtype."""
+        P' <= the bundle's hist_len (shorter histories are zero padded).  numpy or torch, host or device, any integer dtype.
+        top_k=k (an integer >= 1): only the k' = min(k, C) best candidates of every user -> {'prob': float32 [k'] / [U, k'],
+        'index': int32, same shape: positions on the request's candidate axis}, in the order of `topk_rows_host` (higher
+        probability first, equal ones by the lower position).  `topk_path_for(k)` says where a request with that k selects
+        (ask it before the call; `topk_path` records where the LATEST such request did):
+        "device" (rank_path == "fused" and k <= 1024): rsx_topk_rows behind every chunk's rank launch, in the chunk's graph,
+        the running list on the device and ONE copy of k' pairs at the end of the request; "host": the probabilities as
+        without top_k, then `topk_rows_host`.  Both give the same bits."""
         import torch
         if getattr(self, "script", None) != "din":
             raise _lib.RsxError("rank_candidates: only din.py bundles rank candidates against a history; this bundle is %s.py"
                                 % getattr(self, "script", None))
         P, n_item, n_cate, _ = self._din_sizes()
         U, Cn, Pq, single = check_rank_request(u_iid_seq, u_icat_seq, i_id, i_cate, P, n_item, n_cate)
+        if top_k is not None:
+            k = check_top_k(top_k)
+            if self._topk_on_device(k):
+                self.topk_path = "device"
+                prob, index = self._rank_topk_device(U, Cn, P, Pq, k, u_iid_seq, u_icat_seq, i_id, i_cate)
+                out = {"prob": prob, "index": index}
+            else:
+                self.topk_path = "host"
+                out = topk_rows_host(self.rank_candidates(u_iid_seq, u_icat_seq, i_id, i_cate)["prob"].reshape(U, Cn), k)
+            return {key: v[0] for key, v in out.items()} if single else out
         shape = (Cn,) if single else (U, Cn)
         if self.rank_path != "fused":
             host = [x.detach().cpu().numpy() if isinstance(x, torch.Tensor) else np.asarray(x)
                     for x in (u_iid_seq, u_icat_seq, i_id, i_cate)]
             return {"prob": self.predict(expand_rank_request(*host, hist_len=P))["prob"].reshape(shape)}
 
-        def dev32(x, rows):
-            if isinstance(x, torch.Tensor):
-                return x.reshape(rows, -1).to(torch.int32)
-            return torch.from_numpy(np.ascontiguousarray(np.asarray(x).reshape(rows, -1), np.int32))
-
         out = np.empty((U, Cn), np.float32)
         with torch.no_grad():
             r = self._rank_setup(U)
-            for buf, x in zip(r["hist"], (u_iid_seq, u_icat_seq)):
-                hv = buf[:U * P].view(U, P)
-                if Pq:
-                    hv[:, :Pq].copy_(dev32(x, U), non_blocking=True)
-                if Pq < P:
-                    hv[:, Pq:].zero_()
-            ci, cc = dev32(i_id, U), dev32(i_cate, U)
+            self._rank_histories(r, U, P, Pq, u_iid_seq, u_icat_seq)
+            ci, cc = self._dev32(i_id, U), self._dev32(i_cate, U)
             for s in range(0, Cn, self.max_candidates):
                 e = min(Cn, s + self.max_candidates)
                 out[:, s:e] = self._rank_chunk(U, ci[:, s:e], cc[:, s:e]).cpu().numpy()

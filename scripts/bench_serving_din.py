@@ -18,6 +18,17 @@ can answer it, in ONE process, their timed regions alternating, `--repeats` roun
         the kernel's time against the sum of A's kernels per request (every other kernel the trace holds at least once per
         request, the runtime's buffer copies left out), and its achieved FLOP/s against the fp32 MFMA peak.
 
+  --top_k K  the request that ends in the K best candidates, C = 200 / 4096 / 63001 (the whole catalogue, 16 chunks at the default
+     max_candidates of 4096) unless --sizes says otherwise, the same protocol (one process, the contenders alternating,
+     medians and spread of --repeats rounds):
+       A  rank_candidates(...)["prob"] (a blocking copy of every chunk's probabilities), then the fastest host selection with
+          the order of serving.topk_rows_host: np.partition for the K-th value, a stable sort of the survivors;
+       B  rank_candidates(..., top_k=K): rsx_topk_rows (csrc/topk.hip) behind every chunk's rank launch, one copy of K pairs.
+     wall time host to host; device time = hipEvents around replays of the request's captured chunk graphs (B: with the
+     state's zeroing in front) over the static buffers as one request of that size left them: the request's own history, the
+     candidates of its last chunk.  With --profile-run C: eager B requests for a kernel trace of its own, and --kernel-stats
+     prints the selection launch's time next to the rank launch's.
+
 FLOPs of a request, from shapes: 2 x C x valid positions x (K x 80 + 80 x 40 + 40) per attention (the folded first layer), both
 attentions; the user-side and candidate-side terms and the tower are not counted."""
 import argparse
@@ -93,6 +104,107 @@ def capture_both(pred, req):
     return ga[0]["graph"], pred._graphs[("rank", 1, C)]["graph"], err
 
 
+def host_select(prob, k):
+    """The k best of prob [C] in the order of serving.topk_rows_host (no NaN among probabilities): np.partition for the k-th
+    value, every entry >= it in index order, a stable sort of those survivors (ties keep the lower index)."""
+    C = len(prob)
+    kk = min(k, C)
+    thr = np.partition(prob, C - kk)[C - kk]
+    cand = np.flatnonzero(prob >= thr)
+    order = cand[np.argsort(-prob[cand], kind="stable")][:kk]
+    return {"prob": prob[order], "index": order.astype(np.int32)}
+
+
+def host_select_argpartition(prob, k):
+    """The same answer from np.argpartition.  Its k picks are right except inside the tie group of the k-th value, where it may
+    take any members: those are replaced by the group's lowest indices, then the picks go through the same stable sort."""
+    C = len(prob)
+    kk = min(k, C)
+    pick = np.argpartition(-prob, kk - 1)[:kk] if kk < C else np.arange(C)
+    thr = prob[pick].min()
+    above = pick[prob[pick] > thr]
+    cand = np.sort(np.concatenate([above, np.flatnonzero(prob == thr)[:kk - len(above)]]))
+    order = cand[np.argsort(-prob[cand], kind="stable")]
+    return {"prob": prob[order], "index": order.astype(np.int32)}
+
+
+def topk_a(pred, req, k):
+    return host_select(pred.rank_candidates(*req)["prob"], k)
+
+
+def topk_b(pred, req, k):
+    return pred.rank_candidates(*req, top_k=k)
+
+
+def time_request_graphs(pred, graphs, n, zero_state):
+    """us per request of replaying the captured graphs of a request's chunks (over the resident inputs of the last chunk)."""
+    import torch
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    state = pred._rank["topk"]["state"] if zero_state else None
+    torch.cuda.synchronize()
+    e0.record()
+    for _ in range(n):
+        if state is not None:
+            state.zero_()
+        for g in graphs:
+            g.replay()
+    e1.record()
+    e1.synchronize()
+    return e0.elapsed_time(e1) * 1e3 / n
+
+
+def bench_topk(pred, sizes, k, a):
+    out = []
+    reqs = {C: request(C, 100 + C) for C in sizes}
+    graphs = {}
+    for C in sizes:                                        # every size warmed up and captured before any timing
+        for _ in range(3):
+            ra, rb = topk_a(pred, reqs[C], k), topk_b(pred, reqs[C], k)
+        assert pred.topk_path == "device"
+        assert np.array_equal(ra["index"], rb["index"]) and np.array_equal(ra["prob"].view(np.uint32), rb["prob"].view(np.uint32)), C
+        ns = [min(pred.max_candidates, C - s) for s in range(0, C, pred.max_candidates)]
+        graphs[C] = ([pred._graphs[("rank", 1, n)]["graph"] for n in ns], [pred._graphs[("rank_topk", 1, n, k)]["graph"] for n in ns])
+    for C in sizes:
+        ga, gb = graphs[C]
+        # the replays run over whatever the static buffers hold: make that THIS request (its history decides the rank kernel's
+        # time; the candidates are those of its last chunk), once for each contender's timed region below
+        topk_a(pred, reqs[C], k)
+        topk_b(pred, reqs[C], k)
+        nrep = max(20, min(a.replays, int(5e5 / max(time_request_graphs(pred, gb, 10, True), 1.0))))
+        nw = max(10, min(a.wall_calls, nrep))
+        ta, tb, wa, wb = [], [], [], []
+        for _ in range(a.repeats):                         # the contenders alternate within every round
+            ta.append(time_request_graphs(pred, ga, nrep, False))
+            tb.append(time_request_graphs(pred, gb, nrep, True))
+        for _ in range(a.repeats):
+            wa.append(time_wall(lambda p, r: topk_a(p, r, k), pred, reqs[C], nw))
+            wb.append(time_wall(lambda p, r: topk_b(p, r, k), pred, reqs[C], nw))
+        prob = pred.rank_candidates(*reqs[C])["prob"]
+        sel_us = {}
+        for fn in (host_select, host_select_argpartition):  # A uses the first; the second is the form the other way round
+            assert np.array_equal(fn(prob, k)["index"], host_select(prob, k)["index"])
+            t = []
+            for _ in range(a.repeats):
+                t0 = time.perf_counter()
+                for _ in range(50):
+                    fn(prob, k)
+                t.append((time.perf_counter() - t0) / 50 * 1e6)
+            sel_us[fn.__name__] = round(float(np.median(t)), 1)
+        med = lambda x: float(np.median(x))
+        spread = lambda x: max(x) - min(x)
+        rec = {"candidates": C, "top_k": k, "chunks": len(ga),
+               "A_device_us": round(med(ta), 3), "B_device_us": round(med(tb), 3), "device_B_minus_A_us": round(med(tb) - med(ta), 3),
+               "A_device_repeats_us": [round(x, 3) for x in ta], "B_device_repeats_us": [round(x, 3) for x in tb],
+               "A_wall_us": round(med(wa), 1), "B_wall_us": round(med(wb), 1), "wall_B_over_A": round(med(wb) / med(wa), 4),
+               "A_wall_repeats_us": [round(x, 1) for x in wa], "B_wall_repeats_us": [round(x, 1) for x in wb],
+               "wall_accepted": bool(med(wa) - med(wb) > max(spread(wa), spread(wb))),
+               "A_host_selection_us": sel_us["host_select"], "argpartition_selection_us": sel_us["host_select_argpartition"],
+               "history_valid_positions": int((reqs[C][0] > 0).sum()), "replays": nrep, "wall_calls": nw}
+        out.append(rec)
+        print(json.dumps(rec), flush=True)
+    return out
+
+
 def time_replays(graph, n):
     import torch
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -137,7 +249,20 @@ def main():
     p.add_argument("--profile-run", dest="profile_run", type=int, default=0, help="C of a rocprofv3 run")
     p.add_argument("--profile-requests", dest="profile_requests", type=int, default=200)
     p.add_argument("--kernel-stats", dest="kernel_stats", default=None)
+    p.add_argument("--top_k", type=int, default=0, help="compare the top-k request: host selection against rank_candidates(top_k=K)")
+    p.add_argument("--max_candidates", type=int, default=4096, help="--top_k: candidates per rank launch")
     a = p.parse_args()
+    if a.kernel_stats and a.top_k:                # the selection launch next to the rank launch, from the trace
+        st = kernel_stats(a.kernel_stats)
+        rec = {"candidates": a.profile_run, "top_k": a.top_k}
+        for tag, kern in (("topk", "topk_rows_k"), ("rank", B_KERNEL)):
+            c = [(c, avg) for name, (c, t, avg) in st.items() if kern in name]
+            if not c or not sum(x[0] for x in c):
+                sys.exit("%s holds no launch of %s: was the trace taken with --top_k %d --profile-run C on a Predictor whose "
+                         "topk_path is \"device\"?" % (a.kernel_stats, kern, a.top_k))
+            rec[tag + "_calls"], rec[tag + "_kernel_us"] = sum(x[0] for x in c), round(sum(x[0] * x[1] for x in c) / sum(x[0] for x in c) / 1e3, 3)
+        print(json.dumps(rec), flush=True)
+        return rec
     if a.kernel_stats:                            # no GPU needed: the trace's own numbers
         C, n = a.profile_run, a.profile_requests
         st = kernel_stats(a.kernel_stats)
@@ -161,9 +286,20 @@ def main():
     from recsys_amd import build as _b
     _b.build(verbose=False)
     dev = torch.device("cuda")
+    if a.top_k and a.sizes == p.get_default("sizes"):
+        a.sizes = "200,4096,63001"
     sizes = [int(s) for s in a.sizes.split(",")] if not a.profile_run else [a.profile_run]
     with tempfile.TemporaryDirectory() as tmp:
-        pred = build(dev, max(sizes), os.path.join(tmp, "export"))
+        pred = build(dev, a.max_candidates if a.top_k else max(sizes), os.path.join(tmp, "export"))
+    if a.top_k and a.profile_run:
+        pred.use_hip_graph = False                                      # eager: the launches appear in the trace under their names
+        req = request(a.profile_run, 100 + a.profile_run)
+        for _ in range(a.profile_requests):
+            topk_b(pred, req, a.top_k)
+        torch.cuda.synchronize()
+        return None
+    if a.top_k:
+        return bench_topk(pred, sizes, a.top_k, a)
     if a.profile_run:
         pred.use_hip_graph = pred._est.config.use_hip_graph = False     # eager: every launch appears in the trace under its name
         req = request(a.profile_run, 100 + a.profile_run)
