@@ -1417,6 +1417,38 @@ int rsx_eval_metrics_state_words(int num_thresholds);
 int rsx_eval_metrics_update(const float* prob, const float* labels, const float* thresholds, int num_thresholds,
                             const float* batch_loss, uint64_t* state, int B, rsx_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Exact, tie-aware ROC AUC (csrc/auc_exact.hip): the rank statistic of sklearn.metrics.roc_auc_score, which the reference's
+ * serving client reports (deepfm/grpc_client.py:84), over the probabilities and labels the eval_metric_ops of
+ * fm/fm.py:150-153 see.  Opt-in, beside rsx_eval_metrics_update's 200-threshold tf.metrics.auc (which it never changes).
+ * Definition, in integers.  positive: label > 0.5f.  valid: 0 <= p <= 1 (-0.0 is +0.0; NaN, infinities and everything
+ * else are invalid).  A valid example is the 32-bit key (bits(p) << 1) | positive -- at most 0x7F000001, unsigned key order is
+ * score order, negatives in front of positives within one score, subnormals distinct -- an invalid one the padding key
+ * 0xFFFFFFFF (counted, sorted to the end, no part in the statistic).  With P positives and N negatives among the valid keys
+ *   U2 = sum over positives of (2 * #{negatives with a smaller score} + #{negatives with the same score}),
+ *   AUC = U2 / (2 P N), taken by the host from the integers (nan when P N == 0).
+ * The words depend on neither batch sizes, batch order nor the order threads run in (integer atomics only).
+ * The caller owns keys, workspace and output; nothing is allocated and nothing synchronises.
+ *   rsx_auc_exact_append    one launch per eval batch: n keys to keys_at_offset[0 .. n) (the host names the slot: batch
+ *                           sizes are host-side), the batch's invalid count added to counters[0] (device, zeroed by the caller)
+ *                           with one integer atomic per workgroup.  n == 0 is a no-op.
+ *   rsx_auc_exact_finalize  sorts keys[0 .. n) in place (a multi-workgroup LSD radix sort, 4 passes of 8 bits through
+ *                           `workspace`; the buffer ends holding the same multiset, ascending, so appending may continue) and
+ *                           reduces them to out[4] = {U2, P, N, invalid} (device).  keys and workspace 16-byte aligned,
+ *                           workspace_bytes >= rsx_auc_exact_workspace_bytes(n) =
+ *                           round_up(4 n, 256) + 1032 * ceil(n / tile) + 4096.  n == 0 gives four zeros.
+ *   rsx_auc_exact_tile      keys per workgroup tile of the sort and of the reduction (4096)
+ *   rsx_auc_exact_max_keys  the cap on n (2^27: a full Criteo test split fits)
+ * RSX_EINVAL (before any HIP call): a NULL pointer, n < 0 or above the cap, a misaligned buffer, a workspace too small.
+ * rsx_auc_exact_workspace_bytes returns 0 for such an n. */
+int rsx_auc_exact_tile(void);
+int64_t rsx_auc_exact_max_keys(void);
+size_t rsx_auc_exact_workspace_bytes(int64_t n);
+int rsx_auc_exact_append(const float* prob, const float* labels, int64_t n, uint32_t* keys_at_offset, uint64_t* counters,
+                         rsx_stream_t stream);
+int rsx_auc_exact_finalize(uint32_t* keys, int64_t n, void* workspace, size_t workspace_bytes, uint64_t* out,
+                           rsx_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

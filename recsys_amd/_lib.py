@@ -401,6 +401,11 @@ _SIGS = {
     "rsx_fingerprint64_dev_h": (C.c_uint64, [_P, C.c_size_t]),
     "rsx_eval_metrics_state_words": (_I, [_I]),
     "rsx_eval_metrics_update": (_I, [_P, _P, _P, _I, _P, _P, _I, _P]),
+    "rsx_auc_exact_tile": (_I, []),
+    "rsx_auc_exact_max_keys": (C.c_int64, []),
+    "rsx_auc_exact_workspace_bytes": (C.c_size_t, [C.c_int64]),
+    "rsx_auc_exact_append": (_I, [_P, _P, C.c_int64, _P, _P, _P]),
+    "rsx_auc_exact_finalize": (_I, [_P, C.c_int64, _P, C.c_size_t, _P, _P]),
 }
 
 _lib = None

@@ -218,6 +218,10 @@ def define_flags(p=None):
                    help="parse the TFRecord shards on the GPU (input_pipeline.criteo_input_fn(device_parse=True)): the host ships "
                         "raw shard bytes; same batches, same bits.  Single-replica fm.py / deepfm.py / dcn.py with the Criteo "
                         "feature set only")
+    p.add_argument("--exact_auc", type=lambda s: s.lower() in ("1", "true", "yes"), default=False,
+                   help="evaluate() also reports AUC_exact, the exact tie-aware ROC AUC (sklearn's roc_auc_score, "
+                        "deepfm/grpc_client.py:84) from a key sort on the GPU; the 200-threshold AUC stays as it is.  Single "
+                        "replica only")
     p.add_argument("--feature_set", default="criteo", choices=["criteo", "uid_iid"],
                    help="criteo: the 39-field pipeline of fm.py (BASELINE configs); uid_iid: deepfm.py as committed "
                         "(int64 u_id / i_id hashed into 500000 / 100000 buckets, int64 label)")
@@ -305,7 +309,7 @@ def run_main(model_fn, FLAGS, make_params_fn):
     params = make_params_fn(FLAGS)
     config = RunConfig(save_checkpoints_steps=FLAGS.save_checkpoints_steps, keep_checkpoint_max=5,
                        log_step_count_steps=FLAGS.log_steps, adam_mode=FLAGS.adam_mode, optimizer=optimizer,
-                       optimizer_hparams=optimizer_hparams)
+                       optimizer_hparams=optimizer_hparams, exact_auc=bool(getattr(FLAGS, "exact_auc", False)))
     est = Estimator(model_fn, FLAGS.model_dir, params, config)
     shard = None
     if FLAGS.mirror:

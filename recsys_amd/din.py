@@ -589,6 +589,9 @@ def define_flags():
     p.add_argument("--mirror", type=lambda s: s.lower() in ("1", "true", "yes"), default=True)
     p.add_argument("--model_dir", default="./din_model/")
     p.add_argument("--hist_len", type=int, default=100)
+    p.add_argument("--exact_auc", type=lambda s: s.lower() in ("1", "true", "yes"), default=False,
+                   help="evaluate() also reports AUC_exact, the exact tie-aware ROC AUC from a key sort on the GPU; the "
+                        "200-threshold AUC stays as it is.  Single replica only")
     return p
 
 
@@ -611,7 +614,7 @@ def main(argv=None):
     params = {"embedding_size": FLAGS.embedding_size, "learning_rate": FLAGS.learning_rate, "dropout": FLAGS.dropout,
               "max_batch_size": FLAGS.batch_size, "hist_len": FLAGS.hist_len}
     cfg = RunConfig(save_checkpoints_steps=FLAGS.save_checkpoints_steps, keep_checkpoint_max=5,
-                    log_step_count_steps=FLAGS.log_steps)
+                    log_step_count_steps=FLAGS.log_steps, exact_auc=FLAGS.exact_auc)
     est = Estimator(model_fn, FLAGS.model_dir, params, cfg)
     shard = None
     if FLAGS.mirror:

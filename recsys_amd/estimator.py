@@ -61,6 +61,9 @@ class RunConfig:
     # (initial_accumulator_value, learning_rate_power, l1_/l2_/l2_shrinkage_regularization_strength), TF's defaults
     optimizer: str = "adam"
     optimizer_hparams: Optional[Dict[str, float]] = None
+    # evaluate() also reports "AUC_exact", the exact tie-aware rank statistic (metrics.ExactAUC: a device-wide key sort, one more
+    # device->host copy per evaluate).  Off: every result dictionary and log line as before.  Single replica only
+    exact_auc: bool = False
 
 
 @dataclass
@@ -927,9 +930,15 @@ class Estimator:
     def evaluate(self, input_fn, steps=None):
         """Estimator.evaluate (fm/fm.py:216-221): AUC-200 / Accuracy / mean batch loss accumulated ON DEVICE by one
         launch per batch (metrics.EvalMetrics); the host synchronises once, when the counters are read back.
-        Data-parallel: every rank evaluates its own shard of the eval stream and the integer counters are summed."""
+        Data-parallel: every rank evaluates its own shard of the eval stream and the integer counters are summed.
+        RunConfig.exact_auc adds "AUC_exact" (metrics.ExactAUC: one more launch per batch, one sort and one more device->host
+        copy at the end; nan, with a WARNING line, when a probability was outside [0, 1]); single replica only."""
         self._check_consistent("evaluate")
+        exact = bool(getattr(self.config, "exact_auc", False))
+        if exact:                         # refused before the first batch is read
+            _metrics.check_exact_auc_world(1 if self.store.dp is None else self.store.dp.world)
         met = _metrics.EvalMetrics(self.store.device)
+        ex = None                         # metrics.ExactAUC, sized by the first batch: the append launches follow met.update's
         n = 0
         it = input_fn()
         try:
@@ -939,6 +948,11 @@ class Estimator:
                         break
                     prob, loss, lab = self._infer_step(features, labels, ModeKeys.EVAL)
                     met.update(lab, prob, loss)
+                    if exact:
+                        if ex is None:
+                            ex = _metrics.ExactAUC(self.store.device,
+                                                   None if steps is None else max(1, int(steps) * int(prob.numel())))
+                        ex.update(lab, prob)
                     n += 1
         finally:
             _close_iter(it)
@@ -946,9 +960,17 @@ class Estimator:
             met.all_reduce(self.store.dp)
         res = met.result()
         res = {"AUC": res["AUC"], "Accuracy": res["Accuracy"], "loss": res["loss"], "global_step": self.global_step}
+        line = ("INFO:Saving dict for global step %d: AUC = %.7g, Accuracy = %.7g, global_step = %d, loss = %.7g"
+                % (res["global_step"], res["AUC"], res["Accuracy"], res["global_step"], res["loss"]))
+        if exact:
+            xr = (ex or _metrics.ExactAUC(self.store.device, 1)).result()
+            res["AUC_exact"] = _metrics.exact_auc_reported(xr)
+            if xr["invalid"] and self._is_chief():
+                print("WARNING:exact_auc: %d of %d probabilities are outside [0, 1] or not finite; AUC_exact is nan"
+                      % (xr["invalid"], xr["invalid"] + xr["positives"] + xr["negatives"]), flush=True)
+            line += ", AUC_exact = %.7g" % res["AUC_exact"]
         if self._is_chief():
-            print("INFO:Saving dict for global step %d: AUC = %.7g, Accuracy = %.7g, global_step = %d, loss = %.7g"
-                  % (res["global_step"], res["AUC"], res["Accuracy"], res["global_step"], res["loss"]), flush=True)
+            print(line, flush=True)
         return res
 
     def _is_chief(self):
