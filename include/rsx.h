@@ -1449,6 +1449,49 @@ int rsx_auc_exact_append(const float* prob, const float* labels, int64_t n, uint
 int rsx_auc_exact_finalize(uint32_t* keys, int64_t n, void* workspace, size_t workspace_bytes, uint64_t* out,
                            rsx_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * GAUC, the per-group exact AUC (csrc/auc_group.hip): the statistic above made segmented, one AUC per group (a user, an item
+ * category), which the host weights by the group's examples as the DIN paper does.  Opt-in, beside the two AUCs above.
+ * Definition, in integers.  An example is (group g, fp32 p, label y).  k32 is rsx_auc_exact_append's 32-bit key.  The example
+ * is valid when k32 is not the padding key and 0 <= g < 2^group_bits (group_bits in 1..31); it then is the 64-bit key
+ * (uint64(g) << 32) | k32, otherwise the padding key 0xFFFFFFFFFFFFFFFF (counted, sorted to the end, no part in the statistic).
+ * Over the sorted valid keys: c[i] the negatives in front of position i (counted globally), h[i] the value of c at the head of
+ * i's score group (key >> 1 differs from the predecessor's), b[i] the value of c at the head of i's group (key >> 32 differs);
+ * a positive at i adds (c[i] - b[i]) + (h[i] - b[i]) to its group's
+ *   U2_g = sum over the group's positives of (2 * #{the group's negatives with a smaller score} + #{with the same score}).
+ * Per group P_g, N_g, U2_g; a group is mixed when P_g N_g > 0; the host takes
+ *   GAUC = sum over mixed groups of n_g U2_g / (2 P_g N_g)  /  sum over mixed groups of n_g,   n_g = P_g + N_g.
+ * The words depend on neither batch sizes, batch order nor the order threads run in (integer atomics only).
+ * The caller owns keys, workspace, header and records; nothing is allocated and nothing synchronises.
+ *   rsx_auc_group_append    one launch per eval batch: n keys to keys_at_offset[0 .. n); the group of example i is
+ *                           groups[i * group_stride] (int32, stride in elements >= 1: ids[:, slot] of a [B, F] batch needs no
+ *                           copy); the batch's invalid count is added to invalid_word[0] (device, zeroed by the caller) with
+ *                           one integer atomic per workgroup.  n == 0 is a no-op.
+ *   rsx_auc_group_finalize  sorts keys[0 .. n) in place (the LSD radix sort of rsx_auc_exact_finalize on the low
+ *                           32 + group_bits bits: 4 + ceil(group_bits / 8) passes; the buffer ends holding the same multiset,
+ *                           ascending, so appending may continue) and reduces them to the device header of 8 words
+ *                           {valid examples, invalid, groups, mixed groups, examples in one-class groups, P, N, 0}.
+ *                           keys and workspace 16-byte aligned, workspace_bytes >= rsx_auc_group_workspace_bytes(n, group_bits)
+ *                           = round_up(8 n, 256) + round_up(1044 * ceil(n / 4096) + 8192, 256) + 16 * ceil(n / 4096).
+ *                           n == 0 gives a zero header.
+ *   rsx_auc_group_records   after finalize, on the same keys and workspace (both untouched in between), once the host has read
+ *                           the header: one record uint64[4] = {g, P_g, N_g, U2_g} per mixed group, in ascending g, the slot
+ *                           of a group being the number of mixed groups in front of it.  records: 16-byte aligned,
+ *                           record_capacity records (header[3] of them are written; a smaller capacity cannot be seen from the
+ *                           host: every store is guarded and records past it are dropped).  record_capacity == 0 is a no-op.
+ *   rsx_auc_group_max_keys  the cap on n (2^27, as rsx_auc_exact_max_keys)
+ * RSX_EINVAL (before any HIP call): a NULL pointer, n < 0 or above the cap, group_bits outside 1..31, group_stride < 1,
+ * record_capacity < 0, a misaligned buffer, a workspace too small.  rsx_auc_group_workspace_bytes returns 0 for such an n or
+ * group_bits. */
+int64_t rsx_auc_group_max_keys(void);
+size_t rsx_auc_group_workspace_bytes(int64_t n, int group_bits);
+int rsx_auc_group_append(const float* prob, const float* labels, const int32_t* groups, int64_t group_stride, int64_t n,
+                         int group_bits, uint64_t* keys_at_offset, uint64_t* invalid_word, rsx_stream_t stream);
+int rsx_auc_group_finalize(uint64_t* keys, int64_t n, int group_bits, void* workspace, size_t workspace_bytes,
+                           uint64_t* header, rsx_stream_t stream);
+int rsx_auc_group_records(const uint64_t* keys, int64_t n, const void* workspace, const uint64_t* header, uint64_t* records,
+                          int64_t record_capacity, rsx_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

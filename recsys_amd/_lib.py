@@ -406,6 +406,11 @@ _SIGS = {
     "rsx_auc_exact_workspace_bytes": (C.c_size_t, [C.c_int64]),
     "rsx_auc_exact_append": (_I, [_P, _P, C.c_int64, _P, _P, _P]),
     "rsx_auc_exact_finalize": (_I, [_P, C.c_int64, _P, C.c_size_t, _P, _P]),
+    "rsx_auc_group_max_keys": (C.c_int64, []),
+    "rsx_auc_group_workspace_bytes": (C.c_size_t, [C.c_int64, _I]),
+    "rsx_auc_group_append": (_I, [_P, _P, _P, C.c_int64, C.c_int64, _I, _P, _P, _P]),
+    "rsx_auc_group_finalize": (_I, [_P, C.c_int64, _I, _P, C.c_size_t, _P, _P]),
+    "rsx_auc_group_records": (_I, [_P, C.c_int64, _P, _P, _P, C.c_int64, _P]),
 }
 
 _lib = None

@@ -222,6 +222,10 @@ def define_flags(p=None):
                    help="evaluate() also reports AUC_exact, the exact tie-aware ROC AUC (sklearn's roc_auc_score, "
                         "deepfm/grpc_client.py:84) from a key sort on the GPU; the 200-threshold AUC stays as it is.  Single "
                         "replica only")
+    p.add_argument("--group_auc_key", default=None,
+                   help="evaluate() also reports GAUC, the exact AUC of every group's examples weighted by the group's examples "
+                        "(the DIN paper's per-user AUC): the source key of an embedding column, e.g. u_id with --feature_set "
+                        "uid_iid or _c14 with the Criteo set.  Single replica only")
     p.add_argument("--feature_set", default="criteo", choices=["criteo", "uid_iid"],
                    help="criteo: the 39-field pipeline of fm.py (BASELINE configs); uid_iid: deepfm.py as committed "
                         "(int64 u_id / i_id hashed into 500000 / 100000 buckets, int64 label)")
@@ -309,7 +313,8 @@ def run_main(model_fn, FLAGS, make_params_fn):
     params = make_params_fn(FLAGS)
     config = RunConfig(save_checkpoints_steps=FLAGS.save_checkpoints_steps, keep_checkpoint_max=5,
                        log_step_count_steps=FLAGS.log_steps, adam_mode=FLAGS.adam_mode, optimizer=optimizer,
-                       optimizer_hparams=optimizer_hparams, exact_auc=bool(getattr(FLAGS, "exact_auc", False)))
+                       optimizer_hparams=optimizer_hparams, exact_auc=bool(getattr(FLAGS, "exact_auc", False)),
+                       group_auc_key=getattr(FLAGS, "group_auc_key", None) or None)
     est = Estimator(model_fn, FLAGS.model_dir, params, config)
     shard = None
     if FLAGS.mirror:

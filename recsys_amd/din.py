@@ -592,6 +592,9 @@ def define_flags():
     p.add_argument("--exact_auc", type=lambda s: s.lower() in ("1", "true", "yes"), default=False,
                    help="evaluate() also reports AUC_exact, the exact tie-aware ROC AUC from a key sort on the GPU; the "
                         "200-threshold AUC stays as it is.  Single replica only")
+    p.add_argument("--group_auc_key", default=None, choices=("i_id", "i_cate"),
+                   help="evaluate() also reports GAUC, the exact AUC of every group's examples weighted by the group's examples: "
+                        "per target item or per target category (the reference's schema has no user id).  Single replica only")
     return p
 
 
@@ -614,7 +617,8 @@ def main(argv=None):
     params = {"embedding_size": FLAGS.embedding_size, "learning_rate": FLAGS.learning_rate, "dropout": FLAGS.dropout,
               "max_batch_size": FLAGS.batch_size, "hist_len": FLAGS.hist_len}
     cfg = RunConfig(save_checkpoints_steps=FLAGS.save_checkpoints_steps, keep_checkpoint_max=5,
-                    log_step_count_steps=FLAGS.log_steps, exact_auc=FLAGS.exact_auc)
+                    log_step_count_steps=FLAGS.log_steps, exact_auc=FLAGS.exact_auc,
+                    group_auc_key=FLAGS.group_auc_key)
     est = Estimator(model_fn, FLAGS.model_dir, params, cfg)
     shard = None
     if FLAGS.mirror:

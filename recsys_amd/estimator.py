@@ -64,6 +64,10 @@ class RunConfig:
     # evaluate() also reports "AUC_exact", the exact tie-aware rank statistic (metrics.ExactAUC: a device-wide key sort, one more
     # device->host copy per evaluate).  Off: every result dictionary and log line as before.  Single replica only
     exact_auc: bool = False
+    # evaluate() also reports "GAUC" (+ "GAUC_groups", "GAUC_skipped_examples"): the exact AUC of every group's examples, weighted
+    # by the group's examples (the DIN paper's per-user AUC; metrics.GroupAUC).  The key of an embedding column of the layout
+    # (Criteo scripts, --feature_set uid_iid: e.g. "u_id") or "i_id" / "i_cate" (din.py); None: everything as before.  Single replica
+    group_auc_key: Optional[str] = None
 
 
 @dataclass
@@ -884,13 +888,15 @@ class Estimator:
     def _infer_step(self, features, labels, mode):
         """One EVAL / PREDICT forward over a host (or device) batch -> (prob, loss or None, labels on the device).  With HIP
         graphs on, the forward is captured once per input signature over static input buffers (ONE packed copy per batch,
-        one graph launch): evaluate() was 283 us per batch of eager launches against a 70 us TRAIN step."""
+        one graph launch): evaluate() was 283 us per batch of eager launches against a 70 us TRAIN step.
+        self._infer_features: the features of this batch on the device, valid until the next call."""
         has_lab = labels is not None
         if not self.store.built:          # variables are created by the first model_fn call
             self._call_model_fn(self._to_device(features), self._to_device(labels) if has_lab else None, ModeKeys.PREDICT)
         self._maybe_restore()
         if not self._use_graph():
             f, l = self._to_device(features), (self._to_device(labels) if has_lab else None)
+            self._infer_features = f
             spec = self._call_model_fn(f, l if mode == ModeKeys.EVAL else None, mode)
             return spec.predictions["prob"], spec.loss, l
         pb = PackedBatch(features, labels if has_lab else np.zeros(0, np.float32))
@@ -901,6 +907,7 @@ class Estimator:
                 # a serving loop with ever-new request sizes: stop capturing (and stop remembering signatures), stay eager
                 dev = pb if pb.flat.device == self.store.device else pb.to(self.store.device)
                 f, l = dev.views()
+                self._infer_features = f
                 spec = self._call_model_fn(f, l if mode == ModeKeys.EVAL else None, mode)
                 return spec.predictions["prob"], spec.loss, (l if has_lab else None)
             g = self._graphs[key] = {"warm": 0}
@@ -908,11 +915,13 @@ class Estimator:
         if "graph" in g:
             self._h2d(g["static"], pb)
             g["graph"].replay()
+            self._infer_features = g["features"]
             return g["prob"], g["loss"], g["labels"]
         dev = pb if pb.flat.device == self.store.device else pb.to(self.store.device)
         if g["warm"] < 1:                 # first batch of this signature: eager (lazy initialisation, allocator warm-up)
             g["warm"] += 1
             f, l = dev.views()
+            self._infer_features = f
             spec = self._call_model_fn(f, l if mode == ModeKeys.EVAL else None, mode)
             return spec.predictions["prob"], spec.loss, (l if has_lab else None)
         g["static"] = dev.clone()
@@ -923,6 +932,7 @@ class Estimator:
         with torch.cuda.graph(graph, **kw):
             spec = self._call_model_fn(f, l if mode == ModeKeys.EVAL else None, mode)
         g["prob"], g["loss"], g["labels"] = spec.predictions["prob"], spec.loss, (l if has_lab else None)
+        g["features"] = self._infer_features = f
         g["graph"] = graph
         graph.replay()                    # capture executes nothing: the static buffers already hold this batch
         return g["prob"], g["loss"], g["labels"]
@@ -932,13 +942,20 @@ class Estimator:
         launch per batch (metrics.EvalMetrics); the host synchronises once, when the counters are read back.
         Data-parallel: every rank evaluates its own shard of the eval stream and the integer counters are summed.
         RunConfig.exact_auc adds "AUC_exact" (metrics.ExactAUC: one more launch per batch, one sort and one more device->host
-        copy at the end; nan, with a WARNING line, when a probability was outside [0, 1]); single replica only."""
+        copy at the end; nan, with a WARNING line, when a probability was outside [0, 1]); single replica only.
+        RunConfig.group_auc_key adds "GAUC", "GAUC_groups" and "GAUC_skipped_examples" (metrics.GroupAUC: one more launch per
+        batch; at the end one sort, the header's copy, one records launch and the records' copy); single replica only."""
         self._check_consistent("evaluate")
         exact = bool(getattr(self.config, "exact_auc", False))
         if exact:                         # refused before the first batch is read
             _metrics.check_exact_auc_world(1 if self.store.dp is None else self.store.dp.world)
+        gkey = getattr(self.config, "group_auc_key", None)
+        if gkey:                          # an unknown key and a second rank are refused before the first batch is read, too
+            _metrics.check_group_auc_world(1 if self.store.dp is None else self.store.dp.world)
+            group_of, group_bits = self._group_auc_source(gkey)
         met = _metrics.EvalMetrics(self.store.device)
         ex = None                         # metrics.ExactAUC, sized by the first batch: the append launches follow met.update's
+        ga = None                         # metrics.GroupAUC, likewise
         n = 0
         it = input_fn()
         try:
@@ -953,6 +970,13 @@ class Estimator:
                             ex = _metrics.ExactAUC(self.store.device,
                                                    None if steps is None else max(1, int(steps) * int(prob.numel())))
                         ex.update(lab, prob)
+                    if gkey:
+                        if ga is None:
+                            ga = _metrics.GroupAUC(self.store.device, group_bits,
+                                                   None if steps is None else max(1, int(steps) * int(prob.numel())))
+                        # the device copy of the batch that _infer_step just used (the graph's static buffer or the eager
+                        # copy): ids[:, slot] is read in place, behind the forward on the same stream
+                        ga.update(group_of(getattr(self, "_infer_features", None) or features), lab, prob)
                     n += 1
         finally:
             _close_iter(it)
@@ -969,9 +993,41 @@ class Estimator:
                 print("WARNING:exact_auc: %d of %d probabilities are outside [0, 1] or not finite; AUC_exact is nan"
                       % (xr["invalid"], xr["invalid"] + xr["positives"] + xr["negatives"]), flush=True)
             line += ", AUC_exact = %.7g" % res["AUC_exact"]
+        if gkey:
+            gr = (ga or _metrics.GroupAUC(self.store.device, group_bits, 1)).result()
+            res["GAUC"] = _metrics.group_auc_reported(gr)
+            res["GAUC_groups"] = gr["mixed_groups"]
+            res["GAUC_skipped_examples"] = gr["skipped_examples"]
+            if gr["invalid"] and self._is_chief():
+                print("WARNING:group_auc_key %s: %d examples have a probability outside [0, 1] or not finite, or an id outside "
+                      "[0, 2^%d); GAUC is nan" % (gkey, gr["invalid"], group_bits), flush=True)
+            line += ", GAUC = %.7g" % res["GAUC"]
         if self._is_chief():
             print(line, flush=True)
         return res
+
+    def _group_auc_source(self, key):
+        """RunConfig.group_auc_key -> (features -> the batch's group ids, group_bits).  Criteo scripts and --feature_set uid_iid:
+        the key of an embedding column of the layout; the group is the column's table-local id, ids[:, slot] of the batch as it
+        is (host or device, no copy here).  din.py: i_id / i_cate."""
+        cols = self.params.get("embedding_feature_columns")
+        if cols is not None:
+            from .feature_columns import CriteoLayout
+            layout = CriteoLayout.from_columns(cols)
+            rows = {c.key: (slot, int(c.rows)) for slot, c in enumerate(layout.columns)}
+            allowed = [c.key for c in layout.columns]
+        else:
+            from . import din
+            rows = {"i_id": ("i_id", int(self.params.get("n_item", din.N_ITEM)) + 1),
+                    "i_cate": ("i_cate", int(self.params.get("n_cate", din.N_CATE)) + 1)}
+            allowed = list(rows)
+        if key not in rows:
+            raise _metrics.RsxError("group_auc_key %r is not a feature of this model; allowed: %s" % (key, ", ".join(allowed)))
+        where, n_rows = rows[key]
+        bits = min(31, max(1, (n_rows - 1).bit_length()))
+        if cols is not None:
+            return (lambda features: features["ids"][:, where]), bits
+        return (lambda features: features[where]), bits
 
     def _is_chief(self):
         return self.store.dp is None or getattr(self.store.dp, "rank", 0) == 0

@@ -8,7 +8,9 @@ evaluation sums the integer counters of all ranks before the finalisation (`all_
 
 Opt-in beside it (RunConfig.exact_auc): `ExactAUC`, the exact tie-aware rank statistic (sklearn's roc_auc_score, which the
 reference's serving client reports, deepfm/grpc_client.py:84) from a device-wide key sort (csrc/auc_exact.hip); `exact_auc_host`
-states its definition in numpy."""
+states its definition in numpy.  And beside that (RunConfig.group_auc_key): `GroupAUC`, the same statistic per group, weighted by the
+group's examples -- the DIN paper's GAUC (csrc/auc_group.hip); `group_auc_records_host` is its definition in numpy and
+`group_auc_from_records` the one place that divides."""
 import ctypes as C
 
 import numpy as np
@@ -201,3 +203,208 @@ class ExactAUC:
             raise RsxError("exact_auc: the sorted keys hold %d positives, %d negatives and %d invalid examples of %d; the append "
                            "launches counted %d invalid" % (s[1], s[2], s[3], self.count, s[4]))
         return exact_auc_from_counts(s[0], s[1], s[2], s[3])
+
+
+# ---- GAUC: the exact AUC per group, weighted by the group's examples (include/rsx.h rsx_auc_group_*) ---------------------------
+GROUP_AUC_PAD = 0xFFFFFFFFFFFFFFFF
+# the 8 words of rsx_auc_group_finalize's header (the last one is zero)
+GROUP_AUC_HEADER = ("valid", "invalid", "groups", "mixed_groups", "skipped_examples", "positives", "negatives")
+
+
+def _group_ids_int32(groups):
+    """Group ids of any integer dtype as int32, an id that int32 cannot hold as -1 (invalid for every group_bits)."""
+    g = np.asarray(groups).reshape(-1)
+    if g.dtype == np.int32:
+        return np.ascontiguousarray(g)
+    g = g.astype(np.int64)
+    return np.where((g < 0) | (g > 0x7FFFFFFF), -1, g).astype(np.int32)
+
+
+def group_auc_keys_host(groups, labels, prob, group_bits=31):
+    """The 64-bit keys of rsx_auc_group_append: (uint64(g) << 32) | k32 with k32 = exact_auc_keys_host's key, for a valid k32 and
+    0 <= g < 2^group_bits; the padding key otherwise."""
+    if not 1 <= int(group_bits) <= 31:
+        raise ValueError("group_bits must be in 1..31")
+    k32 = exact_auc_keys_host(labels, prob)
+    g = _group_ids_int32(groups).astype(np.int64)
+    if g.size != k32.size:
+        raise ValueError("groups and predictions differ in size")
+    valid = (k32 != EXACT_AUC_PAD) & (g >= 0) & (g < (1 << int(group_bits)))
+    key = (np.where(valid, g, 0).astype(np.uint64) << np.uint64(32)) | k32.astype(np.uint64)
+    return np.where(valid, key, np.uint64(GROUP_AUC_PAD)).astype(np.uint64)
+
+
+def group_auc_records_host(groups, labels, prob, group_bits=31):
+    """The documented definition, in numpy: sort the valid keys; c[i] = negatives in front of position i (globally), h[i] = c at
+    the head of i's score group, b[i] = c at the head of i's group; a positive adds (c - b) + (h - b) = 2 #{the group's smaller
+    negatives} + #{the group's equal negatives} to its group's U2.
+    -> (records uint64 [G, 4] = (g, P_g, N_g, U2_g) of ALL groups in ascending g, the number of invalid examples)"""
+    keys = group_auc_keys_host(groups, labels, prob, group_bits)
+    ks = np.sort(keys[keys != np.uint64(GROUP_AUC_PAD)])
+    invalid = int(keys.size - ks.size)
+    if ks.size == 0:
+        return np.zeros((0, 4), np.uint64), invalid
+    neg = (ks & np.uint64(1)) == 0
+    c = np.cumsum(neg, dtype=np.int64) - neg                          # exclusive
+    score, grp = ks >> np.uint64(1), ks >> np.uint64(32)
+    shead, ghead = np.ones(ks.size, bool), np.ones(ks.size, bool)
+    shead[1:] = score[1:] != score[:-1]
+    ghead[1:] = grp[1:] != grp[:-1]
+    h = np.maximum.accumulate(np.where(shead, c, 0))
+    b = np.maximum.accumulate(np.where(ghead, c, 0))
+    con = np.where(neg, 0, (c - b) + (h - b)).astype(np.int64)
+    starts = np.flatnonzero(ghead)
+    u2 = np.add.reduceat(con, starts)
+    n_neg = np.add.reduceat(neg.astype(np.int64), starts)
+    n_all = np.diff(np.append(starts, ks.size))
+    rec = np.stack([grp[starts].astype(np.int64), n_all - n_neg, n_neg, u2], axis=1)
+    return rec.astype(np.uint64), invalid
+
+
+def group_auc_header_host(records, invalid):
+    """The 8 header words rsx_auc_group_finalize gives for a stream with these records (of all its groups)."""
+    rec = np.asarray(records, np.uint64).reshape(-1, 4)
+    P, N = [int(v) for v in rec[:, 1]], [int(v) for v in rec[:, 2]]
+    mixed = [p > 0 and n > 0 for p, n in zip(P, N)]
+    skipped = sum(p + n for p, n, m in zip(P, N, mixed) if not m)
+    return [sum(P) + sum(N), int(invalid), len(P), sum(mixed), skipped, sum(P), sum(N), 0]
+
+
+def group_auc_from_records(records, header):
+    """THE place that divides.  records: uint64 [G, 4] = (g, P_g, N_g, U2_g) (one-class groups among them are passed over);
+    header: the 8 words of rsx_auc_group_finalize / group_auc_header_host.  Per mixed group the float64 U2 / (2 P N), correctly
+    rounded (from Python integers where a term reaches 2^53 and a float64 would not hold it), weighted by n_g = P_g + N_g; both
+    sums by math.fsum, so equal integers give an equal float.
+    -> {"GAUC" (nan when no group is mixed), "groups", "mixed_groups", "skipped_examples", "invalid"}"""
+    import math
+    rec = np.asarray(records, np.uint64).reshape(-1, 4)
+    hdr = [int(v) for v in header]
+    P, N, U = rec[:, 1], rec[:, 2], rec[:, 3]
+    mixed = (P > 0) & (N > 0)
+    P, N, U = P[mixed], N[mixed], U[mixed]
+    if int(P.size) != hdr[3]:
+        raise RsxError("group_auc: %d mixed groups among the records, %d in the header" % (int(P.size), hdr[3]))
+    gauc = float("nan")
+    if P.size:
+        den = np.uint64(2) * P * N                                    # P, N <= 2^27
+        auc = np.empty(P.size, np.float64)
+        exact = (U < np.uint64(1 << 53)) & (den < np.uint64(1 << 53))
+        auc[exact] = U[exact].astype(np.float64) / den[exact].astype(np.float64)
+        for i in np.flatnonzero(~exact):
+            auc[i] = int(U[i]) / int(den[i])
+        w = (P + N).astype(np.float64)
+        gauc = math.fsum(w * auc) / math.fsum(w)
+    return {"GAUC": gauc, "groups": hdr[2], "mixed_groups": hdr[3], "skipped_examples": hdr[4], "invalid": hdr[1]}
+
+
+def group_auc_host(groups, labels, prob, group_bits=31):
+    """group_auc_from_records of group_auc_records_host: GAUC as evaluate() computes it, in numpy."""
+    rec, invalid = group_auc_records_host(groups, labels, prob, group_bits)
+    return group_auc_from_records(rec, group_auc_header_host(rec, invalid))
+
+
+def group_auc_reported(res):
+    """What evaluate() reports as "GAUC": nan when any example was invalid (as exact_auc_reported)."""
+    return float("nan") if res["invalid"] else res["GAUC"]
+
+
+def check_group_auc_world(world):
+    """group_auc_key is a single-replica evaluation, like exact_auc."""
+    if int(world) > 1:
+        raise RsxError("group_auc_key: data-parallel evaluation is not supported (the ranks' keys would have to be sorted "
+                       "together); evaluate on one replica")
+
+
+class GroupAUC:
+    """GAUC of one evaluate() call: one append launch per batch into a device buffer of 64-bit keys; `result()` does one finalize
+    (sort + segmented reduction), one device->host copy of the header, one records launch and one copy of the records.  capacity
+    (examples): fixed when given (an update past it raises); otherwise the buffer grows by doubling, with a device copy and no
+    synchronisation -- ExactAUC's rules.  group_bits: ids are valid in [0, 2^group_bits).
+    Memory: 8 B per key + rsx_auc_group_workspace_bytes(n, group_bits) = round_up(8 n, 256) + round_up(1044 ceil(n / 4096) + 8192,
+    256) + 16 ceil(n / 4096) B of workspace while result() runs + 32 B per mixed group for the records."""
+    GROW_FROM = 1 << 16
+
+    def __init__(self, device, group_bits, capacity=None):
+        self.device = torch.device(device)
+        self.group_bits = int(group_bits)
+        if not 1 <= self.group_bits <= 31:
+            raise RsxError("group_auc: group_bits %d is outside 1..31" % self.group_bits)
+        self.fixed = capacity is not None
+        self.max_keys = int(lib().rsx_auc_group_max_keys())
+        cap = max(1, int(capacity)) if self.fixed else self.GROW_FROM
+        if cap > self.max_keys:
+            raise RsxError("group_auc: capacity %d is above the %d keys one sort takes" % (cap, self.max_keys))
+        self.keys = torch.empty(cap, dtype=torch.int64, device=self.device)
+        self.count = 0
+        # [0..7] finalize's header; [8] the invalid examples the append launches counted
+        self.out = torch.zeros(9, dtype=torch.int64, device=self.device)
+        self.workspace = None
+        self.header = None                # the latest result()'s header, as Python integers
+
+    def _floats(self, x):
+        if not isinstance(x, torch.Tensor):
+            x = torch.from_numpy(np.ascontiguousarray(np.asarray(x, np.float32)))
+        return x.to(self.device).reshape(-1).to(torch.float32).contiguous()
+
+    def _groups(self, g):
+        """-> (int32 device tensor, element stride): a 1-D int32 device tensor is taken as it is, strided or not."""
+        if isinstance(g, torch.Tensor):
+            if g.is_cuda and g.dtype == torch.int32 and g.dim() == 1 and (g.numel() <= 1 or g.stride(0) >= 1):
+                return g, max(1, int(g.stride(0)))
+            g = g.reshape(-1)
+            if g.dtype != torch.int32:
+                g = g.to(torch.int64)
+                g = torch.where((g < 0) | (g > 0x7FFFFFFF), torch.full_like(g, -1), g).to(torch.int32)
+        else:
+            g = torch.from_numpy(_group_ids_int32(g))
+        return g.to(self.device).contiguous(), 1
+
+    def update(self, groups, labels, prob):
+        """groups / labels / prob: device tensors or numpy arrays of B elements; groups may be a strided column view
+        (ids[:, slot]).  No host synchronisation."""
+        y, p = self._floats(labels), self._floats(prob)
+        g, stride = self._groups(groups)
+        n = int(p.numel())
+        if y.numel() != n or g.numel() != n:
+            raise ValueError("groups, labels and predictions differ in size")
+        if n == 0:
+            return
+        need = self.count + n
+        if need > self.keys.numel():
+            if self.fixed or need > self.max_keys:
+                raise RsxError("group_auc: %d examples do not fit the key buffer of %d"
+                               % (need, self.keys.numel() if self.fixed else self.max_keys))
+            grown = torch.empty(min(self.max_keys, max(2 * self.keys.numel(), need)), dtype=torch.int64, device=self.device)
+            grown[:self.count].copy_(self.keys[:self.count])
+            self.keys = grown
+        check(lib().rsx_auc_group_append(C.c_void_p(p.data_ptr()), C.c_void_p(y.data_ptr()), C.c_void_p(g.data_ptr()), stride, n,
+                                         self.group_bits, C.c_void_p(self.keys.data_ptr() + 8 * self.count),
+                                         C.c_void_p(self.out.data_ptr() + 8 * 8),
+                                         C.c_void_p(torch.cuda.current_stream().cuda_stream)), "rsx_auc_group_append")
+        self.count = need
+
+    def result(self, per_group=False):
+        """-> {"GAUC", "groups", "mixed_groups", "skipped_examples", "invalid"}, plus "records" (uint64 [mixed_groups, 4] =
+        (g, P_g, N_g, U2_g), ascending g) when per_group.  The key buffer keeps its multiset (sorted), so updates may continue."""
+        stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+        need = int(lib().rsx_auc_group_workspace_bytes(self.count, self.group_bits))
+        if self.workspace is None or self.workspace.numel() < need:
+            self.workspace = torch.empty(need, dtype=torch.uint8, device=self.device)
+        check(lib().rsx_auc_group_finalize(C.c_void_p(self.keys.data_ptr()), self.count, self.group_bits,
+                                           C.c_void_p(self.workspace.data_ptr()), int(self.workspace.numel()),
+                                           C.c_void_p(self.out.data_ptr()), stream), "rsx_auc_group_finalize")
+        s = [int(v) for v in self.out.cpu().numpy()]
+        if s[1] != s[8] or s[0] + s[1] != self.count or s[5] + s[6] != s[0] or s[3] > s[2]:
+            raise RsxError("group_auc: the sorted keys hold %d positives, %d negatives and %d invalid examples of %d; the append "
+                           "launches counted %d invalid" % (s[5], s[6], s[1], self.count, s[8]))
+        rec = torch.zeros((s[3], 4), dtype=torch.int64, device=self.device)
+        if s[3]:
+            check(lib().rsx_auc_group_records(C.c_void_p(self.keys.data_ptr()), self.count, C.c_void_p(self.workspace.data_ptr()),
+                                              C.c_void_p(self.out.data_ptr()), C.c_void_p(rec.data_ptr()), s[3], stream),
+                  "rsx_auc_group_records")
+        rec = rec.cpu().numpy().view(np.uint64)
+        self.header = s[:8]
+        res = group_auc_from_records(rec, self.header)
+        if per_group:
+            res["records"] = rec
+        return res
