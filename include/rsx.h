@@ -796,6 +796,13 @@ int rsx_predict_din_rank_supported(int U, int C, int P, int K, int n1, int n2, i
 int rsx_predict_din_rank(const rsx_predict_din_model* model_h, const int32_t* hist_item, const int32_t* hist_cate,
                          const int32_t* cand_item, const int32_t* cand_cate, float* prob, int U, int C, int P,
                          rsx_stream_t stream);
+/* The same launch with ONE candidate list for all users (since rsx_version() 104): cand_item / cand_cate are [C] and every
+ * one of the U histories is scored against them -- the rank kernel with a candidate row stride of 0 (an instantiation of its
+ * own; rsx_predict_din_rank compiles to the code it had).  prob [U, C] equals, bit for bit, what rsx_predict_din_rank gives
+ * for the candidates replicated U times.  The same model, envelope (rsx_predict_din_rank_supported) and refusals. */
+int rsx_predict_din_rank_shared(const rsx_predict_din_model* model_h, const int32_t* hist_item, const int32_t* hist_cate,
+                                const int32_t* cand_item, const int32_t* cand_cate, float* prob, int U, int C, int P,
+                                rsx_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Top-k over rows of fp32 scores, merged with a running list kept on the device: for each of U rows, the k best of the
@@ -822,6 +829,28 @@ int rsx_predict_din_rank(const rsx_predict_din_model* model_h, const int32_t* hi
 int rsx_topk_rows_supported(int n, int k);
 int rsx_topk_rows(const float* scores, int ld, int U, int n, int k, float* out_val, int32_t* out_idx, int32_t* state,
                   rsx_stream_t stream);
+/* Threads of the workgroup rsx_topk_rows and rsx_topk_rows_excl launch for (n, k): 256 while n + k <= 1024, above it 1024;
+ * 0 outside the envelope (since rsx_version() 104). */
+int rsx_topk_rows_threads(int n, int k);
+
+/* ---------------------------------------------------------------------------------------------
+ * rsx_topk_rows with a filter on the new scores (since rsx_version() 104): the contract above with ONE addition.  cand_id [n]
+ * names the column of every new score and is shared by the rows; excl [U, E] is a list of ids per row.  New score j of row u is
+ * LEFT OUT of the union when cand_id[j] equals a positive entry of excl[u, :].  Entries <= 0 of excl are padding and exclude
+ * nothing (so a cand_id <= 0 is never excluded); duplicates in excl are allowed; equal ids in cand_id leave together.
+ * next_index still advances by n -- indices stay positions on the column axis -- and filled becomes
+ * min(k, filled + kept), kept = the new scores not excluded.  The running list is never filtered.  With E = 0, or only padding
+ * in excl, the outputs and the state are rsx_topk_rows' bit for bit.
+ * ONE workgroup per row, in place, no workspace, no grid-wide step, no floating-point atomics; a row's result depends on its
+ * scores, its state, cand_id and its own excl row only.  The row's list is sorted into LDS once (1 KB) and every new score
+ * looks its id up by binary search, so membership does not depend on the order threads run in; an excluded score takes the
+ * key 0, below every real key.  Deterministic.
+ * RSX_EINVAL (before any HIP call): a NULL pointer (excl may be NULL when E = 0), U / n / k <= 0, ld < n, E < 0.  Envelope
+ * (rsx_topk_rows_excl_supported; RSX_EUNSUPPORTED outside, before any HIP call): that of rsx_topk_rows and E <= 256.
+ * ------------------------------------------------------------------------------------------- */
+int rsx_topk_rows_excl_supported(int n, int k, int E);
+int rsx_topk_rows_excl(const float* scores, int ld, const int32_t* cand_id, const int32_t* excl, int E, int U, int n, int k,
+                       float* out_val, int32_t* out_idx, int32_t* state, rsx_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
  * DCN cross layers, dcn/dcn.py:132-142: x_{l+1} = (x_l . w_l) * x0 + x_l + b_l, all L

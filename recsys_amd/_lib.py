@@ -388,6 +388,10 @@ _SIGS = {
     "rsx_predict_din_rank": (_I, [C.POINTER(PredictDinModel)] + [_P] * 5 + [_I, _I, _I, _P]),
     "rsx_topk_rows_supported": (_I, [_I, _I]),
     "rsx_topk_rows": (_I, [_P, _I, _I, _I, _I, _P, _P, _P, _P]),
+    "rsx_predict_din_rank_shared": (_I, [C.POINTER(PredictDinModel)] + [_P] * 5 + [_I, _I, _I, _P]),
+    "rsx_topk_rows_threads": (_I, [_I, _I]),
+    "rsx_topk_rows_excl_supported": (_I, [_I, _I, _I]),
+    "rsx_topk_rows_excl": (_I, [_P, _I, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P]),
     "rsx_criteo_parse_examples_supported": (_I, [_I, _I]),
     "rsx_criteo_parse_examples": (_I, [_P, C.c_int64, _P, _I, C.POINTER(ParseSpec), _P, _P, _P]),
     "rsx_criteo_parse_dev_h": (_I, [_P, C.c_int64, _P, _I, C.POINTER(ParseSpec), _P, _P]),

@@ -91,7 +91,9 @@ __device__ __forceinline__ void tower_layer(const float* __restrict__ in, const 
   }
 }
 
-template <int K>
+// SHARED: every user is scored against the SAME C candidates (cand [C], row stride 0: rsx_predict_din_rank_shared).  An
+// instantiation of its own, so the per-user form compiles to the code it had before the shared one existed.
+template <int K, bool SHARED>
 __global__ __launch_bounds__(DR_T) void predict_din_rank_k(const DinRankArgs p) {
   constexpr int KS = K / 16, K4 = K / 4, LDH = K + 4;
   extern __shared__ __attribute__((aligned(16))) float lds[];
@@ -100,6 +102,7 @@ __global__ __launch_bounds__(DR_T) void predict_din_rank_k(const DinRankArgs p) 
   const int u = blockIdx.x / p.ctiles;
   const int c0 = (blockIdx.x - u * p.ctiles) * p.CT;
   const int nc = p.C - c0 < p.CT ? p.C - c0 : p.CT;
+  const int cbase = (SHARED ? 0 : u * p.C) + c0;   // where this workgroup's candidates start in cand
   const int P = p.P, PT = p.PT, CT = p.CT;
   float* Hs = lds + p.oH;                      // [2][PT][LDH]  valid history rows, compacted
   float* Us = lds + p.oU;                      // [2][PT][DR_LDU]  H . (Wh + Wm)
@@ -144,7 +147,7 @@ __global__ __launch_bounds__(DR_T) void predict_din_rank_k(const DinRankArgs p) 
     const int a = e / (CT * K4), rem = e - a * (CT * K4);
     const int c = rem / K4, q4 = rem - c * K4;
     const int cc = c < nc ? c : nc - 1;
-    const int id = p.cand[a][u * p.C + c0 + cc];
+    const int id = p.cand[a][cbase + cc];
     const float4 v = *reinterpret_cast<const float4*>(p.tab[a] + (size_t)id * K + 4 * q4);
     *reinterpret_cast<float4*>(Qs + (a * CT + c) * K + 4 * q4) = v;
     if (a == 0) *reinterpret_cast<float4*>(Xs + c * 3 * K + 4 * q4) = v;
@@ -323,7 +326,7 @@ __global__ __launch_bounds__(DR_T) void predict_din_rank_k(const DinRankArgs p) 
     float z = 0.f;
 #pragma unroll
     for (int n = 0; n < DR_M2; ++n) z = fmaf(x[n], p.wout[n], z);
-    const int id = p.cand[0][u * p.C + c0 + tid];
+    const int id = p.cand[0][cbase + tid];
     z = (z + p.bout[0]) + p.bias[(size_t)id * p.bias_ld];
     p.prob[u * p.C + c0 + tid] = 1.f / (1.f + expf(-z));
   }
@@ -368,9 +371,9 @@ extern "C" int rsx_predict_din_rank_supported(int U, int C, int P, int K, int n1
   return din_rank_envelope(U, C, P, K, n1, n2, L, widths) ? 1 : 0;
 }
 
-extern "C" int rsx_predict_din_rank(const rsx_predict_din_model* m, const int32_t* hist_item, const int32_t* hist_cate,
-                                    const int32_t* cand_item, const int32_t* cand_cate, float* prob, int U, int C, int P,
-                                    rsx_stream_t stream) {
+namespace {
+int din_rank_launch(const rsx_predict_din_model* m, const int32_t* hist_item, const int32_t* hist_cate, const int32_t* cand_item,
+                    const int32_t* cand_cate, float* prob, int U, int C, int P, bool shared, rsx_stream_t stream) {
   if (!m || !hist_item || !hist_cate || !cand_item || !cand_cate || !prob || U <= 0 || C <= 0 || P <= 0) return RSX_EINVAL;
   if (!m->item_emb || !m->cate_emb || !m->item_bias || !m->mlp_wout || !m->mlp_bout) return RSX_EINVAL;
   if (m->K <= 0 || m->n1 <= 0 || m->n2 <= 0 || m->L < 0 || m->bias_ld < 1) return RSX_EINVAL;
@@ -401,6 +404,22 @@ extern "C" int rsx_predict_din_rank(const rsx_predict_din_model* m, const int32_
   const size_t lds = din_rank_layout(&p, m->K);
   if (lds > (size_t)PR_MAX_LDS) return RSX_EUNSUPPORTED;
   const unsigned grid = (unsigned)(U * p.ctiles);
-  return m->K == 32 ? launch_big_lds<predict_din_rank_k<32>>(p, grid, DR_T, lds, rsx_s(stream))
-                    : launch_big_lds<predict_din_rank_k<16>>(p, grid, DR_T, lds, rsx_s(stream));
+  if (shared)
+    return m->K == 32 ? launch_big_lds<predict_din_rank_k<32, true>>(p, grid, DR_T, lds, rsx_s(stream))
+                      : launch_big_lds<predict_din_rank_k<16, true>>(p, grid, DR_T, lds, rsx_s(stream));
+  return m->K == 32 ? launch_big_lds<predict_din_rank_k<32, false>>(p, grid, DR_T, lds, rsx_s(stream))
+                    : launch_big_lds<predict_din_rank_k<16, false>>(p, grid, DR_T, lds, rsx_s(stream));
+}
+}  // namespace
+
+extern "C" int rsx_predict_din_rank(const rsx_predict_din_model* m, const int32_t* hist_item, const int32_t* hist_cate,
+                                    const int32_t* cand_item, const int32_t* cand_cate, float* prob, int U, int C, int P,
+                                    rsx_stream_t stream) {
+  return din_rank_launch(m, hist_item, hist_cate, cand_item, cand_cate, prob, U, C, P, false, stream);
+}
+
+extern "C" int rsx_predict_din_rank_shared(const rsx_predict_din_model* m, const int32_t* hist_item, const int32_t* hist_cate,
+                                           const int32_t* cand_item, const int32_t* cand_cate, float* prob, int U, int C, int P,
+                                           rsx_stream_t stream) {
+  return din_rank_launch(m, hist_item, hist_cate, cand_item, cand_cate, prob, U, C, P, true, stream);
 }

@@ -1,0 +1,233 @@
+// What the two top-k kernels share (topk.hip: rsx_topk_rows; topk_excl.hip: rsx_topk_rows_excl): the 64-bit key image of a
+// (score, index) pair, the LDS plan, and the workgroup's body -- keys, MSB-first radix select, compaction, rank by counting.
+// topk.hip's head describes the method.  EXCL = false is rsx_topk_rows; EXCL = true adds the exclusion of new scores by id
+// (topk_excl.hip's head), compiled in with `if constexpr` so the plain kernel holds none of it.
+#pragma once
+#include "predict_device.h"      // launch_big_lds, PR_MAX_LDS
+
+namespace {
+
+constexpr int TK_KMAX = 1024;            // largest k
+constexpr int TK_KEYS = 16384;           // largest n + k: 128 KB of keys
+constexpr int TK_T_SMALL = 256, TK_T_BIG = 1024;
+constexpr int TK_SMALL_KEYS = 1024;     // up to this many keys a workgroup of 256 threads, above it 1024
+constexpr int TK_EMAX = 256;             // largest exclusion list of a row (EXCL)
+
+struct TopkArgs {
+  const float* scores;
+  float* out_val;
+  int32_t* out_idx;
+  int32_t* state;
+  int ld, n, k;
+  int oSel, oOldV, oOldI, oHist, oMisc;  // LDS plan, in bytes from the start of the keys
+};
+
+struct TopkExclArgs : TopkArgs {
+  const int32_t* cand_id;                // [n], shared by the rows
+  const int32_t* excl;                   // [U, E]
+  int E;
+  int oExcl;                             // LDS: the row's exclusion ids, sorted [E]
+};
+
+__device__ __forceinline__ unsigned long long tk_key(const float v, const int idx) {
+  unsigned u = __float_as_uint(v);
+  const bool negzero = u == 0x80000000u;
+  if (negzero) u = 0u;
+  unsigned img = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+  if ((u & 0x7fffffffu) > 0x7f800000u) img = 0u;
+  const unsigned lo = ((~(unsigned)idx & 0x7fffffffu) << 1) | (negzero ? 1u : 0u);
+  return ((unsigned long long)img << 32) | lo;
+}
+
+__device__ __forceinline__ int tk_index(const unsigned long long key) { return (int)(~((unsigned)key >> 1) & 0x7fffffffu); }
+
+template <bool EXCL, class Args>
+__device__ __forceinline__ void topk_rows_body(const Args& p, unsigned long long* tk_lds) {
+  unsigned long long* keys = tk_lds;
+  char* base = reinterpret_cast<char*>(tk_lds);
+  unsigned long long* sel = reinterpret_cast<unsigned long long*>(base + p.oSel);
+  float* oldv = reinterpret_cast<float*>(base + p.oOldV);
+  int* oldi = reinterpret_cast<int*>(base + p.oOldI);
+  unsigned* hist = reinterpret_cast<unsigned*>(base + p.oHist);
+  unsigned* misc = reinterpret_cast<unsigned*>(base + p.oMisc);      // 0: bin, 1: rank inside the bin, 2: the bin's count, 3: compaction cursor (EXCL: 4: new scores kept)
+
+  const int tid = threadIdx.x, NT = blockDim.x, lane = tid & 63;
+  const int n = p.n, k = p.k;
+  const size_t row = blockIdx.x;
+  const float* sc = p.scores + row * (size_t)p.ld;
+  float* ov = p.out_val + row * (size_t)k;
+  int32_t* oi = p.out_idx + row * (size_t)k;
+  int32_t* st = p.state + row * 2;
+
+  int filled = st[0];
+  const int next0 = st[1];
+  filled = filled < 0 ? 0 : (filled > k ? k : filled);             // a state nobody zeroed must not index out of the list
+  const int T = filled + n;
+
+  // (1) keys of the running list and of the new scores
+  for (int i = tid; i < filled; i += NT) {
+    const float v = ov[i];
+    const int ix = oi[i];
+    oldv[i] = v;
+    oldi[i] = ix;
+    keys[i] = tk_key(v, ix);
+  }
+  if (tid == 0) misc[3] = 0u;
+  int want;
+  if constexpr (EXCL) {
+    // The row's exclusion ids, sorted into LDS: entries <= 0 (padding) become 0 and sort first.  The unsorted copy borrows the
+    // histogram's 256 words (E <= 256; the select zeroes them before every pass).  Rank = the number of entries that sort
+    // before this one, ties by position: a permutation, whatever order the threads run in.
+    const int E = p.E;
+    int* exs = reinterpret_cast<int*>(base + p.oExcl);
+    if (tid == 0) misc[4] = 0u;
+    if (E > 0) {
+      const int32_t* ex = p.excl + row * (size_t)E;
+      int* raw = reinterpret_cast<int*>(hist);
+      for (int t = tid; t < E; t += NT) {
+        const int v = ex[t];
+        raw[t] = v > 0 ? v : 0;
+      }
+      __syncthreads();
+      for (int t = tid; t < E; t += NT) {
+        const int v = raw[t];
+        int rank = 0;
+        for (int j = 0; j < E; ++j) {
+          const int o = raw[j];
+          rank += (o < v || (o == v && j < t)) ? 1 : 0;
+        }
+        exs[rank] = v;
+      }
+    }
+    __syncthreads();
+    // An excluded score takes key 0: below every real key (tk_key gives 0 only for a NaN at index 2^31 - 1, which the contract
+    // rules out), so it is never among the `want` largest when want counts the kept keys only.
+    unsigned kept = 0u;
+    for (int j = tid; j < n; j += NT) {
+      bool out = false;
+      if (E > 0) {
+        const int id = p.cand_id[j];
+        int lo = 0, hi = E;                                          // lower bound of id in exs
+        while (lo < hi) {
+          const int mid = (lo + hi) >> 1;
+          if (exs[mid] < id) lo = mid + 1; else hi = mid;
+        }
+        out = id > 0 && lo < E && exs[lo] == id;
+      }
+      keys[filled + j] = out ? 0ull : tk_key(sc[j], next0 + j);
+      kept += out ? 0u : 1u;
+    }
+    if (kept) atomicAdd(&misc[4], kept);                             // (integer: the sum does not depend on the order)
+    __syncthreads();
+    const int Te = filled + (int)misc[4];
+    want = Te < k ? Te : k;
+  } else {
+    want = T < k ? T : k;
+    for (int j = tid; j < n; j += NT) keys[filled + j] = tk_key(sc[j], next0 + j);
+    __syncthreads();
+  }
+
+  // The select runs when the keys outnumber the survivors.  Plain: T > k, and then want == k.  EXCL: also when excluded keys
+  // (zeros) sit among no more than k kept ones (filled + kept < k < filled + n included) -- the want-th largest key is a real
+  // one, every zero is smaller, and a bin that holds a zero is never "taken whole", so `key >= prefix` admits no zero.
+  const int nsel = EXCL ? want : k;
+  const bool select = EXCL ? (T > want && want > 0) : (T > k);
+  const unsigned long long* src = keys;                            // the survivors: everything when the union is no longer than k
+  if (select) {
+    // (2) radix select of the nsel-th largest key
+    unsigned long long prefix = 0ull, mask = 0ull;
+    unsigned r = (unsigned)nsel;                                   // the key wanted is the r-th largest of those matching the prefix
+    for (int shift = 56; shift >= 0; shift -= 8) {
+      for (int b = tid; b < 256; b += NT) hist[b] = 0u;
+      __syncthreads();
+      for (int i = tid; i < T; i += NT) {
+        const unsigned long long key = keys[i];
+        if ((key & mask) == prefix) atomicAdd(&hist[(unsigned)(key >> shift) & 255u], 1u);
+      }
+      __syncthreads();
+      if (tid < 64) {                                              // lane l owns bins 4 l .. 4 l + 3; higher bins are larger keys
+        const unsigned c0 = hist[4 * lane], c1 = hist[4 * lane + 1], c2 = hist[4 * lane + 2], c3 = hist[4 * lane + 3];
+        const unsigned s = c0 + c1 + c2 + c3;
+        unsigned suf = s;                                          // -> sum over lanes >= this one
+        for (int d = 1; d < 64; d <<= 1) {
+          const unsigned t = (unsigned)__shfl_down((int)suf, d);
+          if (lane + d < 64) suf += t;
+        }
+        unsigned a = suf - s;                                      // keys in the bins of higher lanes
+        if (a < r && r <= suf) {                                   // exactly one lane: 1 <= r <= the number of matching keys
+          unsigned bin, cnt;
+          if (r <= a + c3) { bin = 3u; cnt = c3; }
+          else {
+            a += c3;
+            if (r <= a + c2) { bin = 2u; cnt = c2; }
+            else {
+              a += c2;
+              if (r <= a + c1) { bin = 1u; cnt = c1; }
+              else { a += c1; bin = 0u; cnt = c0; }
+            }
+          }
+          misc[0] = 4u * lane + bin;
+          misc[1] = r - a;
+          misc[2] = cnt;
+        }
+      }
+      __syncthreads();
+      prefix |= (unsigned long long)misc[0] << shift;
+      mask |= 255ull << shift;
+      r = misc[1];
+      if (misc[2] == r) break;                                     // the bin is taken whole: every key >= prefix is in
+    }
+    // (3) the keys >= prefix are exactly nsel
+    for (int i = tid; i < T; i += NT) {
+      const unsigned long long key = keys[i];
+      if (key >= prefix) {
+        const unsigned at = atomicAdd(&misc[3], 1u);
+        if (at < (unsigned)nsel) sel[at] = key;
+      }
+    }
+    __syncthreads();
+    src = sel;
+  }
+
+  // (4) rank = the number of survivors with a larger key; write (value, index) there
+  for (int w = tid; w < want; w += NT) {
+    const unsigned long long key = src[w];
+    int rank = 0;
+    for (int j = 0; j < want; ++j) rank += src[j] > key ? 1 : 0;
+    const unsigned img = (unsigned)(key >> 32);
+    const int idx = tk_index(key);
+    float v;
+    if (img != 0u) {
+      unsigned u = (img & 0x80000000u) ? (img ^ 0x80000000u) : ~img;
+      if (key & 1ull) u = 0x80000000u;
+      v = __uint_as_float(u);
+    } else if (idx >= next0 && idx - next0 < n) {                  // a NaN of this call: its bits are in the scores
+      v = sc[idx - next0];
+    } else {                                                       // a NaN of the running list: its bits are in the LDS copy
+      v = __uint_as_float(0x7fc00000u);
+      for (int j = 0; j < filled; ++j)
+        if (oldi[j] == idx) v = oldv[j];
+    }
+    ov[rank] = v;
+    oi[rank] = idx;
+  }
+  if (tid == 0) {
+    st[0] = want;
+    st[1] = next0 + n;
+  }
+}
+
+inline bool topk_envelope(int n, int k) { return n >= 1 && k >= 1 && k <= TK_KMAX && (long long)n + k <= TK_KEYS; }
+inline unsigned topk_threads(int n, int k) { return n + k <= TK_SMALL_KEYS ? TK_T_SMALL : TK_T_BIG; }
+
+inline int topk_layout(TopkArgs* p) {
+  int o = 8 * (p->n + p->k);
+  p->oSel = o; o += 8 * p->k;
+  p->oOldV = o; o += 4 * p->k;
+  p->oOldI = o; o += 4 * p->k;
+  p->oHist = o; o += 4 * 256;
+  p->oMisc = o; o += 16;
+  return o;
+}
+
+}  // namespace

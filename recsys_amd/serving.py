@@ -41,6 +41,12 @@ The reference exports a SavedModel whose serving signature parses serialized `tf
               every chunk's rank launch keeps the running list on the device, one copy of k pairs ends the request;
               "host": the probabilities as without top_k, then `topk_rows_host`.  The same bits either way.  (`topk_path`
               records where the latest such request selected.)
+              `set_catalogue(i_id, i_cate)` keeps the servable items on the device; `recommend(u_iid_seq, u_icat_seq, top_k)`
+              then returns the top_k best catalogue entries the user has NOT seen (and that `exclude` does not name),
+              {"prob", "item", "index", "count"}; `recommend_host` is the definition.  recommend_path_for(k) == "device":
+              per chunk rsx_predict_din_rank_shared (one candidate list for all users) and rsx_topk_rows_excl
+              (csrc/topk_excl.hip), the whole request ONE graph, only histories and exclusion ids shipped; "host":
+              `rank_candidates` over the catalogue, then `recommend_host`.  The same bits either way.
 """
 import ctypes as C
 import importlib
@@ -487,6 +493,86 @@ def topk_rows_host(prob, k):
     return out if a.ndim == 2 else {key: v[0] for key, v in out.items()}
 
 
+# ---- recommendation over a resident catalogue (din.py): pure numpy, no device -------------------------------------------------
+EXCL_MAX = 256                        # include/rsx.h rsx_topk_rows_excl: the longest exclusion list of a user on the device
+
+
+def check_catalogue(i_id, i_cate, n_item, n_cate):
+    """Argument checking of `Predictor.set_catalogue` (no device needed): two 1-D integer arrays of equal length N >= 1 (numpy
+    or torch, any integer dtype; lists become numpy) with ids inside [0, n_item) / [0, n_cate) -> (i_id, i_cate) as int32
+    numpy.  Duplicates and item id 0 are allowed: a position is what identifies an entry."""
+    out = []
+    for name, x in (("i_id", i_id), ("i_cate", i_cate)):
+        if not hasattr(x, "shape") or not hasattr(x, "dtype"):
+            x = np.asarray(x)
+        if not _is_int_array(x):
+            raise _lib.RsxError("set_catalogue: %s must hold integers, not %s" % (name, x.dtype))
+        if not isinstance(x, np.ndarray):
+            x = x.detach().cpu().numpy()
+        out.append(x)
+    ci, cc = out
+    if ci.ndim != 1 or cc.ndim != 1 or ci.shape != cc.shape:
+        raise _lib.RsxError("set_catalogue: expected two 1-D arrays of equal length, got i_id %s and i_cate %s" % (ci.shape, cc.shape))
+    if ci.shape[0] < 1:
+        raise _lib.RsxError("set_catalogue: an empty catalogue")
+    for name, x, hi in (("i_id", ci, n_item), ("i_cate", cc, n_cate)):
+        if int(x.min()) < 0 or int(x.max()) >= int(hi):
+            raise _lib.RsxError("set_catalogue: %s holds ids outside [0, %d) (min %d, max %d)" % (name, int(hi), int(x.min()), int(x.max())))
+    return np.ascontiguousarray(ci, np.int32), np.ascontiguousarray(cc, np.int32)
+
+
+def _exclusion_ids(hist_item, exclude, U, exclude_seen):
+    """-> int64 [U, E'']: the ids a request names for exclusion, user by user (the history when exclude_seen, then `exclude`);
+    RsxError when `exclude` does not have the histories' leading shape."""
+    parts = []
+    h = hist_item.detach().cpu().numpy() if hasattr(hist_item, "detach") else np.asarray(hist_item)
+    single = h.ndim == 1
+    if exclude_seen:
+        parts.append(h.reshape(U, -1).astype(np.int64))
+    if exclude is not None:
+        e = exclude.detach().cpu().numpy() if hasattr(exclude, "detach") else np.asarray(exclude)
+        if e.size and not np.issubdtype(e.dtype, np.integer):
+            raise _lib.RsxError("recommend: exclude must hold integers, not %s" % e.dtype)
+        if e.ndim != h.ndim or (not single and e.shape[0] != U):
+            raise _lib.RsxError("recommend: exclude %s does not match the histories %s: [E] for one user, [U, E] for U users"
+                                % (tuple(e.shape), tuple(h.shape)))
+        parts.append(e.reshape(U, -1).astype(np.int64))
+    return np.concatenate(parts, 1) if parts else np.zeros((U, 0), np.int64)
+
+
+def recommend_host(prob, cat_item, hist_item, exclude, top_k, exclude_seen=True):
+    """The definition of `Predictor.recommend`, in numpy.  prob: float32 [N] (one user) or [U, N], the scores of the N catalogue
+    entries; cat_item: int [N], their item ids; hist_item: [P'] / [U, P']; exclude: None or [E'] / [U, E'].  An entry is
+    EXCLUDED for user u when its item id equals a positive id of hist_item[u] (if exclude_seen) or of exclude[u]; ids <= 0 are
+    padding.  The eligible entries, with their catalogue positions, in the order of `topk_rows_host` (higher score first, equal
+    ones by the lower position, NaN last), the first top_k of them ->
+    {'prob': float32 [U, kk], 'item': int32 [U, kk], 'index': int32 [U, kk], 'count': int32 [U]}, kk = min(top_k, N),
+    count[u] = min(top_k, eligible entries of u); entries at and beyond count[u] are NaN / -1 / -1.  The one-user form returns
+    the three arrays cut to count, and count as an int."""
+    k = check_top_k(top_k)
+    a = np.asarray(prob, np.float32)
+    cat = np.asarray(cat_item)
+    if a.ndim not in (1, 2) or cat.ndim != 1 or a.shape[-1] != cat.shape[0] or cat.shape[0] < 1:
+        raise _lib.RsxError("recommend_host: expected scores [N] or [U, N] over a catalogue [N], N >= 1; got %s and %s" % (a.shape, cat.shape))
+    rows = np.atleast_2d(a)
+    U, N = rows.shape
+    ids = _exclusion_ids(hist_item, exclude, U, exclude_seen)
+    kk = min(k, N)
+    out = {"prob": np.full((U, kk), np.nan, np.float32), "item": np.full((U, kk), -1, np.int32),
+           "index": np.full((U, kk), -1, np.int32), "count": np.zeros(U, np.int32)}
+    for u in range(U):
+        pos = np.flatnonzero(~np.isin(cat, ids[u][ids[u] > 0]))
+        order = pos[np.lexsort((pos, -rows[u, pos]))][:kk]
+        c = len(order)
+        out["prob"][u, :c], out["item"][u, :c], out["index"][u, :c], out["count"][u] = rows[u, order], cat[order], order, c
+    return out if a.ndim == 2 else _one_user(out)
+
+
+def _one_user(out):
+    c = int(out["count"][0])
+    return {"prob": out["prob"][0, :c], "item": out["item"][0, :c], "index": out["index"][0, :c], "count": c}
+
+
 # ---- Predictor ---------------------------------------------------------------------------------------------------------------
 class Predictor:
     """An exported model ready to answer requests.  See the module docstring for the two paths.  `table_dtype` is the
@@ -548,6 +634,9 @@ class Predictor:
         self.rank_path = None
         self.topk_path = None               # where the latest `rank_candidates(top_k=k)` selected (before any: a small k)
         self._rank = None
+        self.catalogue_size = None          # N of the latest `set_catalogue` (din.py bundles)
+        self.recommend_path = None          # where the latest `recommend` selected
+        self._cat = None
         if self.script == "din":
             self.rank_path = "fused" if self._rank_supported() else "layers"
             self.topk_path = "device" if self.rank_path == "fused" else "host"
@@ -799,8 +888,9 @@ class Predictor:
             # request buffers of one chunk: the histories [U, P], the candidates and their probabilities [U, max_candidates]
             # (a request of fewer users or candidates uses leading parts of them; graphs captured over smaller buffers go)
             dev, i32 = self.device, torch.int32
-            self._drop_graphs("rank", "rank_topk")
+            self._drop_graphs("rank", "rank_topk", "recommend")
             r.pop("topk", None)
+            r.pop("rec", None)
             r["hist"] = [torch.zeros(U * P, dtype=i32, device=dev) for _ in range(2)]
             r["cand"] = [torch.zeros(U * self.max_candidates, dtype=i32, device=dev) for _ in range(2)]
             r["prob"] = torch.zeros(U * self.max_candidates, dtype=torch.float32, device=dev)
@@ -960,6 +1050,154 @@ class Predictor:
                 e = min(Cn, s + self.max_candidates)
                 out[:, s:e] = self._rank_chunk(U, ci[:, s:e], cc[:, s:e]).cpu().numpy()
         return {"prob": out.reshape(shape)}
+
+    # -- recommendation over a resident catalogue (din.py; csrc/topk_excl.hip) -----------------------------------------------
+    def _need_din(self, what):
+        if getattr(self, "script", None) != "din":
+            raise _lib.RsxError("%s: only din.py bundles rank a catalogue against a history; this bundle is %s.py"
+                                % (what, getattr(self, "script", None)))
+
+    def set_catalogue(self, i_id, i_cate):
+        """din.py bundles: the servable items and their categories, two 1-D integer arrays of equal length N >= 1 (numpy or
+        torch; `check_catalogue` refuses anything else and ids outside the tables).  Uploaded once as int32, a host copy is
+        kept; `catalogue_size` reports N.  A second call replaces the catalogue and drops the graphs captured over the old one."""
+        import torch
+        self._need_din("set_catalogue")
+        _, n_item, n_cate, _ = self._din_sizes()
+        ci, cc = check_catalogue(i_id, i_cate, n_item, n_cate)
+        self._drop_graphs("recommend")
+        self._cat = {"host": (ci, cc), "dev": [torch.from_numpy(x).to(self.device) for x in (ci, cc)]}
+        self.catalogue_size = int(ci.shape[0])
+
+    def _recommend_on_device(self, k):
+        return self.rank_path == "fused" and k <= TOPK_MAX_K and bool(_lib.lib().rsx_topk_rows_excl_supported(1, k, 0))
+
+    def recommend_path_for(self, top_k):
+        """Where `recommend(..., top_k=top_k)` runs on this Predictor: "device" or "host" (None for a bundle that ranks no
+        candidates).  A pure function of the bundle and k; a request that names more than 256 distinct positive ids for one
+        user still takes the host path, and `recommend_path` records what the latest request took."""
+        if self.script != "din":
+            return None
+        return "device" if self._recommend_on_device(check_top_k(top_k)) else "host"
+
+    def recommend_buffer_bytes(self, U=1, top_k=100):
+        """Bytes of the static buffers a `recommend` request of U users holds: the rank buffers, the catalogue (two int32 [N]),
+        and on the device path out_val / out_idx [U, k] with state [U, 2] behind them and the exclusion ids [U, 256]."""
+        n = self.rank_buffer_bytes(U) + 8 * int(self.catalogue_size or 0)
+        if self._recommend_on_device(check_top_k(top_k)):
+            n += 4 * (2 * U * int(top_k) + 2 * U) + 4 * U * EXCL_MAX
+        return n
+
+    def _rec_setup(self, U, k):
+        """The static buffers of a device `recommend` beside the rank buffers: ONE flat buffer that holds out_val [U, k], behind
+        it out_idx [U, k] and state [U, 2] of the request at hand (so the answer and `filled` come back in one copy), and the
+        exclusion ids [U, 256].  Reallocated like the selection's buffers: when a request needs more than they hold."""
+        import torch
+        r = self._rank
+        t = r.get("rec")
+        if t is None or r["U"] * k > t["pairs"]:
+            self._drop_graphs("recommend")
+            t = r["rec"] = {"pairs": r["U"] * k,
+                            "buf": torch.zeros(2 * r["U"] * k + 2 * r["U"], dtype=torch.float32, device=self.device),
+                            "excl": torch.zeros(r["U"] * EXCL_MAX, dtype=torch.int32, device=self.device)}
+        return t
+
+    def _recommend_launch(self, U, k, E):
+        """The whole request, one chain: the state's zeroing, then for every chunk of max_candidates catalogue entries the
+        shared rank launch and the filtered selection (sliced as `_rank_topk_launch` slices it beyond n + k = 16 384).  Every
+        address is fixed -- the catalogue's slices included -- so `_run` captures it as ONE graph per (U, k, E)."""
+        import torch
+        r, t, L = self._rank, self._rank["rec"], _lib.lib()
+        cat_i, cat_c = (x.data_ptr() for x in self._cat["dev"])
+        N, mc, P = self.catalogue_size, self.max_candidates, self._din_sizes()[0]
+        val = t["buf"].data_ptr()
+        idx, state = val + 4 * U * k, val + 8 * U * k
+        t["buf"][2 * U * k:2 * U * k + 2 * U].zero_()
+        stream = torch.cuda.current_stream().cuda_stream
+        for s in range(0, N, mc):
+            n = min(mc, N - s)
+            _lib.check(L.rsx_predict_din_rank_shared(C.byref(r["model"]), r["hist"][0].data_ptr(), r["hist"][1].data_ptr(),
+                                                     cat_i + 4 * s, cat_c + 4 * s, r["prob"].data_ptr(), int(U), int(n), P, stream),
+                       "rsx_predict_din_rank_shared")
+            step = n
+            while not L.rsx_topk_rows_excl_supported(step, k, E):
+                step = (step + 1) // 2
+            for s2 in range(0, n, step):
+                _lib.check(L.rsx_topk_rows_excl(r["prob"].data_ptr() + 4 * s2, int(n), cat_i + 4 * (s + s2), t["excl"].data_ptr(),
+                                                int(E), int(U), min(step, n - s2), int(k), val, idx, state, stream),
+                           "rsx_topk_rows_excl")
+
+    def _recommend_device(self, U, k, P, Pq, u_iid_seq, u_icat_seq, ids):
+        """ids: int32 [U, E] host, E one of the exclusion capacities -> the answer of `recommend_host` for U users."""
+        import torch
+        E = int(ids.shape[1])
+        kk = min(k, self.catalogue_size)
+        with torch.no_grad():
+            r = self._rank_setup(U)
+            t = self._rec_setup(U, k)
+            self._rank_histories(r, U, P, Pq, u_iid_seq, u_icat_seq)
+            if E:
+                t["excl"][:U * E].view(U, E).copy_(torch.from_numpy(ids), non_blocking=True)
+            self._run(("recommend", U, k, E), lambda: self._recommend_launch(U, k, E))
+            h = t["buf"][:2 * U * k + 2 * U].cpu().numpy()           # the ONE device-to-host copy: pairs and `filled`
+        count = h[2 * U * k:].view(np.int32).reshape(U, 2)[:, 0].copy()
+        prob = np.ascontiguousarray(h[:U * k].reshape(U, k)[:, :kk])
+        index = np.ascontiguousarray(h[U * k:2 * U * k].view(np.int32).reshape(U, k)[:, :kk])
+        pad = np.arange(kk)[None, :] >= count[:, None]               # entries past `filled` are unspecified on the device
+        prob[pad], index[pad] = np.nan, 0
+        item = self._cat["host"][0][index]
+        item[pad], index[pad] = -1, -1
+        return {"prob": prob, "item": item, "index": index, "count": count}
+
+    @staticmethod
+    def _excl_capacity(cols):
+        """Columns of the exclusion buffer a request of `cols` ids per user uses (a graph is keyed by it)."""
+        return 0 if cols == 0 else next(c for c in (32, 64, 128, EXCL_MAX) if cols <= c)
+
+    def recommend(self, u_iid_seq, u_icat_seq, top_k, exclude_seen=True, exclude=None):
+        """din.py bundles, after `set_catalogue`: the top_k best catalogue entries for ONE user's history ([P']) or for U users
+        ([U, P']), every entry scored exactly as `rank_candidates` scores it, without the entries whose item id is a positive
+        id of the user's history (exclude_seen) or of `exclude` ([E'] / [U, E']: blocked, already bought; ids <= 0 are padding).
+        -> {'prob': float32 [U, kk], 'item': int32 [U, kk] (the catalogue's i_id), 'index': int32 [U, kk] (the catalogue
+        position), 'count': int32 [U]}, kk = min(top_k, N), count[u] = min(top_k, eligible entries); entries at and beyond
+        count[u] are NaN / -1 / -1.  One user: the arrays cut to count, count an int.  `recommend_host` is the definition.
+        `recommend_path_for(k)` says where a request selects: "device" (rank_path == "fused", k <= 1024, at most 256 distinct
+        positive exclusion ids per user): only the histories and the exclusion ids are shipped, the whole request -- per chunk
+        rsx_predict_din_rank_shared over the resident catalogue and rsx_topk_rows_excl -- is ONE captured graph per
+        (U, k, exclusion capacity), one copy brings the answer back; "host": `rank_candidates` over the catalogue, then
+        `recommend_host`.  Both give the same bits."""
+        import torch
+        self._need_din("recommend")
+        if self._cat is None:
+            raise _lib.RsxError("recommend: no catalogue set -- call set_catalogue(i_id, i_cate) first")
+        k = check_top_k(top_k)
+        P, n_item, n_cate, _ = self._din_sizes()
+        shape = tuple(u_iid_seq.shape) if hasattr(u_iid_seq, "shape") else np.shape(u_iid_seq)
+        one = np.zeros((shape[0], 1) if len(shape) == 2 else 1, np.int32)      # a stand-in candidate: the histories' checks
+        U, _, Pq, single = check_rank_request(u_iid_seq, u_icat_seq, one, one, P, n_item, n_cate)
+        ids = _exclusion_ids(u_iid_seq, exclude, U, exclude_seen)
+        on_device = self._recommend_on_device(k)
+        if on_device:
+            ids = np.where((ids > 0) & (ids < 2 ** 31), ids, 0)
+            if ids.shape[1] > EXCL_MAX:                              # more columns than the kernel takes: the distinct ids may fit
+                rows = [np.unique(x[x > 0]) for x in ids]
+                on_device = max(len(x) for x in rows) <= EXCL_MAX
+                if on_device:
+                    ids = np.zeros((U, max(len(x) for x in rows)), np.int64)
+                    for u, x in enumerate(rows):
+                        ids[u, :len(x)] = x
+        if on_device:
+            self.recommend_path = "device"
+            padded = np.zeros((U, self._excl_capacity(ids.shape[1])), np.int32)
+            padded[:, :ids.shape[1]] = ids
+            out = self._recommend_device(U, k, P, Pq, u_iid_seq, u_icat_seq, padded)
+        else:
+            self.recommend_path = "host"
+            ci, cc = self._cat["host"]
+            cand = (ci, cc) if single else tuple(np.broadcast_to(x, (U, len(x))) for x in (ci, cc))
+            prob = self.rank_candidates(u_iid_seq, u_icat_seq, *cand)["prob"]
+            return recommend_host(prob, ci, u_iid_seq, exclude, k, exclude_seen)
+        return _one_user(out) if single else out
 
     # -- public ------------------------------------------------------------------------------------------------------------
     def _parse(self, serialized):

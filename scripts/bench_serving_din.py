@@ -29,6 +29,15 @@ can answer it, in ONE process, their timed regions alternating, `--repeats` roun
      candidates of its last chunk.  With --profile-run C: eager B requests for a kernel trace of its own, and --kernel-stats
      prints the selection launch's time next to the rank launch's.
 
+  --recommend  the request `recommend` was built for: the K best (--top_k, default 100) items of the whole 63 001-item catalogue
+     that the user has not seen, U = 1 and U = 16 users, the same protocol:
+       A  rank_candidates(history, catalogue, top_k=K + valid history length) with the catalogue passed from the host, then the
+          seen items dropped and the rest cut to K in numpy;
+       B  set_catalogue once, then recommend(history, K): rsx_predict_din_rank_shared over the resident catalogue and
+          rsx_topk_rows_excl (csrc/topk_excl.hip), the whole request ONE captured graph, one copy back.
+     Both must return the same items (asserted).  Device time = hipEvents around replays (A: the state's zeroing and the 16 chunk
+     graphs; B: its one graph); wall time = host arrays in, host result out.
+
 FLOPs of a request, from shapes: 2 x C x valid positions x (K x 80 + 80 x 40 + 40) per attention (the folded first layer), both
 attentions; the user-side and candidate-side terms and the tower are not counted."""
 import argparse
@@ -205,6 +214,77 @@ def bench_topk(pred, sizes, k, a):
     return out
 
 
+def recommend_request(U, seed):
+    """U users' histories (synthetic.din_batch) and the whole catalogue: every item 1 .. N_ITEM - 1 once, a fixed category each."""
+    from recsys_amd import din, synthetic
+    rng = np.random.default_rng(seed)
+    h = synthetic.din_batch(rng, U, P)
+    items = np.arange(1, din.N_ITEM, dtype=np.int32)
+    cates = rng.integers(1, din.N_CATE, len(items)).astype(np.int32)
+    return h["u_iid_seq"].astype(np.int32), h["u_icat_seq"].astype(np.int32), items, cates
+
+
+def recommend_a(pred, req, k):
+    """What a caller does without `recommend`: the catalogue passed from the host, top_k over-fetched by the longest valid
+    history, then the seen items dropped and the rest cut to k in numpy -> items [U, k]."""
+    hi, hc, ci, cc = req
+    over = k + int((hi > 0).sum(1).max())
+    out = pred.rank_candidates(hi, hc, ci, cc, top_k=over)
+    items = np.take_along_axis(ci, out["index"].astype(np.int64), 1)
+    res = np.empty((len(hi), k), np.int32)
+    for u in range(len(hi)):
+        res[u] = items[u][~np.isin(items[u], hi[u][hi[u] > 0])][:k]
+    return res
+
+
+def recommend_b(pred, req, k):
+    return pred.recommend(req[0], req[1], k)["item"]
+
+
+def bench_recommend(pred, k, a):
+    """A against B for U = 1 and U = 16 users over the whole catalogue, alternating, medians and spread of --repeats rounds."""
+    import torch
+    out = []
+    for U in (1, 16):
+        hi, hc, items, cates = recommend_request(U, 300 + U)
+        pred.set_catalogue(items, cates)
+        req = (hi, hc, np.tile(items, (U, 1)), np.tile(cates, (U, 1)))     # A ships [U, N] candidates with every request
+        for _ in range(3):                                     # eager, capture, replay -- before any timing
+            ra, rb = recommend_a(pred, req, k), recommend_b(pred, req, k)
+        assert pred.topk_path == "device" and pred.recommend_path == "device"
+        assert np.array_equal(ra, rb), U                        # the same items in the same order
+        N, over = len(items), k + int((hi > 0).sum(1).max())
+        ns = [min(pred.max_candidates, N - s) for s in range(0, N, pred.max_candidates)]
+        ga = [pred._graphs[("rank_topk", U, n, over)]["graph"] for n in ns]
+        gb = [g["graph"] for key, g in pred._graphs.items() if key[0] == "recommend" and key[1:3] == (U, k)]
+        assert len(gb) == 1
+        nrep = max(10, min(a.replays, int(5e5 / max(time_request_graphs(pred, gb, 5, False), 1.0))))
+        nw = max(5, min(a.wall_calls, nrep))
+        ta, tb, wa, wb = [], [], [], []
+        for _ in range(a.repeats):                             # the contenders alternate within every round
+            recommend_a(pred, req, k)                           # (the static buffers hold this request on A's side)
+            ta.append(time_request_graphs(pred, ga, nrep, True))
+            tb.append(time_request_graphs(pred, gb, nrep, False))
+        for _ in range(a.repeats):
+            wa.append(time_wall(lambda p, r: recommend_a(p, r, k), pred, req, nw))
+            wb.append(time_wall(lambda p, r: recommend_b(p, r, k), pred, req, nw))
+        med = lambda x: float(np.median(x))
+        spread = lambda x: max(x) - min(x)
+        rec = {"users": U, "catalogue": N, "top_k": k, "A_top_k": over, "chunks": len(ns), "A_graphs": len(ga), "B_graphs": 1,
+               "A_device_us": round(med(ta), 3), "B_device_us": round(med(tb), 3), "device_B_minus_A_us": round(med(tb) - med(ta), 3),
+               "A_device_repeats_us": [round(x, 3) for x in ta], "B_device_repeats_us": [round(x, 3) for x in tb],
+               "device_accepted": bool(med(ta) - med(tb) > max(spread(ta), spread(tb))),
+               "A_wall_us": round(med(wa), 1), "B_wall_us": round(med(wb), 1), "wall_B_over_A": round(med(wb) / med(wa), 4),
+               "A_wall_repeats_us": [round(x, 1) for x in wa], "B_wall_repeats_us": [round(x, 1) for x in wb],
+               "wall_accepted": bool(med(wa) - med(wb) > max(spread(wa), spread(wb))),
+               "A_request_bytes_host_to_device": int(8 * U * N + 8 * U * P), "B_request_bytes_host_to_device": int(8 * U * P + 4 * U * 128),
+               "history_valid_positions_max": over - k, "replays": nrep, "wall_calls": nw}
+        out.append(rec)
+        print(json.dumps(rec), flush=True)
+    torch.cuda.synchronize()
+    return out
+
+
 def time_replays(graph, n):
     import torch
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -250,7 +330,9 @@ def main():
     p.add_argument("--profile-requests", dest="profile_requests", type=int, default=200)
     p.add_argument("--kernel-stats", dest="kernel_stats", default=None)
     p.add_argument("--top_k", type=int, default=0, help="compare the top-k request: host selection against rank_candidates(top_k=K)")
-    p.add_argument("--max_candidates", type=int, default=4096, help="--top_k: candidates per rank launch")
+    p.add_argument("--max_candidates", type=int, default=4096, help="--top_k / --recommend: candidates per rank launch")
+    p.add_argument("--recommend", action="store_true",
+                   help="compare the whole-catalogue request without seen items: over-fetch + numpy filter against Predictor.recommend")
     a = p.parse_args()
     if a.kernel_stats and a.top_k:                # the selection launch next to the rank launch, from the trace
         st = kernel_stats(a.kernel_stats)
@@ -290,7 +372,9 @@ def main():
         a.sizes = "200,4096,63001"
     sizes = [int(s) for s in a.sizes.split(",")] if not a.profile_run else [a.profile_run]
     with tempfile.TemporaryDirectory() as tmp:
-        pred = build(dev, a.max_candidates if a.top_k else max(sizes), os.path.join(tmp, "export"))
+        pred = build(dev, a.max_candidates if a.top_k or a.recommend else max(sizes), os.path.join(tmp, "export"))
+    if a.recommend:
+        return bench_recommend(pred, a.top_k or 100, a)
     if a.top_k and a.profile_run:
         pred.use_hip_graph = False                                      # eager: the launches appear in the trace under their names
         req = request(a.profile_run, 100 + a.profile_run)
