@@ -853,6 +853,29 @@ int rsx_topk_rows_excl(const float* scores, int ld, const int32_t* cand_id, cons
                        float* out_val, int32_t* out_idx, int32_t* state, rsx_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Ranks of given targets among rows of scores, by counting (since rsx_version() 105; csrc/rank_count.hip).  In the ORDER of
+ * rsx_topk_rows and with the exclusion rule of rsx_topk_rows_excl: for row u and slot t with tgt_pos[u, t] >= 0, count[u, t] is
+ * INCREASED by the number of columns j < n such that
+ *   - column j is not excluded: cand_id[j] ([n], shared by the rows) equals no positive entry of excl[u, :E], and
+ *   - (scores[u, j], first_index + j) comes before (tgt_score[u, t], tgt_pos[u, t]) in that order: the higher score, equal
+ *     scores (-0.0 == +0.0) by the lower index, every NaN after every number.
+ * Slots with tgt_pos < 0 are left untouched.  The caller zeroes count [U, T] when a request starts and calls once per chunk of
+ * the column axis with that chunk's first_index; after the last chunk count[u, t] is the 0-based rank of the target among the
+ * row's eligible columns.  The target's own column (index == tgt_pos) compares equal and is not counted; a column with the
+ * target's score at a higher index is not counted either.  tgt_score / tgt_pos: [U, T].  scores: row u at scores + u * ld.
+ * One workgroup per (row, slice of 512 columns); the T keys in registers; per-thread integer counters, a wave reduction, one
+ * integer atomicAdd per (workgroup, slot).  Integer sums: deterministic.  No workspace, no grid-wide step, no floating-point
+ * atomics; a row's counts depend on its scores, cand_id, its excl row and its targets only.
+ * RSX_EINVAL (before any HIP call): a NULL pointer (excl may be NULL when E = 0), U / n / T <= 0, ld < n, E < 0,
+ * first_index < 0.  Envelope (rsx_rank_count_rows_supported; RSX_EUNSUPPORTED outside, before any HIP call): T <= 32, E <= 256,
+ * first_index + n < 2^31 - 1.
+ * ------------------------------------------------------------------------------------------- */
+int rsx_rank_count_rows_supported(int n, int T, int E);
+int rsx_rank_count_rows(const float* scores, int ld, const int32_t* cand_id, int first_index, const int32_t* excl, int E,
+                        const float* tgt_score, const int32_t* tgt_pos, int T, int32_t* count, int U, int n,
+                        rsx_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
  * DCN cross layers, dcn/dcn.py:132-142: x_{l+1} = (x_l . w_l) * x0 + x_l + b_l, all L
  * layers fused per example.  dim % 4 == 0, dim <= 1024, L <= 8.
  * ------------------------------------------------------------------------------------------- */

@@ -41,6 +41,35 @@ __device__ __forceinline__ unsigned long long tk_key(const float v, const int id
 
 __device__ __forceinline__ int tk_index(const unsigned long long key) { return (int)(~((unsigned)key >> 1) & 0x7fffffffu); }
 
+// The exclusion list of a row (EXCL; rank_count.hip uses the same two steps).  tk_excl_sort: the E ids of `ex` rank-sorted into
+// LDS at exs, with `raw` (LDS, E words) as the unsorted copy; every thread of the workgroup calls it, and a barrier must follow
+// before exs is read.  tk_excluded: whether `id` is a positive entry of the sorted list -- a binary search, <= 8 LDS reads.
+__device__ __forceinline__ void tk_excl_sort(const int32_t* ex, const int E, int* raw, int* exs, const int tid, const int NT) {
+  for (int t = tid; t < E; t += NT) {
+    const int v = ex[t];
+    raw[t] = v > 0 ? v : 0;
+  }
+  __syncthreads();
+  for (int t = tid; t < E; t += NT) {
+    const int v = raw[t];
+    int rank = 0;
+    for (int j = 0; j < E; ++j) {
+      const int o = raw[j];
+      rank += (o < v || (o == v && j < t)) ? 1 : 0;
+    }
+    exs[rank] = v;
+  }
+}
+
+__device__ __forceinline__ bool tk_excluded(const int* exs, const int E, const int id) {
+  int lo = 0, hi = E;                                                // lower bound of id in exs
+  while (lo < hi) {
+    const int mid = (lo + hi) >> 1;
+    if (exs[mid] < id) lo = mid + 1; else hi = mid;
+  }
+  return id > 0 && lo < E && exs[lo] == id;
+}
+
 template <bool EXCL, class Args>
 __device__ __forceinline__ void topk_rows_body(const Args& p, unsigned long long* tk_lds) {
   unsigned long long* keys = tk_lds;
@@ -81,39 +110,13 @@ __device__ __forceinline__ void topk_rows_body(const Args& p, unsigned long long
     const int E = p.E;
     int* exs = reinterpret_cast<int*>(base + p.oExcl);
     if (tid == 0) misc[4] = 0u;
-    if (E > 0) {
-      const int32_t* ex = p.excl + row * (size_t)E;
-      int* raw = reinterpret_cast<int*>(hist);
-      for (int t = tid; t < E; t += NT) {
-        const int v = ex[t];
-        raw[t] = v > 0 ? v : 0;
-      }
-      __syncthreads();
-      for (int t = tid; t < E; t += NT) {
-        const int v = raw[t];
-        int rank = 0;
-        for (int j = 0; j < E; ++j) {
-          const int o = raw[j];
-          rank += (o < v || (o == v && j < t)) ? 1 : 0;
-        }
-        exs[rank] = v;
-      }
-    }
+    if (E > 0) tk_excl_sort(p.excl + row * (size_t)E, E, reinterpret_cast<int*>(hist), exs, tid, NT);
     __syncthreads();
     // An excluded score takes key 0: below every real key (tk_key gives 0 only for a NaN at index 2^31 - 1, which the contract
     // rules out), so it is never among the `want` largest when want counts the kept keys only.
     unsigned kept = 0u;
     for (int j = tid; j < n; j += NT) {
-      bool out = false;
-      if (E > 0) {
-        const int id = p.cand_id[j];
-        int lo = 0, hi = E;                                          // lower bound of id in exs
-        while (lo < hi) {
-          const int mid = (lo + hi) >> 1;
-          if (exs[mid] < id) lo = mid + 1; else hi = mid;
-        }
-        out = id > 0 && lo < E && exs[lo] == id;
-      }
+      const bool out = E > 0 && tk_excluded(exs, E, p.cand_id[j]);
       keys[filled + j] = out ? 0ull : tk_key(sc[j], next0 + j);
       kept += out ? 0u : 1u;
     }

@@ -47,6 +47,12 @@ The reference exports a SavedModel whose serving signature parses serialized `tf
               per chunk rsx_predict_din_rank_shared (one candidate list for all users) and rsx_topk_rows_excl
               (csrc/topk_excl.hip), the whole request ONE graph, only histories and exclusion ids shipped; "host":
               `rank_candidates` over the catalogue, then `recommend_host`.  The same bits either way.
+              `evaluate_recommend(u_iid_seq, u_icat_seq, held_out, ks)` scores that list offline: the exact 0-based rank of every
+              held-out item among the eligible catalogue entries (`target_ranks_host` is the definition) and HR / Recall / NDCG @k
+              and MRR from the ranks (`ranking_metrics`).  evaluate_recommend_path_for(T) == "device": per block of users ONE
+              graph -- the targets' scores, then per chunk rsx_predict_din_rank_shared and rsx_rank_count_rows
+              (csrc/rank_count.hip) -- and 8 bytes per (user, slot) copied back; "host": `rank_candidates` over the catalogue,
+              then `target_ranks_host`.  The same integers and probability bits either way.
 """
 import ctypes as C
 import importlib
@@ -573,6 +579,130 @@ def _one_user(out):
     return {"prob": out["prob"][0, :c], "item": out["item"][0, :c], "index": out["index"][0, :c], "count": c}
 
 
+# ---- offline ranking metrics over the catalogue (din.py): pure numpy, no device -------------------------------------------
+RANK_MISSING = -1                     # a held-out id that is not in the catalogue, or whose entry is itself excluded
+RANK_PAD = -2                         # a padding slot of held_out (id <= 0)
+RANK_MAX_T = 32                       # include/rsx.h rsx_rank_count_rows: the most targets of a user on the device
+
+
+def catalogue_first_positions(cat_item):
+    """cat_item int [N] -> (the distinct ids ascending, int64; the LOWEST catalogue position of each, int64): the index that
+    resolves a held-out id to its target entry."""
+    ids, first = np.unique(np.asarray(cat_item).astype(np.int64), return_index=True)
+    return ids, first.astype(np.int64)
+
+
+def check_held_out(held_out, U, single, what="target_ranks_host"):
+    """held_out: integers, [T] for the one-user form and [U, T] otherwise, T >= 1; no positive id twice in a row -> int64
+    [U, T].  RsxError otherwise."""
+    h = held_out.detach().cpu().numpy() if hasattr(held_out, "detach") else np.asarray(held_out)
+    if not np.issubdtype(h.dtype, np.integer):
+        raise _lib.RsxError("%s: held_out must hold integers, not %s" % (what, h.dtype))
+    if h.ndim != (1 if single else 2) or (not single and h.shape[0] != U) or h.shape[-1] < 1:
+        raise _lib.RsxError("%s: held_out %s does not match the request: [T] for one user, [U, T] for U = %d users, T >= 1"
+                            % (what, tuple(h.shape), U))
+    h = h.reshape(U, -1).astype(np.int64)
+    for u in range(U):
+        pos = h[u][h[u] > 0]
+        if len(np.unique(pos)) != len(pos):
+            raise _lib.RsxError("%s: held_out names an item twice for user %d" % (what, u))
+    return h
+
+
+def _target_positions(index, held):
+    """held int64 [U, T] -> int64 [U, T]: the target entry's catalogue position, RANK_MISSING for an id the catalogue does not
+    hold, RANK_PAD for padding.  index: `catalogue_first_positions`."""
+    ids, first = index
+    at = np.minimum(np.searchsorted(ids, held), len(ids) - 1)
+    pos = np.where(ids[at] == held, first[at], RANK_MISSING)
+    return np.where(held > 0, pos, RANK_PAD)
+
+
+def target_ranks_host(prob, cat_item, hist_item, held_out, exclude=None, exclude_seen=True):
+    """The definition of `Predictor.evaluate_recommend`'s ranks, in numpy.  prob: float32 [N] (one user) or [U, N], the scores
+    of the N catalogue entries; cat_item: int [N]; hist_item: [P'] / [U, P']; held_out: int [T] / [U, T], ids <= 0 are padding;
+    exclude: None or [E'] / [U, E'].  For every non-padding id the TARGET ENTRY is the lowest catalogue position that holds it,
+    and its rank is the number of ELIGIBLE entries that come before the target entry in `recommend_host`'s order (a higher
+    score first, equal scores -- -0.0 == +0.0 -- by the lower position, every NaN after every number): 0-based, the index at
+    which that position stands in recommend_host(..., top_k=N)['index'].  Eligibility is recommend_host's: an entry is excluded
+    when its item id is a positive id of the history (if exclude_seen) or of `exclude`.  The user's other held-out items stay
+    eligible and compete.  -> int32 [U, T] ([T] for one user): the rank, RANK_MISSING (-1) for an id that is not in the
+    catalogue or whose entry is excluded, RANK_PAD (-2) for padding.  The same positive id twice in a row: RsxError.
+    Written by counting, not by sorting: entry j precedes the target p when score[j] > score[p], or they are equal and j < p;
+    when score[p] is a NaN, every number precedes it and so do the NaNs at lower positions."""
+    a = np.asarray(prob, np.float32)
+    cat = np.asarray(cat_item)
+    if a.ndim not in (1, 2) or cat.ndim != 1 or a.shape[-1] != cat.shape[0] or cat.shape[0] < 1:
+        raise _lib.RsxError("target_ranks_host: expected scores [N] or [U, N] over a catalogue [N], N >= 1; got %s and %s" % (a.shape, cat.shape))
+    rows = np.atleast_2d(a)
+    U, N = rows.shape
+    held = check_held_out(held_out, U, a.ndim == 1)
+    ids = _exclusion_ids(hist_item, exclude, U, exclude_seen)
+    pos = _target_positions(catalogue_first_positions(cat), held)
+    where = np.arange(N)
+    out = np.where(pos >= 0, RANK_MISSING, pos).astype(np.int32)
+    for u in range(U):
+        eligible = ~np.isin(cat, ids[u][ids[u] > 0])
+        s, nan = rows[u], np.isnan(rows[u])
+        for t in np.flatnonzero(pos[u] >= 0):
+            p = int(pos[u, t])
+            if not eligible[p]:
+                continue
+            before = ~nan | (where < p) if nan[p] else (s > s[p]) | ((s == s[p]) & (where < p))
+            out[u, t] = np.count_nonzero(before & eligible)
+    return out if a.ndim == 2 else out[0]
+
+
+def check_ks(ks):
+    """`ranking_metrics`' ks -> a list of ints; RsxError unless every one is an integer (no bool) >= 1."""
+    try:
+        ks = list(ks)
+    except TypeError:
+        raise _lib.RsxError("ranking_metrics: ks must be an iterable of integers >= 1, not %r" % (ks,))
+    for k in ks:
+        if isinstance(k, (bool, np.bool_)) or not isinstance(k, (int, np.integer)) or int(k) < 1:
+            raise _lib.RsxError("ranking_metrics: ks must hold integers >= 1, not %r" % (k,))
+    return [int(k) for k in ks]
+
+
+def ranking_metrics(rank, ks, per_user=False):
+    """rank: int [U, T] (or [T], one user) from `target_ranks_host` / `evaluate_recommend`; ks: integers >= 1.  In float64, per
+    user first, then the mean over the users with at least one non-padding slot (NaN when there is none).  With n_u the
+    non-padding slots of user u (RANK_MISSING slots count: they are misses) and hits_k the slots with 0 <= rank < k:
+      'HR@k'      hits_k > 0
+      'Recall@k'  hits_k / min(k, n_u)
+      'NDCG@k'    sum over the hits of 1 / log2(rank + 2), over the sum for i < min(k, n_u) of 1 / log2(i + 2) (binary relevance)
+      'MRR'       1 / (1 + the lowest non-negative rank), 0 without one
+    and 'users' (those users) and 'missing' (the RANK_MISSING slots).  per_user=True adds the per-user float64 [U] arrays under
+    the same keys suffixed '_user' (NaN for a user without a slot)."""
+    ks = check_ks(ks)
+    r = np.asarray(rank)
+    if r.ndim not in (1, 2) or not np.issubdtype(r.dtype, np.integer) or r.size < 1 or int(r.min()) < RANK_PAD:
+        raise _lib.RsxError("ranking_metrics: rank must be integers >= %d of shape [T] or [U, T], T >= 1, got %s %s" % (RANK_PAD, r.dtype, r.shape))
+    r = np.atleast_2d(r).astype(np.int64)
+    n_u = np.count_nonzero(r != RANK_PAD, axis=1)
+    users = n_u > 0
+    found = r >= 0
+    gain = np.where(found, 1.0 / np.log2(np.where(found, r, 0) + 2.0), 0.0)
+    ideal = np.concatenate([[0.0], np.cumsum(1.0 / np.log2(np.arange(r.shape[1]) + 2.0))])     # ideal[m]: m hits at ranks 0 .. m - 1
+    per = {}
+    with np.errstate(invalid="ignore", divide="ignore"):
+        for k in ks:
+            hit = found & (r < k)
+            m = np.minimum(k, n_u)
+            per["HR@%d" % k] = np.where(users, (hit.sum(1) > 0).astype(np.float64), np.nan)
+            per["Recall@%d" % k] = np.where(users, hit.sum(1) / m.astype(np.float64), np.nan)
+            per["NDCG@%d" % k] = np.where(users, np.where(hit, gain, 0.0).sum(1) / ideal[m], np.nan)
+        best = np.where(found, r, np.iinfo(np.int64).max).min(1)
+        per["MRR"] = np.where(users, np.where(found.any(1), 1.0 / (1.0 + np.where(found.any(1), best, 0)), 0.0), np.nan)
+    out = {"users": int(users.sum()), "missing": int(np.count_nonzero(r == RANK_MISSING))}
+    for key, v in per.items():
+        out[key] = float(v[users].mean()) if users.any() else float("nan")
+        if per_user:
+            out[key + "_user"] = v
+    return out
+
+
 # ---- Predictor ---------------------------------------------------------------------------------------------------------------
 class Predictor:
     """An exported model ready to answer requests.  See the module docstring for the two paths.  `table_dtype` is the
@@ -636,6 +766,7 @@ class Predictor:
         self._rank = None
         self.catalogue_size = None          # N of the latest `set_catalogue` (din.py bundles)
         self.recommend_path = None          # where the latest `recommend` selected
+        self.evaluate_recommend_path = None # where the latest `evaluate_recommend` ranked
         self._cat = None
         if self.script == "din":
             self.rank_path = "fused" if self._rank_supported() else "layers"
@@ -888,9 +1019,10 @@ class Predictor:
             # request buffers of one chunk: the histories [U, P], the candidates and their probabilities [U, max_candidates]
             # (a request of fewer users or candidates uses leading parts of them; graphs captured over smaller buffers go)
             dev, i32 = self.device, torch.int32
-            self._drop_graphs("rank", "rank_topk", "recommend")
+            self._drop_graphs("rank", "rank_topk", "recommend", "eval_recommend")
             r.pop("topk", None)
             r.pop("rec", None)
+            r.pop("eval", None)
             r["hist"] = [torch.zeros(U * P, dtype=i32, device=dev) for _ in range(2)]
             r["cand"] = [torch.zeros(U * self.max_candidates, dtype=i32, device=dev) for _ in range(2)]
             r["prob"] = torch.zeros(U * self.max_candidates, dtype=torch.float32, device=dev)
@@ -1065,8 +1197,9 @@ class Predictor:
         self._need_din("set_catalogue")
         _, n_item, n_cate, _ = self._din_sizes()
         ci, cc = check_catalogue(i_id, i_cate, n_item, n_cate)
-        self._drop_graphs("recommend")
-        self._cat = {"host": (ci, cc), "dev": [torch.from_numpy(x).to(self.device) for x in (ci, cc)]}
+        self._drop_graphs("recommend", "eval_recommend")
+        self._cat = {"host": (ci, cc), "dev": [torch.from_numpy(x).to(self.device) for x in (ci, cc)],
+                     "first": catalogue_first_positions(ci)}       # id -> its lowest position (evaluate_recommend)
         self.catalogue_size = int(ci.shape[0])
 
     def _recommend_on_device(self, k):
@@ -1154,6 +1287,23 @@ class Predictor:
         """Columns of the exclusion buffer a request of `cols` ids per user uses (a graph is keyed by it)."""
         return 0 if cols == 0 else next(c for c in (32, 64, 128, EXCL_MAX) if cols <= c)
 
+    @classmethod
+    def _device_exclusion(cls, ids):
+        """ids: int64 [U, E''] (`_exclusion_ids`) -> int32 [U, capacity], the list the device takes (padding and ids no int32
+        catalogue can hold as 0), or None when a user names more than 256 distinct positive ids."""
+        U = ids.shape[0]
+        ids = np.where((ids > 0) & (ids < 2 ** 31), ids, 0)
+        if ids.shape[1] > EXCL_MAX:                                  # more columns than the kernel takes: the distinct ids may fit
+            rows = [np.unique(x[x > 0]) for x in ids]
+            if max(len(x) for x in rows) > EXCL_MAX:
+                return None
+            ids = np.zeros((U, max(len(x) for x in rows)), np.int64)
+            for u, x in enumerate(rows):
+                ids[u, :len(x)] = x
+        padded = np.zeros((U, cls._excl_capacity(ids.shape[1])), np.int32)
+        padded[:, :ids.shape[1]] = ids
+        return padded
+
     def recommend(self, u_iid_seq, u_icat_seq, top_k, exclude_seen=True, exclude=None):
         """din.py bundles, after `set_catalogue`: the top_k best catalogue entries for ONE user's history ([P']) or for U users
         ([U, P']), every entry scored exactly as `rank_candidates` scores it, without the entries whose item id is a positive
@@ -1176,20 +1326,9 @@ class Predictor:
         one = np.zeros((shape[0], 1) if len(shape) == 2 else 1, np.int32)      # a stand-in candidate: the histories' checks
         U, _, Pq, single = check_rank_request(u_iid_seq, u_icat_seq, one, one, P, n_item, n_cate)
         ids = _exclusion_ids(u_iid_seq, exclude, U, exclude_seen)
-        on_device = self._recommend_on_device(k)
-        if on_device:
-            ids = np.where((ids > 0) & (ids < 2 ** 31), ids, 0)
-            if ids.shape[1] > EXCL_MAX:                              # more columns than the kernel takes: the distinct ids may fit
-                rows = [np.unique(x[x > 0]) for x in ids]
-                on_device = max(len(x) for x in rows) <= EXCL_MAX
-                if on_device:
-                    ids = np.zeros((U, max(len(x) for x in rows)), np.int64)
-                    for u, x in enumerate(rows):
-                        ids[u, :len(x)] = x
-        if on_device:
+        padded = self._device_exclusion(ids) if self._recommend_on_device(k) else None
+        if padded is not None:
             self.recommend_path = "device"
-            padded = np.zeros((U, self._excl_capacity(ids.shape[1])), np.int32)
-            padded[:, :ids.shape[1]] = ids
             out = self._recommend_device(U, k, P, Pq, u_iid_seq, u_icat_seq, padded)
         else:
             self.recommend_path = "host"
@@ -1198,6 +1337,153 @@ class Predictor:
             prob = self.rank_candidates(u_iid_seq, u_icat_seq, *cand)["prob"]
             return recommend_host(prob, ci, u_iid_seq, exclude, k, exclude_seen)
         return _one_user(out) if single else out
+
+    # -- offline ranking metrics over the resident catalogue (din.py; csrc/rank_count.hip) -----------------------------------
+    def _evaluate_on_device(self, T):
+        return self.rank_path == "fused" and T <= RANK_MAX_T and bool(_lib.lib().rsx_rank_count_rows_supported(1, T, 0))
+
+    def evaluate_recommend_path_for(self, T):
+        """Where `evaluate_recommend` ranks T held-out items per user on this Predictor: "device" or "host" (None for a bundle
+        that ranks no candidates).  A pure function of the bundle and T; a request that names more than 256 distinct positive
+        exclusion ids for one user still takes the host path, and `evaluate_recommend_path` records what the latest took."""
+        if self.script != "din":
+            return None
+        if isinstance(T, (bool, np.bool_)) or not isinstance(T, (int, np.integer)) or int(T) < 1:
+            raise _lib.RsxError("evaluate_recommend: T must be an integer >= 1, not %r" % (T,))
+        return "device" if self._evaluate_on_device(int(T)) else "host"
+
+    @staticmethod
+    def _target_capacity(T):
+        """Columns of the target buffers a request of T held-out items per user uses (a graph is keyed by it; the capacities
+        are the forms rsx_rank_count_rows is compiled in)."""
+        return next(c for c in (1, 8, RANK_MAX_T) if T <= c)
+
+    def _eval_setup(self):
+        """The static buffers of a device `evaluate_recommend` beside the rank buffers, for the users the rank buffers hold and
+        32 targets each: ONE flat buffer with count [U, T] and, behind it, tgt_score [U, T] of the block at hand (so both come
+        back in one copy); one with the targets' item ids, categories and positions, three [U, T] (one copy up); the exclusion
+        ids [U, 256]."""
+        import torch
+        r = self._rank
+        t = r.get("eval")
+        if t is None:
+            n = r["U"] * RANK_MAX_T
+            t = r["eval"] = {"buf": torch.zeros(2 * n, dtype=torch.float32, device=self.device),
+                             "tgt": torch.zeros(3 * n, dtype=torch.int32, device=self.device),
+                             "excl": torch.zeros(r["U"] * EXCL_MAX, dtype=torch.int32, device=self.device)}
+        return t
+
+    def _eval_launch(self, U, T, E):
+        """One block of users, one chain: count's zeroing, the targets' own scores (one rsx_predict_din_rank launch over
+        [U, T] pairs), then for every chunk of max_candidates catalogue entries the shared rank launch and the count of the
+        entries that precede each target.  Every address is fixed, so `_run` captures it as ONE graph per (U, T, E)."""
+        import torch
+        r, t, L = self._rank, self._rank["eval"], _lib.lib()
+        cat_i, cat_c = (x.data_ptr() for x in self._cat["dev"])
+        N, mc, P = self.catalogue_size, self.max_candidates, self._din_sizes()[0]
+        count = t["buf"].data_ptr()
+        score = count + 4 * U * T
+        item = t["tgt"].data_ptr()
+        cate, pos = item + 4 * U * T, item + 8 * U * T
+        hist_i, hist_c = r["hist"][0].data_ptr(), r["hist"][1].data_ptr()
+        t["buf"][:U * T].zero_()
+        stream = torch.cuda.current_stream().cuda_stream
+        _lib.check(L.rsx_predict_din_rank(C.byref(r["model"]), hist_i, hist_c, item, cate, score, int(U), int(T), P, stream),
+                   "rsx_predict_din_rank")
+        for s in range(0, N, mc):
+            n = min(mc, N - s)
+            _lib.check(L.rsx_predict_din_rank_shared(C.byref(r["model"]), hist_i, hist_c, cat_i + 4 * s, cat_c + 4 * s,
+                                                     r["prob"].data_ptr(), int(U), int(n), P, stream), "rsx_predict_din_rank_shared")
+            _lib.check(L.rsx_rank_count_rows(r["prob"].data_ptr(), int(n), cat_i + 4 * s, int(s), t["excl"].data_ptr(), int(E),
+                                             score, pos, int(T), count, int(U), int(n), stream), "rsx_rank_count_rows")
+
+    def _eval_device_block(self, hi, hc, P, Pq, excl, tgt):
+        """hi, hc: int32 [U, P'] tensors; excl: int32 [U, E] host; tgt: int32 [3, U, T] host (item, category, position; T a
+        target capacity) -> (count int32 [U, T], tgt_score float32 [U, T]) of one block of users."""
+        import torch
+        _, U, T = tgt.shape
+        E = int(excl.shape[1])
+        with torch.no_grad():
+            r = self._rank
+            t = self._eval_setup()
+            self._rank_histories(r, U, P, Pq, hi, hc)
+            if E:
+                t["excl"][:U * E].view(U, E).copy_(torch.from_numpy(excl), non_blocking=True)
+            t["tgt"][:3 * U * T].copy_(torch.from_numpy(tgt.reshape(-1)), non_blocking=True)
+            self._run(("eval_recommend", U, T, E), lambda: self._eval_launch(U, T, E))
+            h = t["buf"][:2 * U * T].cpu().numpy()                   # the ONE device-to-host copy of the block
+        return h[:U * T].view(np.int32).reshape(U, T).copy(), h[U * T:].reshape(U, T).copy()
+
+    def evaluate_recommend(self, u_iid_seq, u_icat_seq, held_out, ks=(10, 50, 100), exclude_seen=True, exclude=None,
+                           user_block=16, per_user=False):
+        """din.py bundles, after `set_catalogue`: where do each user's held-out items land in the list `recommend` would return
+        over the WHOLE catalogue?  Histories [P'] / [U, P'] and `exclude` as in `recommend`; held_out: integer item ids [T] /
+        [U, T], ids <= 0 are padding, no positive id twice for a user.  `target_ranks_host` is the definition of the ranks,
+        `ranking_metrics` of the metrics -> ranking_metrics(rank, ks, per_user) plus 'rank' (int32 [U, T] / [T]: 0-based,
+        RANK_MISSING = -1 for an id that is not in the catalogue or is itself excluded, RANK_PAD = -2 for padding) and
+        'target_prob' (float32, same shape: the target entry's probability, NaN where the rank is negative).
+        `evaluate_recommend_path_for(T)` says where a request ranks.  "device" (rank_path == "fused", T <= 32, at most 256
+        distinct positive exclusion ids per user): the host resolves every held-out id to its catalogue position and
+        eligibility and ships the histories, the exclusion ids and the targets; per block of at most `user_block` users ONE
+        captured graph per (users, target capacity, exclusion capacity) zeroes the counts, scores the targets
+        (rsx_predict_din_rank) and runs rsx_predict_din_rank_shared and rsx_rank_count_rows over every catalogue chunk; ONE
+        copy of 8 bytes per (user, slot) comes back.  "host": `rank_candidates` over the catalogue per block of users, then
+        `target_ranks_host`.  Both give the same integers and the same probability bits, whatever user_block and
+        max_candidates are."""
+        import torch
+        self._need_din("evaluate_recommend")
+        if self._cat is None:
+            raise _lib.RsxError("evaluate_recommend: no catalogue set -- call set_catalogue(i_id, i_cate) first")
+        ks = check_ks(ks)
+        if isinstance(user_block, (bool, np.bool_)) or not isinstance(user_block, (int, np.integer)) or int(user_block) < 1:
+            raise _lib.RsxError("evaluate_recommend: user_block must be an integer >= 1, not %r" % (user_block,))
+        user_block = int(user_block)
+        P, n_item, n_cate, _ = self._din_sizes()
+        shape = tuple(u_iid_seq.shape) if hasattr(u_iid_seq, "shape") else np.shape(u_iid_seq)
+        one = np.zeros((shape[0], 1) if len(shape) == 2 else 1, np.int32)      # a stand-in candidate: the histories' checks
+        U, _, Pq, single = check_rank_request(u_iid_seq, u_icat_seq, one, one, P, n_item, n_cate)
+        held = check_held_out(held_out, U, single, "evaluate_recommend")
+        T = held.shape[1]
+        ids = _exclusion_ids(u_iid_seq, exclude, U, exclude_seen)
+        ci, cc = self._cat["host"]
+        N = self.catalogue_size
+        hi, hc = (self._dev32(x, U) if Pq else torch.zeros((U, 0), dtype=torch.int32) for x in (u_iid_seq, u_icat_seq))
+        rank = np.empty((U, T), np.int32)
+        tprob = np.full((U, T), np.nan, np.float32)
+        excl = self._device_exclusion(ids) if self._evaluate_on_device(T) else None
+        if excl is not None:
+            self.evaluate_recommend_path = "device"
+            pos = _target_positions(self._cat["first"], held)
+            for u in range(U):                                       # a target whose entry is excluded has no rank
+                x = ids[u][ids[u] > 0]
+                if len(x):
+                    pos[u][(pos[u] >= 0) & np.isin(held[u], x)] = RANK_MISSING
+            ok = pos >= 0
+            Tc = self._target_capacity(T)
+            tgt = np.zeros((3, U, Tc), np.int32)                    # slots without a target: id 0, an ordinary row
+            tgt[2] = -1
+            at = np.where(ok, pos, 0)
+            tgt[0, :, :T], tgt[1, :, :T], tgt[2, :, :T] = np.where(ok, ci[at], 0), np.where(ok, cc[at], 0), np.where(ok, pos, -1)
+            self._rank_setup(min(U, user_block))
+            for b in range(0, U, user_block):
+                e = min(U, b + user_block)
+                count, score = self._eval_device_block(hi[b:e], hc[b:e], P, Pq, excl[b:e], np.ascontiguousarray(tgt[:, b:e]))
+                rank[b:e] = np.where(ok[b:e], count[:, :T], pos[b:e])
+                tprob[b:e][ok[b:e]] = score[:, :T][ok[b:e]]
+        else:
+            self.evaluate_recommend_path = "host"
+            hist_np = hi.cpu().numpy()
+            for b in range(0, U, user_block):
+                e = min(U, b + user_block)
+                cand = tuple(np.tile(x, (e - b, 1)) for x in (ci, cc))
+                prob = self.rank_candidates(hi[b:e], hc[b:e], *cand)["prob"]
+                rank[b:e] = target_ranks_host(prob, ci, hist_np[b:e], held[b:e], ids[b:e], False)      # (ids: history included)
+                pos = _target_positions(self._cat["first"], held[b:e])
+                ok = rank[b:e] >= 0
+                tprob[b:e][ok] = np.take_along_axis(prob, np.where(ok, pos, 0), 1)[ok]
+        out = ranking_metrics(rank, ks, per_user)
+        out["rank"], out["target_prob"] = (rank[0], tprob[0]) if single else (rank, tprob)
+        return out
 
     # -- public ------------------------------------------------------------------------------------------------------------
     def _parse(self, serialized):
