@@ -853,6 +853,38 @@ int rsx_topk_rows_excl(const float* scores, int ld, const int32_t* cand_id, cons
                        float* out_val, int32_t* out_idx, int32_t* state, rsx_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * rsx_topk_rows_excl with category rules (since rsx_version() 106; csrc/topk_rules.hip): the contract above with TWO additions.
+ * Every entry has a category: cate[a] for the entry of ABSOLUTE index a (next_index + j for new score j), shared by the rows.
+ * cate must cover every index fed so far in the request, [0, next_index + n), and stay unchanged over the request: the running
+ * list's entries are looked up again on every call.  G is the number of categories.
+ *   (a) ALLOW: allow [U, W], W = ceil(G / 32) words per row, bit (g & 31) of word (g >> 5) of row u set = category g is allowed
+ *       for row u.  A new score whose category's bit is clear is LEFT OUT like an excluded one.  NULL: every category allowed.
+ *   (b) CAP: 1 <= m <= 16 keeps at most m entries of one category in the list; m = 0 is no cap.  Take the entries that are
+ *       neither excluded nor disallowed, over ALL calls of the request, in the ORDER above; walk them and keep an entry unless m
+ *       kept entries of its category precede it; the list holds the first k kept ones.  (Equivalently: the top k of the entries
+ *       with fewer than m entries of their own category before them.)  The cap counts entries, not ids.  Entries of the running
+ *       list CAN leave under a later call's scores; the running list of k entries is nevertheless exact, because an entry that
+ *       left the capped top k of what was fed so far can never return.  filled = the number of entries kept, at most k: it can
+ *       stay below k while eligible entries remain.
+ * A category outside [0, G) is never used as an index: a new score that has one is left out, and so is a list entry under a cap.
+ * With allow == NULL and m == 0 (cate and G are then ignored; cate may be NULL) the outputs and the state are
+ * rsx_topk_rows_excl's, bit for bit; with E == 0 as well they are rsx_topk_rows'.
+ * ONE workgroup per row, in place, no workspace, no grid-wide step, no floating-point atomics; a row's result depends on its
+ * scores, its state, cand_id, cate, its own excl row and its own allow row only.  Under a cap the m-th largest key of every
+ * category is found by m rounds of 64-bit integer LDS atomicMax over two [G] arrays (keys are unique and max is commutative:
+ * independent of the order threads run in) and the keys' categories are cached in LDS, 16 bits each.  Deterministic.
+ * RSX_EINVAL (before any HIP call): a NULL pointer that is needed (excl may be NULL when E = 0; cate is needed when allow is
+ * given or m > 0), U / n / k <= 0, ld < n, E < 0, m < 0, G <= 0 when allow is given or m > 0.  Envelope
+ * (rsx_topk_rows_rules_supported; RSX_EUNSUPPORTED outside, before any HIP call): that of rsx_topk_rows_excl, m <= 16, and with
+ * m > 0 an LDS plan of at most 160 KB: 8 (n + k) + 16 k + 2 080 + 16 G + 2 (n + k) <= 163 840 -- for G = 802 and k = 1 024
+ * that is n + k <= 13 254.  rsx_topk_rows_rules_supported(n, k, E, G, m) with m == 0 is rsx_topk_rows_excl_supported (G >= 0).
+ * ------------------------------------------------------------------------------------------- */
+int rsx_topk_rows_rules_supported(int n, int k, int E, int G, int m);
+int rsx_topk_rows_rules(const float* scores, int ld, const int32_t* cand_id, const int32_t* excl, int E, const int32_t* cate,
+                        int G, const uint32_t* allow, int m, int U, int n, int k, float* out_val, int32_t* out_idx,
+                        int32_t* state, rsx_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Ranks of given targets among rows of scores, by counting (since rsx_version() 105; csrc/rank_count.hip).  In the ORDER of
  * rsx_topk_rows and with the exclusion rule of rsx_topk_rows_excl: for row u and slot t with tgt_pos[u, t] >= 0, count[u, t] is
  * INCREASED by the number of columns j < n such that

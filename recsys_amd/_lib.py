@@ -392,6 +392,8 @@ _SIGS = {
     "rsx_topk_rows_threads": (_I, [_I, _I]),
     "rsx_topk_rows_excl_supported": (_I, [_I, _I, _I]),
     "rsx_topk_rows_excl": (_I, [_P, _I, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P]),
+    "rsx_topk_rows_rules_supported": (_I, [_I, _I, _I, _I, _I]),
+    "rsx_topk_rows_rules": (_I, [_P, _I, _P, _P, _I, _P, _I, _P, _I, _I, _I, _I, _P, _P, _P, _P]),
     "rsx_rank_count_rows_supported": (_I, [_I, _I, _I]),
     "rsx_rank_count_rows": (_I, [_P, _I, _P, _I, _P, _I, _P, _P, _I, _P, _I, _I, _P]),
     "rsx_criteo_parse_examples_supported": (_I, [_I, _I]),

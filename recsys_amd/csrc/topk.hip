@@ -29,7 +29,7 @@ namespace {
 
 __global__ __launch_bounds__(TK_T_BIG) void topk_rows_k(const TopkArgs p) {
   extern __shared__ unsigned long long tk_lds[];
-  topk_rows_body<false>(p, tk_lds);
+  topk_rows_body<TK_PLAIN>(p, tk_lds);
 }
 
 }  // namespace

@@ -1,7 +1,8 @@
-// What the two top-k kernels share (topk.hip: rsx_topk_rows; topk_excl.hip: rsx_topk_rows_excl): the 64-bit key image of a
-// (score, index) pair, the LDS plan, and the workgroup's body -- keys, MSB-first radix select, compaction, rank by counting.
-// topk.hip's head describes the method.  EXCL = false is rsx_topk_rows; EXCL = true adds the exclusion of new scores by id
-// (topk_excl.hip's head), compiled in with `if constexpr` so the plain kernel holds none of it.
+// What the three top-k kernels share (topk.hip: rsx_topk_rows; topk_excl.hip: rsx_topk_rows_excl; topk_rules.hip:
+// rsx_topk_rows_rules): the 64-bit key image of a (score, index) pair, the LDS plan, and the workgroup's body -- keys, MSB-first
+// radix select, compaction, rank by counting.  topk.hip's head describes the method.  MODE TK_PLAIN is rsx_topk_rows; TK_EXCL
+// adds the exclusion of new scores by id (topk_excl.hip's head); TK_RULES adds the category rules on top of that
+// (topk_rules.hip's head).  Each addition is compiled in with `if constexpr`, so a kernel holds nothing of the modes above it.
 #pragma once
 #include "predict_device.h"      // launch_big_lds, PR_MAX_LDS
 
@@ -12,6 +13,8 @@ constexpr int TK_KEYS = 16384;           // largest n + k: 128 KB of keys
 constexpr int TK_T_SMALL = 256, TK_T_BIG = 1024;
 constexpr int TK_SMALL_KEYS = 1024;     // up to this many keys a workgroup of 256 threads, above it 1024
 constexpr int TK_EMAX = 256;             // largest exclusion list of a row (EXCL)
+constexpr int TK_MMAX = 16;              // largest per-category cap (RULES)
+constexpr int TK_PLAIN = 0, TK_EXCL = 1, TK_RULES = 2;
 
 struct TopkArgs {
   const float* scores;
@@ -27,6 +30,13 @@ struct TopkExclArgs : TopkArgs {
   const int32_t* excl;                   // [U, E]
   int E;
   int oExcl;                             // LDS: the row's exclusion ids, sorted [E]
+};
+
+struct TopkRulesArgs : TopkExclArgs {
+  const int32_t* cate;                   // [next_index + n]: the category of every entry fed so far, by absolute index
+  const uint32_t* allow;                 // [U, W] bitmap of the allowed categories, or null (all allowed)
+  int G, W, m;                           // categories, words of a bitmap row, cap (0: none)
+  int oThr, oCat;                        // LDS (m > 0): two [G] arrays of 64-bit thresholds; the keys' categories, 16 bits each
 };
 
 __device__ __forceinline__ unsigned long long tk_key(const float v, const int idx) {
@@ -70,15 +80,16 @@ __device__ __forceinline__ bool tk_excluded(const int* exs, const int E, const i
   return id > 0 && lo < E && exs[lo] == id;
 }
 
-template <bool EXCL, class Args>
+template <int MODE, class Args>
 __device__ __forceinline__ void topk_rows_body(const Args& p, unsigned long long* tk_lds) {
+  constexpr bool EXCL = MODE >= TK_EXCL, RULES = MODE == TK_RULES;
   unsigned long long* keys = tk_lds;
   char* base = reinterpret_cast<char*>(tk_lds);
   unsigned long long* sel = reinterpret_cast<unsigned long long*>(base + p.oSel);
   float* oldv = reinterpret_cast<float*>(base + p.oOldV);
   int* oldi = reinterpret_cast<int*>(base + p.oOldI);
   unsigned* hist = reinterpret_cast<unsigned*>(base + p.oHist);
-  unsigned* misc = reinterpret_cast<unsigned*>(base + p.oMisc);      // 0: bin, 1: rank inside the bin, 2: the bin's count, 3: compaction cursor (EXCL: 4: new scores kept)
+  unsigned* misc = reinterpret_cast<unsigned*>(base + p.oMisc);      // 0: bin, 1: rank inside the bin, 2: the bin's count, 3: compaction cursor (EXCL: 4: new scores kept; RULES: 5: keys left under the cap)
 
   const int tid = threadIdx.x, NT = blockDim.x, lane = tid & 63;
   const int n = p.n, k = p.k;
@@ -101,6 +112,20 @@ __device__ __forceinline__ void topk_rows_body(const Args& p, unsigned long long
     oldi[i] = ix;
     keys[i] = tk_key(v, ix);
   }
+  if constexpr (RULES) {
+    // Under a cap the running list's entries need their category again: from `cate` by their absolute index, into the cache.
+    // An index that is not one fed before, or a category outside [0, G), takes key 0 and indexes nothing.
+    if (p.m > 0) {
+      unsigned short* kcat = reinterpret_cast<unsigned short*>(base + p.oCat);
+      for (int i = tid; i < filled; i += NT) {
+        const int ix = oi[i];
+        const int c = (ix >= 0 && ix < next0) ? p.cate[ix] : -1;
+        const bool ok = c >= 0 && c < p.G;
+        kcat[i] = (unsigned short)(ok ? c : 0);
+        if (!ok) keys[i] = 0ull;
+      }
+    }
+  }
   if (tid == 0) misc[3] = 0u;
   int want;
   if constexpr (EXCL) {
@@ -116,7 +141,17 @@ __device__ __forceinline__ void topk_rows_body(const Args& p, unsigned long long
     // rules out), so it is never among the `want` largest when want counts the kept keys only.
     unsigned kept = 0u;
     for (int j = tid; j < n; j += NT) {
-      const bool out = E > 0 && tk_excluded(exs, E, p.cand_id[j]);
+      bool out = E > 0 && tk_excluded(exs, E, p.cand_id[j]);
+      if constexpr (RULES) {
+        // A new score also leaves when its category is outside [0, G) or its bit of the row's bitmap is clear.
+        if (p.allow || p.m > 0) {
+          const int c = p.cate[(size_t)next0 + j];
+          const bool ok = c >= 0 && c < p.G;
+          if (!ok) out = true;
+          else if (p.allow) out = out || !((p.allow[row * (size_t)p.W + (c >> 5)] >> (c & 31)) & 1u);
+          if (p.m > 0) reinterpret_cast<unsigned short*>(base + p.oCat)[filled + j] = (unsigned short)(ok ? c : 0);
+        }
+      }
       keys[filled + j] = out ? 0ull : tk_key(sc[j], next0 + j);
       kept += out ? 0u : 1u;
     }
@@ -124,6 +159,48 @@ __device__ __forceinline__ void topk_rows_body(const Args& p, unsigned long long
     __syncthreads();
     const int Te = filled + (int)misc[4];
     want = Te < k ? Te : k;
+    if constexpr (RULES) {
+      if (p.m > 0) {
+        // The cap.  thr[g] = the m-th largest key of category g in the union (0 when g holds fewer than m keys), found in m
+        // rounds: in round r every live key below its category's threshold of round r - 1 (round 0: every live key) is
+        // max-ed into the category's slot.  Keys are unique and max is commutative, so the thresholds do not depend on the
+        // order threads run in.  (The plain read before the atomic only spares the atomic where it could change nothing:
+        // a slot only grows inside a round.)  A key below its threshold has m category mates above it and takes key 0 --
+        // an entry of the running list included.  want counts what is left.
+        const int G = p.G, m = p.m;
+        unsigned long long* cur = reinterpret_cast<unsigned long long*>(base + p.oThr);
+        unsigned long long* prev = cur + G;
+        const unsigned short* kcat = reinterpret_cast<const unsigned short*>(base + p.oCat);
+        for (int g = tid; g < 2 * G; g += NT) cur[g] = 0ull;
+        if (tid == 0) misc[5] = 0u;
+        __syncthreads();
+        for (int r = 0; r < m; ++r) {
+          if (r >= 2) {                                              // this round's slots held the thresholds of round r - 2
+            for (int g = tid; g < G; g += NT) cur[g] = 0ull;
+            __syncthreads();
+          }
+          for (int i = tid; i < T; i += NT) {
+            const unsigned long long key = keys[i];
+            if (key == 0ull) continue;
+            const int c = kcat[i];
+            if (r > 0 && key >= prev[c]) continue;
+            if (key > __hip_atomic_load(&cur[c], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)) atomicMax(&cur[c], key);
+          }
+          __syncthreads();
+          unsigned long long* t = cur; cur = prev; prev = t;
+        }
+        unsigned left = 0u;
+        for (int i = tid; i < T; i += NT) {
+          const unsigned long long key = keys[i];
+          if (key == 0ull) continue;
+          if (key < prev[kcat[i]]) keys[i] = 0ull; else ++left;
+        }
+        if (left) atomicAdd(&misc[5], left);
+        __syncthreads();
+        const int Tl = (int)misc[5];
+        want = Tl < k ? Tl : k;
+      }
+    }
   } else {
     want = T < k ? T : k;
     for (int j = tid; j < n; j += NT) keys[filled + j] = tk_key(sc[j], next0 + j);
@@ -133,6 +210,7 @@ __device__ __forceinline__ void topk_rows_body(const Args& p, unsigned long long
   // The select runs when the keys outnumber the survivors.  Plain: T > k, and then want == k.  EXCL: also when excluded keys
   // (zeros) sit among no more than k kept ones (filled + kept < k < filled + n included) -- the want-th largest key is a real
   // one, every zero is smaller, and a bin that holds a zero is never "taken whole", so `key >= prefix` admits no zero.
+  // RULES: the same argument, wherever the zeros sit -- under a cap entries of the running list become zeros too.
   const int nsel = EXCL ? want : k;
   const bool select = EXCL ? (T > want && want > 0) : (T > k);
   const unsigned long long* src = keys;                            // the survivors: everything when the union is no longer than k
@@ -230,6 +308,29 @@ inline int topk_layout(TopkArgs* p) {
   p->oOldI = o; o += 4 * p->k;
   p->oHist = o; o += 4 * 256;
   p->oMisc = o; o += 16;
+  return o;
+}
+
+inline bool topk_excl_envelope(int n, int k, int E) { return topk_envelope(n, k) && E >= 0 && E <= TK_EMAX; }
+
+inline int topk_excl_layout(TopkExclArgs* p) {
+  int o = topk_layout(p);
+  o += 16;                               // misc[4 .. 7]: the count of kept scores (RULES: and of the keys left under the cap)
+  p->oExcl = o; o += 4 * TK_EMAX;
+  return o;
+}
+
+// RULES: without a cap (m == 0) the plan is rsx_topk_rows_excl's; a cap adds the two threshold arrays and the category cache.
+// -1: not a plan (m outside [0, 16], a cap without categories, or more than the LDS can ever hold).
+inline long long topk_rules_layout(TopkRulesArgs* p) {
+  long long o = topk_excl_layout(p);
+  p->oThr = p->oCat = 0;
+  if (p->m < 0 || p->m > TK_MMAX) return -1;
+  if (p->m > 0) {
+    if (p->G <= 0 || p->G > 65535) return -1;                  // (16 bits of category cache a key)
+    p->oThr = (int)o; o += 16ll * p->G;
+    p->oCat = (int)o; o += 2ll * (p->n + p->k);              // (last: nothing behind it needs an alignment)
+  }
   return o;
 }
 

@@ -18,10 +18,8 @@ namespace {
 
 __global__ __launch_bounds__(TK_T_BIG) void topk_rows_excl_k(const TopkExclArgs p) {
   extern __shared__ unsigned long long tk_lds[];
-  topk_rows_body<true>(p, tk_lds);
+  topk_rows_body<TK_EXCL>(p, tk_lds);
 }
-
-inline bool topk_excl_envelope(int n, int k, int E) { return topk_envelope(n, k) && E >= 0 && E <= TK_EMAX; }
 
 }  // namespace
 
@@ -36,9 +34,7 @@ extern "C" int rsx_topk_rows_excl(const float* scores, int ld, const int32_t* ca
   p.scores = scores; p.out_val = out_val; p.out_idx = out_idx; p.state = state;
   p.ld = ld; p.n = n; p.k = k;
   p.cand_id = cand_id; p.excl = excl; p.E = E;
-  int o = topk_layout(&p);
-  o += 16;                               // misc[4 .. 7]: the count of kept scores
-  p.oExcl = o; o += 4 * TK_EMAX;
+  const int o = topk_excl_layout(&p);
   if ((size_t)o > (size_t)PR_MAX_LDS) return RSX_EUNSUPPORTED;
   return launch_big_lds<topk_rows_excl_k>(p, (unsigned)U, topk_threads(n, k), (size_t)o, rsx_s(stream));
 }

@@ -47,6 +47,10 @@ The reference exports a SavedModel whose serving signature parses serialized `tf
               per chunk rsx_predict_din_rank_shared (one candidate list for all users) and rsx_topk_rows_excl
               (csrc/topk_excl.hip), the whole request ONE graph, only histories and exclusion ids shipped; "host":
               `rank_candidates` over the catalogue, then `recommend_host`.  The same bits either way.
+              `recommend(..., categories=, exclude_categories=, max_per_category=m)` adds category rules: only / never these
+              categories, at most m entries of one category.  On the device rsx_topk_rows_rules (csrc/topk_rules.hip) takes
+              rsx_topk_rows_excl's place, a bitmap [U, ceil(n_cate / 32)] travels with the exclusion ids, still ONE graph and
+              one copy back; `rules_on_device = False` sends such requests to the host path.  The same bits either way.
               `evaluate_recommend(u_iid_seq, u_icat_seq, held_out, ks)` scores that list offline: the exact 0-based rank of every
               held-out item among the eligible catalogue entries (`target_ranks_host` is the definition) and HR / Recall / NDCG @k
               and MRR from the ranks (`ranking_metrics`).  evaluate_recommend_path_for(T) == "device": per block of users ONE
@@ -546,7 +550,54 @@ def _exclusion_ids(hist_item, exclude, U, exclude_seen):
     return np.concatenate(parts, 1) if parts else np.zeros((U, 0), np.int64)
 
 
-def recommend_host(prob, cat_item, hist_item, exclude, top_k, exclude_seen=True):
+RULES_MAX_M = 16                      # include/rsx.h rsx_topk_rows_rules: the largest per-category cap applied on the device
+
+
+def check_max_per_category(max_per_category):
+    """`recommend`'s max_per_category -> None (no cap) or int; RsxError unless it is None or an integer (no bool) >= 1."""
+    m = max_per_category
+    if m is None:
+        return None
+    if isinstance(m, (bool, np.bool_)) or not isinstance(m, (int, np.integer)) or int(m) < 1:
+        raise _lib.RsxError("recommend: max_per_category must be None or an integer >= 1, not %r" % (m,))
+    return int(m)
+
+
+def check_category_list(x, name, U, single, n_cate=None):
+    """`recommend`'s categories / exclude_categories -> None or int64 [U, G'].  The shape convention of `exclude`: [G'] for the
+    one-user form, [U, G'] for U users; negative ids are padding, 0 is a category.  RsxError for non-integers, another shape,
+    and -- when n_cate is given -- ids >= n_cate."""
+    if x is None:
+        return None
+    c = x.detach().cpu().numpy() if hasattr(x, "detach") else np.asarray(x)
+    if (c.size and not np.issubdtype(c.dtype, np.integer)) or c.dtype == np.bool_:
+        raise _lib.RsxError("recommend: %s must hold integers, not %s" % (name, c.dtype))
+    if c.ndim != (1 if single else 2) or (not single and c.shape[0] != U):
+        raise _lib.RsxError("recommend: %s %s does not match the histories: [G] for one user, [U, G] for U = %d users"
+                            % (name, tuple(c.shape), U))
+    c = c.reshape(U, -1).astype(np.int64)
+    if n_cate is not None and c.size and int(c.max()) >= int(n_cate):
+        raise _lib.RsxError("recommend: %s holds ids outside [0, %d) (max %d); negative ids are padding" % (name, int(n_cate), int(c.max())))
+    return c
+
+
+def category_bitmap(categories, exclude_categories, n_cate):
+    """The two checked lists (`check_category_list`: int64 [U, G'] or None, at least one given) folded into the bitmap
+    rsx_topk_rows_rules takes: uint32 [U, ceil(n_cate / 32)], bit g of row u set when category g is allowed for user u."""
+    U = (categories if categories is not None else exclude_categories).shape[0]
+    ok = np.zeros((U, 32 * ((int(n_cate) + 31) // 32)), bool)
+    for u in range(U):
+        if categories is None:
+            ok[u, :int(n_cate)] = True
+        else:
+            ok[u, categories[u][categories[u] >= 0]] = True
+        if exclude_categories is not None:
+            ok[u, exclude_categories[u][exclude_categories[u] >= 0]] = False
+    return np.packbits(ok.reshape(U, -1, 32), axis=-1, bitorder="little").view(np.uint32).reshape(U, -1)
+
+
+def recommend_host(prob, cat_item, hist_item, exclude, top_k, exclude_seen=True, cat_cate=None, categories=None,
+                   exclude_categories=None, max_per_category=None, n_cate=None):
     """The definition of `Predictor.recommend`, in numpy.  prob: float32 [N] (one user) or [U, N], the scores of the N catalogue
     entries; cat_item: int [N], their item ids; hist_item: [P'] / [U, P']; exclude: None or [E'] / [U, E'].  An entry is
     EXCLUDED for user u when its item id equals a positive id of hist_item[u] (if exclude_seen) or of exclude[u]; ids <= 0 are
@@ -554,7 +605,14 @@ def recommend_host(prob, cat_item, hist_item, exclude, top_k, exclude_seen=True)
     ones by the lower position, NaN last), the first top_k of them ->
     {'prob': float32 [U, kk], 'item': int32 [U, kk], 'index': int32 [U, kk], 'count': int32 [U]}, kk = min(top_k, N),
     count[u] = min(top_k, eligible entries of u); entries at and beyond count[u] are NaN / -1 / -1.  The one-user form returns
-    the three arrays cut to count, and count as an int."""
+    the three arrays cut to count, and count as an int.
+    CATEGORY RULES (all off by default; any of them needs cat_cate: int [N], the category of every catalogue entry -- what
+    `set_catalogue` was given, not a table lookup).  categories / exclude_categories: [G'] / [U, G'] like `exclude`, negative
+    ids padding, 0 a real category, ids >= n_cate refused when n_cate is given.  An entry is ALLOWED when its category is in
+    categories[u] (if given; an empty list allows nothing) and not in exclude_categories[u] (if given); the eligible entries are
+    the allowed ones that are not excluded.  max_per_category = m (an integer >= 1): walk the eligible entries in the order
+    above and keep an entry only when fewer than m kept entries of its category precede it; stop at top_k.  The cap counts
+    entries -- an item id at two positions counts twice -- and count[u] can stay below top_k while eligible entries remain."""
     k = check_top_k(top_k)
     a = np.asarray(prob, np.float32)
     cat = np.asarray(cat_item)
@@ -563,12 +621,38 @@ def recommend_host(prob, cat_item, hist_item, exclude, top_k, exclude_seen=True)
     rows = np.atleast_2d(a)
     U, N = rows.shape
     ids = _exclusion_ids(hist_item, exclude, U, exclude_seen)
+    m = check_max_per_category(max_per_category)
+    only = check_category_list(categories, "categories", U, a.ndim == 1, n_cate)
+    deny = check_category_list(exclude_categories, "exclude_categories", U, a.ndim == 1, n_cate)
+    rules = m is not None or only is not None or deny is not None
+    if rules:
+        cc = None if cat_cate is None else np.asarray(cat_cate)
+        if cc is None or cc.shape != cat.shape or not np.issubdtype(cc.dtype, np.integer):
+            raise _lib.RsxError("recommend_host: a category rule needs cat_cate, integers [N] like cat_item; got %s"
+                                % (None if cc is None else (cc.dtype, cc.shape),))
     kk = min(k, N)
     out = {"prob": np.full((U, kk), np.nan, np.float32), "item": np.full((U, kk), -1, np.int32),
            "index": np.full((U, kk), -1, np.int32), "count": np.zeros(U, np.int32)}
     for u in range(U):
-        pos = np.flatnonzero(~np.isin(cat, ids[u][ids[u] > 0]))
-        order = pos[np.lexsort((pos, -rows[u, pos]))][:kk]
+        gone = np.isin(cat, ids[u][ids[u] > 0])
+        if only is not None:
+            gone |= ~np.isin(cc, only[u][only[u] >= 0])
+        if deny is not None:
+            gone |= np.isin(cc, deny[u][deny[u] >= 0])
+        pos = np.flatnonzero(~gone)
+        order = pos[np.lexsort((pos, -rows[u, pos]))]
+        if m is None:
+            order = order[:kk]
+        else:                                                          # the cap: the plain greedy walk
+            taken, keep = {}, []
+            for p in order:
+                g = int(cc[p])
+                if taken.get(g, 0) < m:
+                    taken[g] = taken.get(g, 0) + 1
+                    keep.append(p)
+                    if len(keep) == kk:
+                        break
+            order = np.asarray(keep, order.dtype)
         c = len(order)
         out["prob"][u, :c], out["item"][u, :c], out["index"][u, :c], out["count"][u] = rows[u, order], cat[order], order, c
     return out if a.ndim == 2 else _one_user(out)
@@ -766,6 +850,7 @@ class Predictor:
         self._rank = None
         self.catalogue_size = None          # N of the latest `set_catalogue` (din.py bundles)
         self.recommend_path = None          # where the latest `recommend` selected
+        self.rules_on_device = True         # False: a `recommend` with a category rule takes the host path
         self.evaluate_recommend_path = None # where the latest `evaluate_recommend` ranked
         self._cat = None
         if self.script == "din":
@@ -1205,26 +1290,42 @@ class Predictor:
     def _recommend_on_device(self, k):
         return self.rank_path == "fused" and k <= TOPK_MAX_K and bool(_lib.lib().rsx_topk_rows_excl_supported(1, k, 0))
 
-    def recommend_path_for(self, top_k):
+    def _rules_on_device(self, k, m):
+        """A request with a category rule (m: the cap, None or 0 for none): today's conditions, the switch, m <= 16 and
+        rsx_topk_rows_rules' envelope for this bundle's n_cate."""
+        m = int(m or 0)
+        return (self.rules_on_device and self._recommend_on_device(k) and m <= RULES_MAX_M
+                and bool(_lib.lib().rsx_topk_rows_rules_supported(1, k, 0, self._din_sizes()[2], m)))
+
+    def recommend_path_for(self, top_k, max_per_category=None, rules=False):
         """Where `recommend(..., top_k=top_k)` runs on this Predictor: "device" or "host" (None for a bundle that ranks no
         candidates).  A pure function of the bundle and k; a request that names more than 256 distinct positive ids for one
-        user still takes the host path, and `recommend_path` records what the latest request took."""
+        user still takes the host path, and `recommend_path` records what the latest request took.  With max_per_category or
+        rules=True (a request that names categories / exclude_categories) the answer is that of a request with a category
+        rule: "device" needs `rules_on_device`, a cap of at most 16 and rsx_topk_rows_rules' envelope as well."""
         if self.script != "din":
             return None
-        return "device" if self._recommend_on_device(check_top_k(top_k)) else "host"
+        k, m = check_top_k(top_k), check_max_per_category(max_per_category)
+        if m is not None or rules:
+            return "device" if self._rules_on_device(k, m) else "host"
+        return "device" if self._recommend_on_device(k) else "host"
 
-    def recommend_buffer_bytes(self, U=1, top_k=100):
+    def recommend_buffer_bytes(self, U=1, top_k=100, rules=False):
         """Bytes of the static buffers a `recommend` request of U users holds: the rank buffers, the catalogue (two int32 [N]),
-        and on the device path out_val / out_idx [U, k] with state [U, 2] behind them and the exclusion ids [U, 256]."""
+        and on the device path out_val / out_idx [U, k] with state [U, 2] behind them and the exclusion ids [U, 256]; with
+        rules=True also the category bitmap [U, ceil(n_cate / 32)] that a request with a category rule holds."""
         n = self.rank_buffer_bytes(U) + 8 * int(self.catalogue_size or 0)
         if self._recommend_on_device(check_top_k(top_k)):
             n += 4 * (2 * U * int(top_k) + 2 * U) + 4 * U * EXCL_MAX
+            if rules:
+                n += 4 * U * ((self._din_sizes()[2] + 31) // 32)
         return n
 
-    def _rec_setup(self, U, k):
+    def _rec_setup(self, U, k, rules=False):
         """The static buffers of a device `recommend` beside the rank buffers: ONE flat buffer that holds out_val [U, k], behind
         it out_idx [U, k] and state [U, 2] of the request at hand (so the answer and `filled` come back in one copy), and the
-        exclusion ids [U, 256].  Reallocated like the selection's buffers: when a request needs more than they hold."""
+        exclusion ids [U, 256].  Reallocated like the selection's buffers: when a request needs more than they hold.  The
+        category bitmap [U, ceil(n_cate / 32)] joins them with the first request that names a category rule."""
         import torch
         r = self._rank
         t = r.get("rec")
@@ -1233,12 +1334,16 @@ class Predictor:
             t = r["rec"] = {"pairs": r["U"] * k,
                             "buf": torch.zeros(2 * r["U"] * k + 2 * r["U"], dtype=torch.float32, device=self.device),
                             "excl": torch.zeros(r["U"] * EXCL_MAX, dtype=torch.int32, device=self.device)}
+        if rules and "allow" not in t:
+            t["allow"] = torch.zeros(r["U"] * ((self._din_sizes()[2] + 31) // 32), dtype=torch.int32, device=self.device)
         return t
 
-    def _recommend_launch(self, U, k, E):
+    def _recommend_launch(self, U, k, E, rules=None):
         """The whole request, one chain: the state's zeroing, then for every chunk of max_candidates catalogue entries the
         shared rank launch and the filtered selection (sliced as `_rank_topk_launch` slices it beyond n + k = 16 384).  Every
-        address is fixed -- the catalogue's slices included -- so `_run` captures it as ONE graph per (U, k, E)."""
+        address is fixed -- the catalogue's slices included -- so `_run` captures it as ONE graph per (U, k, E).
+        rules = (bitmap present, m) for a request with a category rule: rsx_topk_rows_rules in rsx_topk_rows_excl's place,
+        sliced by its own envelope, with the resident categories from position 0 and the bitmap buffer (or no bitmap)."""
         import torch
         r, t, L = self._rank, self._rank["rec"], _lib.lib()
         cat_i, cat_c = (x.data_ptr() for x in self._cat["dev"])
@@ -1253,6 +1358,16 @@ class Predictor:
                                                      cat_i + 4 * s, cat_c + 4 * s, r["prob"].data_ptr(), int(U), int(n), P, stream),
                        "rsx_predict_din_rank_shared")
             step = n
+            if rules is not None:
+                bitmap, m = rules
+                G = self._din_sizes()[2]
+                while not L.rsx_topk_rows_rules_supported(step, k, E, G, m):
+                    step = (step + 1) // 2
+                for s2 in range(0, n, step):
+                    _lib.check(L.rsx_topk_rows_rules(r["prob"].data_ptr() + 4 * s2, int(n), cat_i + 4 * (s + s2), t["excl"].data_ptr(),
+                                                     int(E), cat_c, G, t["allow"].data_ptr() if bitmap else None, int(m), int(U),
+                                                     min(step, n - s2), int(k), val, idx, state, stream), "rsx_topk_rows_rules")
+                continue
             while not L.rsx_topk_rows_excl_supported(step, k, E):
                 step = (step + 1) // 2
             for s2 in range(0, n, step):
@@ -1260,18 +1375,28 @@ class Predictor:
                                                 int(E), int(U), min(step, n - s2), int(k), val, idx, state, stream),
                            "rsx_topk_rows_excl")
 
-    def _recommend_device(self, U, k, P, Pq, u_iid_seq, u_icat_seq, ids):
-        """ids: int32 [U, E] host, E one of the exclusion capacities -> the answer of `recommend_host` for U users."""
+    def _recommend_device(self, U, k, P, Pq, u_iid_seq, u_icat_seq, ids, rules=None):
+        """ids: int32 [U, E] host, E one of the exclusion capacities -> the answer of `recommend_host` for U users.
+        rules: None, or (bitmap: uint32 [U, W] host or None, m: the cap or 0) of a request with a category rule; its graph is
+        keyed by (U, k, E, bitmap present, m)."""
         import torch
         E = int(ids.shape[1])
         kk = min(k, self.catalogue_size)
         with torch.no_grad():
             r = self._rank_setup(U)
-            t = self._rec_setup(U, k)
+            t = self._rec_setup(U, k, rules is not None)
             self._rank_histories(r, U, P, Pq, u_iid_seq, u_icat_seq)
             if E:
                 t["excl"][:U * E].view(U, E).copy_(torch.from_numpy(ids), non_blocking=True)
-            self._run(("recommend", U, k, E), lambda: self._recommend_launch(U, k, E))
+            if rules is None:
+                self._run(("recommend", U, k, E), lambda: self._recommend_launch(U, k, E))
+            else:
+                bitmap, m = rules
+                if bitmap is not None:
+                    W = bitmap.shape[1]
+                    t["allow"][:U * W].view(U, W).copy_(torch.from_numpy(bitmap.view(np.int32)), non_blocking=True)
+                how = (bitmap is not None, int(m))
+                self._run(("recommend", U, k, E) + how, lambda: self._recommend_launch(U, k, E, how))
             h = t["buf"][:2 * U * k + 2 * U].cpu().numpy()           # the ONE device-to-host copy: pairs and `filled`
         count = h[2 * U * k:].view(np.int32).reshape(U, 2)[:, 0].copy()
         prob = np.ascontiguousarray(h[:U * k].reshape(U, k)[:, :kk])
@@ -1304,7 +1429,8 @@ class Predictor:
         padded[:, :ids.shape[1]] = ids
         return padded
 
-    def recommend(self, u_iid_seq, u_icat_seq, top_k, exclude_seen=True, exclude=None):
+    def recommend(self, u_iid_seq, u_icat_seq, top_k, exclude_seen=True, exclude=None, categories=None, exclude_categories=None,
+                  max_per_category=None):
         """din.py bundles, after `set_catalogue`: the top_k best catalogue entries for ONE user's history ([P']) or for U users
         ([U, P']), every entry scored exactly as `rank_candidates` scores it, without the entries whose item id is a positive
         id of the user's history (exclude_seen) or of `exclude` ([E'] / [U, E']: blocked, already bought; ids <= 0 are padding).
@@ -1315,7 +1441,16 @@ class Predictor:
         positive exclusion ids per user): only the histories and the exclusion ids are shipped, the whole request -- per chunk
         rsx_predict_din_rank_shared over the resident catalogue and rsx_topk_rows_excl -- is ONE captured graph per
         (U, k, exclusion capacity), one copy brings the answer back; "host": `rank_candidates` over the catalogue, then
-        `recommend_host`.  Both give the same bits."""
+        `recommend_host`.  Both give the same bits.
+        CATEGORY RULES (`recommend_host` defines them; a request without one is exactly the request above): categories /
+        exclude_categories ([G'] / [U, G'] like `exclude`; negative ids padding, ids >= n_cate refused) keep only / drop the
+        entries of those categories -- the category of an entry is what `set_catalogue` was given -- and max_per_category = m
+        keeps at most m entries of one category in the list, so count[u] can stay below top_k.
+        `recommend_path_for(k, m, rules=True)` says where such a request runs: "device" (the conditions above,
+        `rules_on_device`, m <= 16 and rsx_topk_rows_rules' envelope): the lists are folded into a bitmap [U, ceil(n_cate / 32)]
+        that is shipped with the exclusion ids, rsx_topk_rows_rules takes rsx_topk_rows_excl's place launch for launch, and
+        the request is ONE captured graph per (U, k, exclusion capacity, bitmap present, m); "host": `rank_candidates` over the
+        catalogue, then `recommend_host`.  Both give the same bits."""
         import torch
         self._need_din("recommend")
         if self._cat is None:
@@ -1326,16 +1461,28 @@ class Predictor:
         one = np.zeros((shape[0], 1) if len(shape) == 2 else 1, np.int32)      # a stand-in candidate: the histories' checks
         U, _, Pq, single = check_rank_request(u_iid_seq, u_icat_seq, one, one, P, n_item, n_cate)
         ids = _exclusion_ids(u_iid_seq, exclude, U, exclude_seen)
-        padded = self._device_exclusion(ids) if self._recommend_on_device(k) else None
+        m = check_max_per_category(max_per_category)
+        only = check_category_list(categories, "categories", U, single, n_cate)
+        deny = check_category_list(exclude_categories, "exclude_categories", U, single, n_cate)
+        rules = None
+        if m is not None or only is not None or deny is not None:
+            rules = (category_bitmap(only, deny, n_cate) if only is not None or deny is not None else None, m or 0)
+            on_device = self._rules_on_device(k, m)
+        else:
+            on_device = self._recommend_on_device(k)
+        padded = self._device_exclusion(ids) if on_device else None
         if padded is not None:
             self.recommend_path = "device"
-            out = self._recommend_device(U, k, P, Pq, u_iid_seq, u_icat_seq, padded)
+            out = self._recommend_device(U, k, P, Pq, u_iid_seq, u_icat_seq, padded, rules)
         else:
             self.recommend_path = "host"
             ci, cc = self._cat["host"]
             cand = (ci, cc) if single else tuple(np.broadcast_to(x, (U, len(x))) for x in (ci, cc))
             prob = self.rank_candidates(u_iid_seq, u_icat_seq, *cand)["prob"]
-            return recommend_host(prob, ci, u_iid_seq, exclude, k, exclude_seen)
+            if rules is None:
+                return recommend_host(prob, ci, u_iid_seq, exclude, k, exclude_seen)
+            return recommend_host(prob, ci, u_iid_seq, exclude, k, exclude_seen, cat_cate=cc, categories=categories,
+                                  exclude_categories=exclude_categories, max_per_category=m, n_cate=n_cate)
         return _one_user(out) if single else out
 
     # -- offline ranking metrics over the resident catalogue (din.py; csrc/rank_count.hip) -----------------------------------
