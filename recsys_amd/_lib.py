@@ -1,6 +1,8 @@
 """ctypes binding of librsx.so (include/rsx.h).  Fails loudly when the library is missing: there is
 no CPU fallback anywhere in this package."""
+import contextlib
 import ctypes as C
+import gc
 import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -444,6 +446,23 @@ def lib():
         fn.restype, fn.argtypes = res, args
     _lib = L
     return L
+
+
+@contextlib.contextmanager
+def capture_gc_guard():
+    """Around an open stream capture (`with capture_gc_guard(), torch.cuda.graph(...)`): Python's cyclic garbage collector runs
+    once BEFORE the capture opens and is suspended while it is open.  A collection that starts inside an open capture finalizes
+    whatever dropped Estimator / Predictor / SegmentedGraph is still waiting in a reference cycle, and with it its
+    torch.cuda.CUDAGraph, whose destructor synchronizes the device on ROCm -- which a capturing thread may not do: the error
+    leaves a destructor and the process aborts.  (torch.cuda.graph itself collected before every capture until torch 2.9.)"""
+    gc.collect()
+    was_enabled = gc.isenabled()
+    gc.disable()
+    try:
+        yield
+    finally:
+        if was_enabled:
+            gc.enable()
 
 
 def exported_symbols():

@@ -659,7 +659,9 @@ __global__ __launch_bounds__(512) void din_attn_bwd_k(const AttnBwdArgs p) {
       for (int t = 0; t < 4; ++t) {
         const int n = 16 * kb + 4 * kq + t;
         const bool ok = mok && n < p.N2;
-        const float av = a2N[kb][t] * (ok ? 1.f : 0.f);
+        // (a1 / a2 are SELECTED, never multiplied by 0: a lane past the end holds row 0's values, and with a row list row 0
+        // may be a skipped row, which may hold anything -- a NaN there reached dW1 / dW2 through the tiles below)
+        const float av = ok ? a2N[kb][t] : 0.f;
         const float mul = d2.mode == 0 ? 1.f : (ok ? drop_mul(d2, p.mask2, mc * p.N2 + n) : 0.f);
         const float gv = av > 0.f ? dz * sw2[n] * mul : 0.f;
         g2[kb][t] = gv;
@@ -676,7 +678,7 @@ __global__ __launch_bounds__(512) void din_attn_bwd_k(const AttnBwdArgs p) {
           for (int t = 0; t < 4; ++t) {
             const int n = 16 * (nt0 + u) + 4 * kq + t;
             const bool ok = mok && n < p.N1;
-            const float av = a1N[u][t] * (ok ? 1.f : 0.f);
+            const float av = ok ? a1N[u][t] : 0.f;
             const float mul = d1.mode == 0 ? 1.f : (ok ? drop_mul(d1, p.mask1, mc * p.N1 + n) : 0.f);
             sA1[n * LDR + 16 * rt + i] = av * mul;
           }
@@ -737,7 +739,7 @@ __global__ __launch_bounds__(512) void din_attn_bwd_k(const AttnBwdArgs p) {
             const int row = 16 * rt + 4 * kq + r;
             const size_t mm = (size_t)mrow[r];
             const bool ok = blk * 64 + row < Mv && n < p.N1;
-            const float av = a1N[u][r] * (ok ? 1.f : 0.f);
+            const float av = ok ? a1N[u][r] : 0.f;
             const float mul = d1.mode == 0 ? 1.f : (ok ? drop_mul(d1, p.mask1, mm * p.N1 + n) : 0.f);
             const float gv = av > 0.f ? dg1[u][r] * mul : 0.f;
             db0acc[u] += gv;

@@ -25,6 +25,8 @@ import warnings
 import torch
 import torch.distributed as dist
 
+from . import _lib
+
 
 def is_distributed_env():
     return int(os.environ.get("WORLD_SIZE", "1")) > 1 or os.environ.get("RSX_FORCE_DIST") == "1"
@@ -238,12 +240,13 @@ class SegmentedGraph:
         """Runs fn() under capture (fn's collectives call graph_break); returns fn's result."""
         assert SegmentedGraph._active is None
         SegmentedGraph._active = self
-        self._begin()
-        try:
-            out = fn()
-        finally:
-            self._end()
-            SegmentedGraph._active = None
+        with _lib.capture_gc_guard():       # (over all segments: the eager collectives between them do not collect either)
+            self._begin()
+            try:
+                out = fn()
+            finally:
+                self._end()
+                SegmentedGraph._active = None
         return out
 
     def run_eager(self, op):

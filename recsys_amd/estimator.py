@@ -455,7 +455,7 @@ class Estimator:
         # (data parallel with captured collectives: "thread_local" lets ProcessGroupNCCL's watchdog thread poll its events
         # while THIS thread captures -- see dist.SegmentedGraph._begin)
         kw = {"capture_error_mode": "thread_local"} if self.store.dp is not None else {}
-        with torch.cuda.graph(graph, **kw):
+        with _lib.capture_gc_guard(), torch.cuda.graph(graph, **kw):
             out = fn()
         return graph, out
 
@@ -630,7 +630,7 @@ class Estimator:
             K = self._window_len()
             # (data parallel with captured collectives: see _capture -- a communicator thread may poll events meanwhile)
             kw = {"capture_error_mode": "thread_local"} if self.store.dp is not None else {}
-            with torch.cuda.graph(graph, **kw):
+            with _lib.capture_gc_guard(), torch.cuda.graph(graph, **kw):
                 k = 0
                 nwin = -(-count // K)    # windows of the graph, as EVEN as possible (20 steps: 7 + 7 + 6 rather than 8 + 8 + 4:
                 while k < count:         # a window's ONE sweep costs 57 us + ~3 us per step, so short windows are the dear ones)
@@ -929,7 +929,7 @@ class Estimator:
         torch.cuda.synchronize()
         graph = torch.cuda.CUDAGraph()
         kw = {"capture_error_mode": "thread_local"} if self.store.dp is not None else {}
-        with torch.cuda.graph(graph, **kw):
+        with _lib.capture_gc_guard(), torch.cuda.graph(graph, **kw):
             spec = self._call_model_fn(f, l if mode == ModeKeys.EVAL else None, mode)
         g["prob"], g["loss"], g["labels"] = spec.predictions["prob"], spec.loss, (l if has_lab else None)
         g["features"] = self._infer_features = f

@@ -971,7 +971,7 @@ class Predictor:
         else:
             torch.cuda.synchronize()
             graph = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(graph):
+            with _lib.capture_gc_guard(), torch.cuda.graph(graph):
                 launch()
             g["graph"] = graph
             graph.replay()                  # capture executes nothing

@@ -144,6 +144,10 @@ def test_attention_envelope(L):
     assert L.rsx_din_attn_bwd(P, P, P, P, P, P, P, P, None, P, P, P, None, None, P, u32(1), 0, 0.0, 0, None, None, None, 4, 10, 32, 80, 40, None) == EINVAL
     # a row list needs the ids it was made from (the dq reduction masks by them)
     assert L.rsx_din_attn_bwd(P, P, P, P, P, P, P, P, P, P, P, P, None, None, P, u32(1), 0, 0.0, 0, P, P, None, 4, 10, 32, 80, 40, None) == EINVAL
+    # strided outputs (din.py's fused step): a row stride shorter than the row, with and without a list
+    assert L.rsx_din_attn_bwd_ld(P, P, P, P, P, P, P, P, P, P, P, P, None, None, P, u32(1), 0, 0.0, 0, None, None, None, 4, 10, 32, 80, 40, 31, 32, None, 0, None) == EINVAL   # ld_dH < K
+    assert L.rsx_din_attn_bwd_ld(P, P, P, P, P, P, P, P, P, P, P, P, None, None, P, u32(1), 0, 0.0, 0, P, P, None, 4, 10, 32, 80, 40, 64, 96, None, 0, None) == EINVAL   # a list without ids
+    assert L.rsx_din_attn_bwd_nofinish(P, P, P, P, P, P, P, P, P, P, None, None, P, u32(1), 0, 0.0, 1, P, P, P, 4, 10, 32, 80, 40, 31, None) == EINVAL   # ld_dH < K
     assert L.rsx_din_valid_rows(None, 4, 10, P, P, None, None) == EINVAL
     assert L.rsx_din_valid_rows(P, 1 << 20, 1 << 10, P, P, None, None) == EUNSUPPORTED
     assert L.rsx_din_attn_bwd_workspace_floats(4, 10, 32, 80, 40) > 0

@@ -233,14 +233,15 @@ def hash32(x):
     return x
 
 
-def hash_masks(B, widths, rate, step=RNG_STEP, seed=HASH_SEED):
+def hash_masks(B, widths, rate, step=RNG_STEP, seed=HASH_SEED, layer0=0):
     """The keep masks the kernels derive when none is injected: element b * n + col of layer l is dropped when
     hash32(element ^ key) < rate * 2^32, key = hash32(seed ^ step * 0x9E3779B9 ^ (l * 0x85EBCA6B + 0x27220A95)) (32-bit arithmetic;
-    the rate is the fp32 value the kernels are handed)."""
+    the rate is the fp32 value the kernels are handed).  layer0: the layer number of widths[0] (the tower counts from 0; the two
+    attention blocks of din.py from 0 and 2)."""
     M = 0xFFFFFFFF
     thresh = np.uint64(int(float(np.float32(rate)) * 2.0 ** 32))
     out = []
-    for l, n in enumerate(widths):
+    for l, n in enumerate(widths, start=layer0):
         key = hash32(np.array([(seed ^ ((step * 0x9E3779B9) & M) ^ ((l * 0x85EBCA6B + 0x27220A95) & M)) & M]))[0]
         h = hash32((np.arange(B * n, dtype=np.uint64) & np.uint64(M)) ^ key)
         out.append(torch.from_numpy((h >= thresh).astype(np.float32).reshape(B, n)))
