@@ -908,6 +908,54 @@ int rsx_rank_count_rows(const float* scores, int ld, const int32_t* cand_id, int
                         rsx_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Two-stage DIN recommendation (since rsx_version() 107): item neighbours from the item embeddings, candidate retrieval on the
+ * device, and the selection over per-user candidate lists.  serving.Predictor.build_neighbours / recommend_two_stage.
+ *
+ * (a) rsx_rows_dot (csrc/rows_dot.hip): scores[q, j] = dot(unit[q_rows[q]], unit[first + j]) for q < Q, j < n; unit is one
+ * fp32 matrix [N, K], rows contiguous and 16-byte aligned, K in {16, 32}; q_rows [Q] (device) names the query rows; scores: row
+ * q at scores + q * ld (ld >= n; the padding is never written).  ARITHMETIC, the contract: one fp32 accumulator per output,
+ * s = +0.0f, then s = s + a[d] * b[d] for d = 0 .. K - 1 in that order, every product and every sum rounded to fp32 -- no
+ * fused multiply-add, no matrix-core instruction, no split accumulators -- so a numpy restatement gives the same bits
+ * (subnormal products aside: the kernel's fp32 denormal mode decides those).  The kernel normalises nothing: for cosine
+ * similarity the caller passes unit-length rows.  A q_rows entry outside [0, N) is taken as a row of zeros.  Deterministic.
+ * RSX_EINVAL (before any HIP call): a NULL pointer, unit not 16-byte aligned, N / K / Q / n <= 0, first < 0, first + n > N,
+ * ld < n.  Envelope (rsx_rows_dot_supported; RSX_EUNSUPPORTED outside, before any HIP call): K in {16, 32}; Q <= 4 194 240.
+ * ------------------------------------------------------------------------------------------- */
+int rsx_rows_dot_supported(int K);
+int rsx_rows_dot(const float* unit, int N, int K, const int32_t* q_rows, int Q, int first, int n, float* scores, int ld,
+                 rsx_stream_t stream);
+
+/* (b) rsx_topk_rows_counted (csrc/topk_counted.hip): rsx_topk_rows with ONE addition.  n_valid [U] (int32, device): new score j
+ * of row u is LEFT OUT of the union when j >= n_valid[u] (a count outside [0, n] is clamped into it); such a score takes the
+ * key 0, as an excluded score of rsx_topk_rows_excl does, and is never read.  next_index still advances by n and filled becomes
+ * min(k, filled + the count).  The running list is never filtered.  With n_valid[u] >= n for every row the outputs and the
+ * state are rsx_topk_rows' bit for bit.  The same envelope (rsx_topk_rows_supported), thread count (rsx_topk_rows_threads), LDS
+ * plan and refusals as rsx_topk_rows; n_valid NULL is RSX_EINVAL. */
+int rsx_topk_rows_counted(const float* scores, int ld, const int32_t* n_valid, int U, int n, int k, float* out_val,
+                          int32_t* out_idx, int32_t* state, rsx_stream_t stream);
+
+/* (c) rsx_din_retrieve_candidates (csrc/retrieve.hip): the candidates of U users from an item-neighbour table, one workgroup
+ * per user.  hist_item [U, P]: the histories, ids <= 0 padding.  first_pos [n_item]: id -> the lowest catalogue position that
+ * holds it, -1 for an id the catalogue does not hold.  nbr_pos [N, n_nbr] / nbr_count [N]: row i holds nbr_count[i] catalogue
+ * positions.  cat_item / cat_cate [N]: the catalogue.  excl [U, E]: ids per user, entries <= 0 padding (rsx_topk_rows_excl's
+ * list).  A SEED of user u is a history id in (0, n_item) with first_pos >= 0.  The candidates of u are the positions named by
+ * the neighbour rows of the seeds' first positions -- with include_seeds != 0 also every position whose item id is a seed id --
+ * without the positions whose item id is a positive entry of excl[u, :].  Outputs: cand_pos [U, cap] the distinct candidate
+ * positions ascending, cand_item / cand_cate [U, cap] the catalogue's ids at those positions, all padded from the count to cap
+ * with -1 / 0 / 0, and n_cand [U] the count.  cap >= min(N, P (n_nbr + 1)) holds every possible count; with a smaller cap the
+ * lowest cap positions are written and n_cand = cap -- nothing is written at or beyond cap.
+ * A bitmap of N bits in LDS, set with integer LDS atomics (a set of bits does not depend on the order threads run in),
+ * compacted by a popcount prefix sum.  No global atomics, no workspace, no grid-wide step.  Deterministic.
+ * RSX_EINVAL (before any HIP call): a NULL pointer (excl may be NULL when E = 0), U / P / n_item / n_nbr / N / cap <= 0, E < 0.
+ * Envelope (rsx_din_retrieve_candidates_supported; RSX_EUNSUPPORTED outside, before any HIP call): N <= 2^20 (a 128 KB bitmap),
+ * P <= 128, n_nbr <= 64, E <= 256. */
+int rsx_din_retrieve_candidates_supported(int N, int P, int n_nbr, int E);
+int rsx_din_retrieve_candidates(const int32_t* hist_item, int P, const int32_t* first_pos, int n_item, const int32_t* nbr_pos,
+                                const int32_t* nbr_count, int n_nbr, const int32_t* cat_item, const int32_t* cat_cate, int N,
+                                const int32_t* excl, int E, int include_seeds, int32_t* cand_pos, int32_t* cand_item,
+                                int32_t* cand_cate, int32_t* n_cand, int cap, int U, rsx_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
  * DCN cross layers, dcn/dcn.py:132-142: x_{l+1} = (x_l . w_l) * x0 + x_l + b_l, all L
  * layers fused per example.  dim % 4 == 0, dim <= 1024, L <= 8.
  * ------------------------------------------------------------------------------------------- */

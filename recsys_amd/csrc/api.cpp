@@ -1,7 +1,7 @@
 // Version / error strings of librsx.so.
 #include "rsx.h"
 
-extern "C" int rsx_version(void) { return 106; /* 0.1.6: rsx_topk_rows_rules; 105: rsx_rank_count_rows; 104: rsx_predict_din_rank_shared, rsx_topk_rows_excl, rsx_topk_rows_threads; 103: the device parse of TFRecord records (rsx_criteo_parse_records); 102: the device parse entries (rsx_criteo_parse_examples, rsx_log_thresholds_h); 101: table_dtype appended to the predict models */ }
+extern "C" int rsx_version(void) { return 107; /* 0.1.7: rsx_rows_dot, rsx_topk_rows_counted, rsx_din_retrieve_candidates; 106: rsx_topk_rows_rules; 105: rsx_rank_count_rows; 104: rsx_predict_din_rank_shared, rsx_topk_rows_excl, rsx_topk_rows_threads; 103: the device parse of TFRecord records (rsx_criteo_parse_records); 102: the device parse entries (rsx_criteo_parse_examples, rsx_log_thresholds_h); 101: table_dtype appended to the predict models */ }
 
 extern "C" const char* rsx_strerror(int status) {
   switch (status) {

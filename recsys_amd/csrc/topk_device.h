@@ -1,8 +1,10 @@
-// What the three top-k kernels share (topk.hip: rsx_topk_rows; topk_excl.hip: rsx_topk_rows_excl; topk_rules.hip:
-// rsx_topk_rows_rules): the 64-bit key image of a (score, index) pair, the LDS plan, and the workgroup's body -- keys, MSB-first
+// What the top-k kernels share (topk.hip: rsx_topk_rows; topk_excl.hip: rsx_topk_rows_excl; topk_rules.hip:
+// rsx_topk_rows_rules; topk_counted.hip: rsx_topk_rows_counted): the 64-bit key image of a (score, index) pair, the LDS plan, and the workgroup's body -- keys, MSB-first
 // radix select, compaction, rank by counting.  topk.hip's head describes the method.  MODE TK_PLAIN is rsx_topk_rows; TK_EXCL
 // adds the exclusion of new scores by id (topk_excl.hip's head); TK_RULES adds the category rules on top of that
 // (topk_rules.hip's head).  Each addition is compiled in with `if constexpr`, so a kernel holds nothing of the modes above it.
+// TK_COUNTED (topk_counted.hip: rsx_topk_rows_counted) is TK_PLAIN with a per-row count of valid new scores; it stands beside
+// the three, not above them, and is compiled in the same way.
 #pragma once
 #include "predict_device.h"      // launch_big_lds, PR_MAX_LDS
 
@@ -14,7 +16,7 @@ constexpr int TK_T_SMALL = 256, TK_T_BIG = 1024;
 constexpr int TK_SMALL_KEYS = 1024;     // up to this many keys a workgroup of 256 threads, above it 1024
 constexpr int TK_EMAX = 256;             // largest exclusion list of a row (EXCL)
 constexpr int TK_MMAX = 16;              // largest per-category cap (RULES)
-constexpr int TK_PLAIN = 0, TK_EXCL = 1, TK_RULES = 2;
+constexpr int TK_PLAIN = 0, TK_EXCL = 1, TK_RULES = 2, TK_COUNTED = -1;
 
 struct TopkArgs {
   const float* scores;
@@ -23,6 +25,10 @@ struct TopkArgs {
   int32_t* state;
   int ld, n, k;
   int oSel, oOldV, oOldI, oHist, oMisc;  // LDS plan, in bytes from the start of the keys
+};
+
+struct TopkCountedArgs : TopkArgs {
+  const int32_t* n_valid;                // [U]: new score j of row u is left out when j >= n_valid[u]
 };
 
 struct TopkExclArgs : TopkArgs {
@@ -82,7 +88,7 @@ __device__ __forceinline__ bool tk_excluded(const int* exs, const int E, const i
 
 template <int MODE, class Args>
 __device__ __forceinline__ void topk_rows_body(const Args& p, unsigned long long* tk_lds) {
-  constexpr bool EXCL = MODE >= TK_EXCL, RULES = MODE == TK_RULES;
+  constexpr bool EXCL = MODE >= TK_EXCL, RULES = MODE == TK_RULES, COUNTED = MODE == TK_COUNTED;
   unsigned long long* keys = tk_lds;
   char* base = reinterpret_cast<char*>(tk_lds);
   unsigned long long* sel = reinterpret_cast<unsigned long long*>(base + p.oSel);
@@ -201,6 +207,13 @@ __device__ __forceinline__ void topk_rows_body(const Args& p, unsigned long long
         want = Tl < k ? Tl : k;
       }
     }
+  } else if constexpr (COUNTED) {
+    // The new scores at and beyond the row's count take key 0, as an excluded score does; they are never read.
+    int nv = p.n_valid[row];
+    nv = nv < 0 ? 0 : (nv > n ? n : nv);
+    want = filled + nv < k ? filled + nv : k;
+    for (int j = tid; j < n; j += NT) keys[filled + j] = j < nv ? tk_key(sc[j], next0 + j) : 0ull;
+    __syncthreads();
   } else {
     want = T < k ? T : k;
     for (int j = tid; j < n; j += NT) keys[filled + j] = tk_key(sc[j], next0 + j);
@@ -211,8 +224,9 @@ __device__ __forceinline__ void topk_rows_body(const Args& p, unsigned long long
   // (zeros) sit among no more than k kept ones (filled + kept < k < filled + n included) -- the want-th largest key is a real
   // one, every zero is smaller, and a bin that holds a zero is never "taken whole", so `key >= prefix` admits no zero.
   // RULES: the same argument, wherever the zeros sit -- under a cap entries of the running list become zeros too.
-  const int nsel = EXCL ? want : k;
-  const bool select = EXCL ? (T > want && want > 0) : (T > k);
+  // COUNTED: EXCL's argument with the zeros behind the row's count.
+  const int nsel = (EXCL || COUNTED) ? want : k;
+  const bool select = (EXCL || COUNTED) ? (T > want && want > 0) : (T > k);
   const unsigned long long* src = keys;                            // the survivors: everything when the union is no longer than k
   if (select) {
     // (2) radix select of the nsel-th largest key

@@ -57,6 +57,15 @@ The reference exports a SavedModel whose serving signature parses serialized `tf
               graph -- the targets' scores, then per chunk rsx_predict_din_rank_shared and rsx_rank_count_rows
               (csrc/rank_count.hip) -- and 8 bytes per (user, slot) copied back; "host": `rank_candidates` over the catalogue,
               then `target_ranks_host`.  The same integers and probability bits either way.
+              `build_neighbours(n)` keeps, per catalogue position, the n most similar other entries by cosine similarity of
+              the item embedding rows (rsx_rows_dot, csrc/rows_dot.hip, + rsx_topk_rows_excl; `item_neighbours_host` is the
+              definition; `similar_items` reads the rows).  `recommend_two_stage(u_iid_seq, u_icat_seq, top_k)` then scores
+              only the neighbours of the history's items: two_stage_path_for(k) == "device": ONE graph --
+              rsx_din_retrieve_candidates (csrc/retrieve.hip), rsx_predict_din_rank over the users' candidate lists,
+              rsx_topk_rows_counted (csrc/topk_counted.hip), a gather of the positions -- and one copy back; "host":
+              `retrieve_candidates_host`, `rank_candidates`, `topk_rows_host`.  The same bits either way;
+              `recommend_two_stage_host` is the definition.  No back-fill: a list can be shorter than top_k and differs from
+              `recommend`'s by design.
 """
 import ctypes as C
 import importlib
@@ -787,6 +796,152 @@ def ranking_metrics(rank, ks, per_user=False):
     return out
 
 
+# ---- two-stage recommendation: item neighbours and candidate retrieval (din.py): pure numpy, no device -------------------------
+NBR_MAX = 64                          # include/rsx.h rsx_din_retrieve_candidates: the most neighbours kept per catalogue entry
+
+
+def check_n_neighbours(n_neighbours):
+    """`build_neighbours`' argument -> int; RsxError unless it is an integer (no bool) in [1, 64]."""
+    n = n_neighbours
+    if isinstance(n, (bool, np.bool_)) or not isinstance(n, (int, np.integer)) or not 1 <= int(n) <= NBR_MAX:
+        raise _lib.RsxError("build_neighbours: n_neighbours must be an integer in [1, %d], not %r" % (NBR_MAX, n))
+    return int(n)
+
+
+def unit_rows_host(E):
+    """E: float [N, K] embedding rows -> float32 [N, K]: every row divided by its float64 norm and rounded to float32; a
+    zero-norm row stays all +0.0.  RsxError for a non-finite entry.  This is what `build_neighbours` uploads: the device
+    never normalises."""
+    e = np.asarray(E, np.float64)
+    if e.ndim != 2 or e.shape[0] < 1 or e.shape[1] < 1:
+        raise _lib.RsxError("unit_rows_host: expected embedding rows [N, K], got %s" % (e.shape,))
+    if not np.isfinite(e).all():
+        raise _lib.RsxError("unit_rows_host: a non-finite embedding (row %d)" % int(np.flatnonzero(~np.isfinite(e).all(1))[0]))
+    norm = np.sqrt((e * e).sum(1))
+    out = np.zeros(e.shape, np.float32)
+    nz = norm > 0
+    out[nz] = (e[nz] / norm[nz, None]).astype(np.float32)
+    return out
+
+
+def rows_dot_host(A, q_rows, first, n):
+    """The arithmetic of rsx_rows_dot (include/rsx.h) in numpy: A float32 [N, K], q_rows int [Q] ->
+    float32 [Q, n], out[q, j] = dot(A[q_rows[q]], A[first + j]) as `s = +0.0f; for d in 0 .. K - 1: s = s + a[d] * b[d]`,
+    strictly ascending in d, every product and every sum rounded to float32, no fused multiply-add."""
+    A = np.asarray(A, np.float32)
+    q = np.asarray(q_rows, np.int64).reshape(-1)
+    first, n = int(first), int(n)
+    if A.ndim != 2 or first < 0 or n < 1 or first + n > A.shape[0] or (q.size and (q.min() < 0 or q.max() >= A.shape[0])):
+        raise _lib.RsxError("rows_dot_host: rows [%d, %d) or the query rows are outside A %s" % (first, first + n, A.shape))
+    a, b = A[q], A[first:first + n]
+    s = np.zeros((len(q), n), np.float32)
+    for d in range(A.shape[1]):
+        s = s + a[:, d, None] * b[None, :, d]                          # (two float32 ufuncs: a rounded product, a rounded sum)
+    return s
+
+
+def item_neighbours_host(unit, cat_item, n, block=512):
+    """The definition of `build_neighbours`' table.  unit: float32 [N, K] (`unit_rows_host` of the catalogue entries' item
+    embeddings); cat_item: int [N]; n in [1, 64].  For position i with cat_item[i] > 0: the n best positions j by
+    `rows_dot_host` similarity in the ORDER of rsx_topk_rows (higher similarity first, equal ones by the lower position), every
+    j with cat_item[j] == cat_item[i] left out -- i itself and the duplicates of its item.  A position with item id 0 (history
+    padding, never a seed) gets an empty row; it may still be another entry's neighbour.
+    -> (nbr_pos int32 [N, n], nbr_sim float32 [N, n], nbr_count int32 [N]), -1 / NaN beyond the count."""
+    n = check_n_neighbours(n)
+    unit = np.asarray(unit, np.float32)
+    cat = np.asarray(cat_item).astype(np.int64)
+    N = cat.shape[0]
+    if unit.ndim != 2 or unit.shape[0] != N or cat.ndim != 1:
+        raise _lib.RsxError("item_neighbours_host: unit rows %s do not match the catalogue %s" % (unit.shape, cat.shape))
+    pos = np.full((N, n), -1, np.int32)
+    sim = np.full((N, n), np.nan, np.float32)
+    count = np.zeros(N, np.int32)
+    cols = np.arange(N, dtype=np.int64)
+    for s in range(0, N, block):
+        rows = np.arange(s, min(N, s + block))
+        score = rows_dot_host(unit, rows, 0, N)
+        for r, i in enumerate(rows):
+            if cat[i] <= 0:
+                continue
+            ok = cols[cat != cat[i]]
+            order = ok[np.lexsort((ok, -score[r, ok]))][:n]
+            c = len(order)
+            pos[i, :c], sim[i, :c], count[i] = order, score[r, order], c
+    return pos, sim, count
+
+
+def check_neighbours(nbr_pos, nbr_count, N):
+    pos, cnt = np.asarray(nbr_pos), np.asarray(nbr_count)
+    if pos.ndim != 2 or cnt.shape != (pos.shape[0],) or pos.shape[0] != N:
+        raise _lib.RsxError("neighbour table %s / %s does not match the catalogue [%d]" % (pos.shape, cnt.shape, N))
+    return pos, cnt
+
+
+def retrieve_candidates_host(nbr_pos, nbr_count, cat_item, hist_item, exclude=None, exclude_seen=True):
+    """The definition of `Predictor.retrieve_candidates`, in numpy.  nbr_pos [N, n] / nbr_count [N]: `item_neighbours_host`'s
+    table; cat_item int [N]; hist_item [P'] / [U, P']; exclude None or [E'] / [U, E'].  Per user: the SEEDS are the positive
+    history ids that occur in the catalogue, each resolved to its lowest position (`catalogue_first_positions`); the candidates
+    are the union of the seeds' neighbour rows -- with exclude_seen=False joined by every position whose item id is a seed id
+    -- without every position whose item id is a positive id of the exclusion list (`_exclusion_ids`: the history when
+    exclude_seen, then `exclude`; the list `recommend` uses).  -> a list of U int32 arrays: the sorted distinct positions."""
+    cat = np.asarray(cat_item).astype(np.int64)
+    N = cat.shape[0]
+    pos, cnt = check_neighbours(nbr_pos, nbr_count, N)
+    h = hist_item.detach().cpu().numpy() if hasattr(hist_item, "detach") else np.asarray(hist_item)
+    if h.ndim not in (1, 2):
+        raise _lib.RsxError("retrieve_candidates_host: expected histories [P] or [U, P], got %s" % (h.shape,))
+    U = 1 if h.ndim == 1 else h.shape[0]
+    ids = _exclusion_ids(h, exclude, U, exclude_seen)
+    index = catalogue_first_positions(cat)
+    hist = h.reshape(U, -1).astype(np.int64)
+    out = []
+    for u in range(U):
+        at = _target_positions(index, hist[u][None, :])[0] if hist.shape[1] else np.zeros(0, np.int64)
+        at = at[at >= 0]                                               # (padding and ids the catalogue does not hold are < 0)
+        mark = np.zeros(N, bool)
+        for a in at:
+            mark[pos[a, :cnt[a]]] = True
+        if not exclude_seen:
+            mark |= np.isin(cat, cat[at])
+        mark &= ~np.isin(cat, ids[u][ids[u] > 0])
+        out.append(np.flatnonzero(mark).astype(np.int32))
+    return out
+
+
+def recommend_two_stage_host(prob, nbr_pos, nbr_count, cat_item, hist_item, exclude, top_k, exclude_seen=True):
+    """The definition of `Predictor.recommend_two_stage`, in numpy.  prob: float32 [N] (one user) or [U, N], the scores of ALL
+    catalogue entries (`rank_candidates` over the whole catalogue).  `recommend_host`'s order (higher score first, equal ones
+    by the lower position, NaN last) restricted to the positions `retrieve_candidates_host` gives ->
+    `recommend_host`'s dictionary, kk = min(top_k, N), count[u] = min(top_k, candidates of u): it can stay below top_k and can
+    be 0 -- nothing is filled in from the rest of the catalogue."""
+    k = check_top_k(top_k)
+    a = np.asarray(prob, np.float32)
+    cat = np.asarray(cat_item)
+    if a.ndim not in (1, 2) or cat.ndim != 1 or a.shape[-1] != cat.shape[0] or cat.shape[0] < 1:
+        raise _lib.RsxError("recommend_two_stage_host: expected scores [N] or [U, N] over a catalogue [N], N >= 1; got %s and %s"
+                            % (a.shape, cat.shape))
+    rows = np.atleast_2d(a)
+    U, N = rows.shape
+    cands = retrieve_candidates_host(nbr_pos, nbr_count, cat, hist_item, exclude, exclude_seen)
+    if len(cands) != U:
+        raise _lib.RsxError("recommend_two_stage_host: %d histories for %d rows of scores" % (len(cands), U))
+    kk = min(k, N)
+    out = {"prob": np.full((U, kk), np.nan, np.float32), "item": np.full((U, kk), -1, np.int32),
+           "index": np.full((U, kk), -1, np.int32), "count": np.zeros(U, np.int32)}
+    for u, pos in enumerate(cands):
+        pos = pos.astype(np.int64)
+        order = pos[np.lexsort((pos, -rows[u, pos]))][:kk]
+        c = len(order)
+        out["prob"][u, :c], out["item"][u, :c], out["index"][u, :c], out["count"][u] = rows[u, order], cat[order], order, c
+    return out if a.ndim == 2 else _one_user(out)
+
+
+def candidate_capacity(N, hist_len, n_neighbours):
+    """Columns of a user's candidate list: min(N, hist_len * (n + 1)) -- every seed, its n neighbours -- rounded up to 64."""
+    c = max(1, min(int(N), int(hist_len) * (int(n_neighbours) + 1)))
+    return (c + 63) // 64 * 64
+
+
 # ---- Predictor ---------------------------------------------------------------------------------------------------------------
 class Predictor:
     """An exported model ready to answer requests.  See the module docstring for the two paths.  `table_dtype` is the
@@ -853,6 +1008,9 @@ class Predictor:
         self.rules_on_device = True         # False: a `recommend` with a category rule takes the host path
         self.evaluate_recommend_path = None # where the latest `evaluate_recommend` ranked
         self._cat = None
+        self._nbr = None                    # `build_neighbours`' table (din.py bundles)
+        self.neighbours_path = None         # where the latest `build_neighbours` built it
+        self.two_stage_path = None          # where the latest `recommend_two_stage` ran
         if self.script == "din":
             self.rank_path = "fused" if self._rank_supported() else "layers"
             self.topk_path = "device" if self.rank_path == "fused" else "host"
@@ -1104,7 +1262,8 @@ class Predictor:
             # request buffers of one chunk: the histories [U, P], the candidates and their probabilities [U, max_candidates]
             # (a request of fewer users or candidates uses leading parts of them; graphs captured over smaller buffers go)
             dev, i32 = self.device, torch.int32
-            self._drop_graphs("rank", "rank_topk", "recommend", "eval_recommend")
+            self._drop_graphs("rank", "rank_topk", "recommend", "eval_recommend", "two_stage")
+            r.pop("ts", None)
             r.pop("topk", None)
             r.pop("rec", None)
             r.pop("eval", None)
@@ -1277,12 +1436,14 @@ class Predictor:
     def set_catalogue(self, i_id, i_cate):
         """din.py bundles: the servable items and their categories, two 1-D integer arrays of equal length N >= 1 (numpy or
         torch; `check_catalogue` refuses anything else and ids outside the tables).  Uploaded once as int32, a host copy is
-        kept; `catalogue_size` reports N.  A second call replaces the catalogue and drops the graphs captured over the old one."""
+        kept; `catalogue_size` reports N.  A second call replaces the catalogue and drops the graphs captured over the old one
+        and `build_neighbours`' table, which names positions of the old catalogue."""
         import torch
         self._need_din("set_catalogue")
         _, n_item, n_cate, _ = self._din_sizes()
         ci, cc = check_catalogue(i_id, i_cate, n_item, n_cate)
-        self._drop_graphs("recommend", "eval_recommend")
+        self._drop_graphs("recommend", "eval_recommend", "two_stage")
+        self._nbr, self.neighbours_path = None, None                   # the neighbour table names positions of the old catalogue
         self._cat = {"host": (ci, cc), "dev": [torch.from_numpy(x).to(self.device) for x in (ci, cc)],
                      "first": catalogue_first_positions(ci)}       # id -> its lowest position (evaluate_recommend)
         self.catalogue_size = int(ci.shape[0])
@@ -1483,6 +1644,298 @@ class Predictor:
                 return recommend_host(prob, ci, u_iid_seq, exclude, k, exclude_seen)
             return recommend_host(prob, ci, u_iid_seq, exclude, k, exclude_seen, cat_cate=cc, categories=categories,
                                   exclude_categories=exclude_categories, max_per_category=m, n_cate=n_cate)
+        return _one_user(out) if single else out
+
+    # -- two-stage recommendation: item neighbours, candidates on the device (din.py; csrc/rows_dot.hip, retrieve.hip) ---------
+    def _need_catalogue(self, what):
+        self._need_din(what)
+        if self._cat is None:
+            raise _lib.RsxError("%s: no catalogue set -- call set_catalogue(i_id, i_cate) first" % what)
+
+    def _need_neighbours(self, what):
+        self._need_catalogue(what)
+        if self._nbr is None:
+            raise _lib.RsxError("%s: no neighbour table -- call build_neighbours() after set_catalogue" % what)
+        return self._nbr
+
+    def _neighbours_on_device(self, n):
+        P, _, _, K = self._din_sizes()
+        L = _lib.lib()
+        return (self.rank_path == "fused" and bool(L.rsx_rows_dot_supported(K)) and bool(L.rsx_topk_rows_excl_supported(1, n, 1))
+                and bool(L.rsx_din_retrieve_candidates_supported(self.catalogue_size, P, n, 0)))
+
+    def _build_neighbours_device(self, unit, n):
+        """The build chain: the state's zeroing, then per block of max_candidates query positions and per chunk of catalogue
+        rows rsx_rows_dot and rsx_topk_rows_excl -- cand_id = the chunk's item ids, excl [Q, 1] = each query's own id, k = n --
+        so the running list carries absolute catalogue positions.  -> (pos int32 [N, n], sim float32 [N, n], count int32 [N])
+        on the device, padded like `item_neighbours_host`'s."""
+        import torch
+        L, dev = _lib.lib(), self.device
+        N, K = unit.shape
+        cat_i = self._cat["dev"][0]
+        unit_d = torch.from_numpy(np.ascontiguousarray(unit)).to(dev)
+        chunk = min(N, self.max_candidates)
+        while not L.rsx_topk_rows_excl_supported(chunk, n, 1):
+            chunk = (chunk + 1) // 2
+        QB = min(N, self.max_candidates)
+        scores = torch.empty(QB * chunk, dtype=torch.float32, device=dev)
+        q_rows = torch.arange(N, dtype=torch.int32, device=dev)
+        sim = torch.zeros(N * n, dtype=torch.float32, device=dev)
+        pos = torch.zeros(N * n, dtype=torch.int32, device=dev)
+        state = torch.zeros(2 * N, dtype=torch.int32, device=dev)
+        stream = torch.cuda.current_stream().cuda_stream
+        for q0 in range(0, N, QB):
+            Q = min(QB, N - q0)
+            for s in range(0, N, chunk):
+                m = min(chunk, N - s)
+                _lib.check(L.rsx_rows_dot(unit_d.data_ptr(), int(N), int(K), q_rows.data_ptr() + 4 * q0, int(Q), int(s), int(m),
+                                          scores.data_ptr(), int(m), stream), "rsx_rows_dot")
+                _lib.check(L.rsx_topk_rows_excl(scores.data_ptr(), int(m), cat_i.data_ptr() + 4 * s, cat_i.data_ptr() + 4 * q0, 1,
+                                                int(Q), int(m), int(n), sim.data_ptr() + 4 * q0 * n, pos.data_ptr() + 4 * q0 * n,
+                                                state.data_ptr() + 8 * q0, stream), "rsx_topk_rows_excl")
+        count = torch.where(cat_i > 0, state.view(N, 2)[:, 0], torch.zeros_like(cat_i))
+        pad = torch.arange(n, device=dev)[None, :] >= count[:, None]     # entries past `filled` are unspecified on the device
+        pos, sim = pos.view(N, n), sim.view(N, n)
+        pos[pad], sim[pad] = -1, float("nan")
+        torch.cuda.synchronize()
+        return pos, sim, count.contiguous()
+
+    def build_neighbours(self, n_neighbours=32):
+        """din.py bundles, after `set_catalogue`: builds and keeps, for every catalogue position, the n most similar OTHER
+        catalogue entries by cosine similarity of the bundle's item embedding rows (`item_neighbours_host` is the definition:
+        entries of the same item id are left out, a position with item id 0 gets an empty row).  1 <= n <= 64.
+        The rows are normalised on the host (`unit_rows_host`, float64 norms) and uploaded once, N K 4 bytes, released when the
+        build ends.  `neighbours_path` == "device" (rank_path == "fused" and the kernels' envelopes hold): per block of query
+        positions and per chunk of the catalogue rsx_rows_dot and rsx_topk_rows_excl, the table never leaves the device;
+        "host": `item_neighbours_host`.  Both give the same bits.  The table is N n 8 + N 4 bytes (`neighbours_buffer_bytes`
+        adds the id -> first position index, n_item 4 bytes); `set_catalogue` drops it."""
+        import torch
+        self._need_catalogue("build_neighbours")
+        n = check_n_neighbours(n_neighbours)
+        P, n_item, _, K = self._din_sizes()
+        ci, _ = self._cat["host"]
+        emb = self._est.store.embeddings["i_id"].table.detach()[:, :K].float().cpu().numpy()
+        unit = unit_rows_host(emb[ci])
+        self._drop_graphs("two_stage")
+        self._nbr = None
+        ids, first = self._cat["first"]
+        first_pos = np.full(n_item, -1, np.int32)
+        first_pos[ids] = first
+        if self._neighbours_on_device(n):
+            self.neighbours_path = "device"
+            with torch.no_grad():
+                pos, sim, count = self._build_neighbours_device(unit, n)
+            host = (pos.cpu().numpy(), sim.cpu().numpy(), count.cpu().numpy())
+        else:
+            self.neighbours_path = "host"
+            host = item_neighbours_host(unit, ci, n)
+            pos = sim = count = None
+            if self.rank_path == "fused":
+                pos, sim, count = (torch.from_numpy(x).to(self.device) for x in host)
+        self._nbr = {"n": n, "host": host, "first_host": first_pos}
+        if pos is not None:
+            self._nbr["dev"] = (pos, sim, count)
+            self._nbr["first"] = torch.from_numpy(first_pos).to(self.device)
+
+    def neighbours_buffer_bytes(self):
+        """Device bytes of the neighbour table and the id -> first position index (0 before `build_neighbours`, or when the
+        table lives on the host only)."""
+        if self._nbr is None or "dev" not in self._nbr:
+            return 0
+        N, n = self.catalogue_size, self._nbr["n"]
+        return N * n * 8 + N * 4 + 4 * self._din_sizes()[1]
+
+    def similar_items(self, item_ids, top_k):
+        """After `build_neighbours(n)`: for every id of item_ids ([Q] integers) the kk = min(top_k, n) best neighbours of the
+        LOWEST catalogue position that holds it -- rows of the table -> {'item': int32 [Q, kk], 'index': int32 [Q, kk] (catalogue
+        positions), 'sim': float32 [Q, kk] (cosine similarity), 'count': int32 [Q]}.  An id the catalogue does not hold (and
+        item id 0) has count 0; entries at and beyond the count are -1 / -1 / NaN.  top_k > n is refused."""
+        nb = self._need_neighbours("similar_items")
+        k = check_top_k(top_k)
+        if k > nb["n"]:
+            raise _lib.RsxError("similar_items: top_k %d exceeds the %d neighbours the table keeps" % (k, nb["n"]))
+        q = item_ids.detach().cpu().numpy() if hasattr(item_ids, "detach") else np.asarray(item_ids)
+        if q.ndim != 1 or (q.size and not np.issubdtype(q.dtype, np.integer)):
+            raise _lib.RsxError("similar_items: item_ids must be a 1-D array of integers, got %s %s" % (q.dtype, q.shape))
+        pos, sim, count = nb["host"]
+        ci = self._cat["host"][0]
+        at = _target_positions(self._cat["first"], q.astype(np.int64)[None, :])[0]
+        ok = at >= 0
+        row = np.where(ok, at, 0)
+        index = np.where(ok[:, None], pos[row, :k], -1).astype(np.int32)
+        cnt = np.where(ok, np.minimum(count[row], k), 0).astype(np.int32)
+        s = np.where(index >= 0, sim[row, :k], np.float32(np.nan)).astype(np.float32)
+        item = np.where(index >= 0, ci[np.maximum(index, 0)], -1).astype(np.int32)
+        return {"item": item, "index": index, "sim": s, "count": cnt}
+
+    def _two_stage_cap(self, Pq):
+        return candidate_capacity(self.catalogue_size, Pq, self._nbr["n"])
+
+    def _retrieve_on_device(self, cap):
+        nb = self._nbr
+        return (nb is not None and "dev" in nb and self.rank_path == "fused" and cap <= self.max_candidates
+                and bool(_lib.lib().rsx_din_retrieve_candidates_supported(self.catalogue_size, self._din_sizes()[0], nb["n"], 0)))
+
+    def _two_stage_on_device(self, k, cap):
+        return self._retrieve_on_device(cap) and k <= TOPK_MAX_K and bool(_lib.lib().rsx_topk_rows_supported(cap, k))
+
+    def two_stage_path_for(self, top_k, hist_len=None):
+        """Where `recommend_two_stage(..., top_k=top_k)` runs for histories of hist_len positions (default: the bundle's):
+        "device" or "host" (None for a bundle that ranks no candidates).  "device" needs `build_neighbours`' table on the
+        device, rank_path == "fused", k <= 1024 and a candidate capacity -- min(N, hist_len (n + 1)) rounded up to 64 -- of at
+        most max_candidates.  A request that names more than 256 distinct positive exclusion ids for one user still takes the
+        host path; `two_stage_path` records what the latest request took."""
+        if self.script != "din":
+            return None
+        k = check_top_k(top_k)
+        if self._nbr is None:
+            return "host"
+        return "device" if self._two_stage_on_device(k, self._two_stage_cap(self._din_sizes()[0] if hist_len is None else hist_len)) else "host"
+
+    def _ts_setup(self, U, k):
+        """The static buffers of a device two-stage request beside the rank buffers: cand_pos [U, max_candidates], n_cand [U],
+        the exclusion ids [U, 256], and ONE flat buffer that holds out_val [U, k], behind it the catalogue positions [U, k] and
+        state [U, 2] (so the answer and `filled` come back in one copy) and, last, out_idx [U, k], which stays on the device."""
+        import torch
+        r = self._rank
+        t = r.get("ts")
+        if t is None:
+            self._drop_graphs("two_stage")
+            i32 = torch.int32
+            t = r["ts"] = {"pairs": 0, "buf": None,
+                           "pos": torch.zeros(r["U"] * self.max_candidates, dtype=i32, device=self.device),
+                           "n_cand": torch.zeros(r["U"], dtype=i32, device=self.device),
+                           "excl": torch.zeros(r["U"] * EXCL_MAX, dtype=i32, device=self.device)}
+        if k and (t["buf"] is None or r["U"] * k > t["pairs"]):
+            self._drop_graphs("two_stage")
+            t["pairs"] = r["U"] * k
+            t["buf"] = torch.zeros(3 * r["U"] * k + 2 * r["U"], dtype=torch.float32, device=self.device)
+        return t
+
+    def _two_stage_launch(self, U, k, E, cap, seeds):
+        """The whole request, one chain: the state's zeroing, rsx_din_retrieve_candidates (the candidates' ids straight into
+        the rank launch's candidate buffers), rsx_predict_din_rank over [U, cap], rsx_topk_rows_counted, and the gather that
+        turns the selected columns into catalogue positions.  Every address is fixed, so `_run` captures it as ONE graph per
+        (U, k, E, cap, seeds).  k = 0: the retrieval alone (`retrieve_candidates`)."""
+        import torch
+        r, t, nb, L = self._rank, self._rank["ts"], self._nbr, _lib.lib()
+        cat_i, cat_c = (x.data_ptr() for x in self._cat["dev"])
+        P, n_item = self._din_sizes()[:2]
+        pos, _, count = nb["dev"]
+        stream = torch.cuda.current_stream().cuda_stream
+        if k:
+            t["buf"][2 * U * k:2 * U * k + 2 * U].zero_()
+        _lib.check(L.rsx_din_retrieve_candidates(r["hist"][0].data_ptr(), P, nb["first"].data_ptr(), n_item, pos.data_ptr(),
+                                                 count.data_ptr(), nb["n"], cat_i, cat_c, self.catalogue_size,
+                                                 t["excl"].data_ptr(), int(E), int(seeds), t["pos"].data_ptr(),
+                                                 r["cand"][0].data_ptr(), r["cand"][1].data_ptr(), t["n_cand"].data_ptr(),
+                                                 int(cap), int(U), stream), "rsx_din_retrieve_candidates")
+        if not k:
+            return
+        self._rank_launch(U, cap)
+        val = t["buf"].data_ptr()
+        state, idx = val + 8 * U * k, val + 8 * U * k + 8 * U
+        _lib.check(L.rsx_topk_rows_counted(r["prob"].data_ptr(), int(cap), t["n_cand"].data_ptr(), int(U), int(cap), int(k), val,
+                                           idx, state, stream), "rsx_topk_rows_counted")
+        ints = t["buf"].view(torch.int32)
+        col = ints[2 * U * k + 2 * U:3 * U * k + 2 * U].view(U, k).clamp(0, cap - 1).long()     # (past `filled`: unspecified)
+        torch.gather(t["pos"][:U * cap].view(U, cap), 1, col, out=ints[U * k:2 * U * k].view(U, k))
+
+    def _two_stage_device(self, U, k, P, Pq, cap, u_iid_seq, u_icat_seq, ids, seeds):
+        """ids: int32 [U, E] host, E one of the exclusion capacities.  k = 0 -> (cand_pos [U, cap], n_cand [U]); otherwise the
+        answer of `recommend_two_stage_host` for U users."""
+        import torch
+        E = int(ids.shape[1])
+        with torch.no_grad():
+            r = self._rank_setup(U)
+            t = self._ts_setup(U, k)
+            self._rank_histories(r, U, P, Pq, u_iid_seq, u_icat_seq)
+            if E:
+                t["excl"][:U * E].view(U, E).copy_(torch.from_numpy(ids), non_blocking=True)
+            self._run(("two_stage", U, k, E, cap, bool(seeds)), lambda: self._two_stage_launch(U, k, E, cap, seeds))
+            if not k:
+                return t["pos"][:U * cap].view(U, cap).cpu().numpy(), t["n_cand"][:U].cpu().numpy()
+            h = t["buf"][:2 * U * k + 2 * U].cpu().numpy()           # the ONE device-to-host copy: pairs and `filled`
+        kk = min(k, self.catalogue_size)
+        count = h[2 * U * k:].view(np.int32).reshape(U, 2)[:, 0].copy()
+        prob = np.ascontiguousarray(h[:U * k].reshape(U, k)[:, :kk])
+        index = np.ascontiguousarray(h[U * k:2 * U * k].view(np.int32).reshape(U, k)[:, :kk])
+        pad = np.arange(kk)[None, :] >= count[:, None]
+        prob[pad], index[pad] = np.nan, 0
+        item = self._cat["host"][0][np.maximum(index, 0)]
+        item[pad], index[pad] = -1, -1
+        return {"prob": prob, "item": item, "index": index, "count": count}
+
+    def _two_stage_request(self, what, u_iid_seq, u_icat_seq, exclude_seen, exclude):
+        self._need_neighbours(what)
+        P, n_item, n_cate, _ = self._din_sizes()
+        shape = tuple(u_iid_seq.shape) if hasattr(u_iid_seq, "shape") else np.shape(u_iid_seq)
+        one = np.zeros((shape[0], 1) if len(shape) == 2 else 1, np.int32)      # a stand-in candidate: the histories' checks
+        U, _, Pq, single = check_rank_request(u_iid_seq, u_icat_seq, one, one, P, n_item, n_cate)
+        ids = _exclusion_ids(u_iid_seq, exclude, U, exclude_seen)
+        return U, P, Pq, single, ids, self._two_stage_cap(Pq)
+
+    def retrieve_candidates(self, u_iid_seq, u_icat_seq, exclude_seen=True, exclude=None):
+        """After `build_neighbours`: the catalogue positions stage two of `recommend_two_stage` would score for these histories
+        ([P'] or [U, P']) -- `retrieve_candidates_host` is the definition -> {'index': int32 [U, cap], ascending, -1 beyond the
+        count; 'count': int32 [U]}, cap = min(N, P' (n + 1)) rounded up to 64.  One user: index cut to count, count an int.
+        With held-out items this measures the candidate recall of the retrieval stage."""
+        U, P, Pq, single, ids, cap = self._two_stage_request("retrieve_candidates", u_iid_seq, u_icat_seq, exclude_seen, exclude)
+        padded = self._device_exclusion(ids) if self._retrieve_on_device(cap) else None
+        if padded is not None:
+            index, count = self._two_stage_device(U, 0, P, Pq, cap, u_iid_seq, u_icat_seq, padded, not exclude_seen)
+        else:
+            pos, _, cnt = self._nbr["host"]
+            rows = retrieve_candidates_host(pos, cnt, self._cat["host"][0], u_iid_seq, exclude, exclude_seen)
+            index = np.full((U, cap), -1, np.int32)
+            count = np.zeros(U, np.int32)
+            for u, x in enumerate(rows):
+                index[u, :len(x)], count[u] = x, len(x)
+        if single:
+            return {"index": index[0, :int(count[0])], "count": int(count[0])}
+        return {"index": index, "count": count}
+
+    def recommend_two_stage(self, u_iid_seq, u_icat_seq, top_k, exclude_seen=True, exclude=None):
+        """din.py bundles, after `set_catalogue` and `build_neighbours`: `recommend` over a RETRIEVED candidate set instead of
+        the whole catalogue.  Stage one takes the neighbour rows of the history's items (`retrieve_candidates`), stage two scores
+        those candidates exactly as `rank_candidates` scores them and returns the top_k best -- `recommend`'s result dictionary
+        and one-user / U-user forms; `recommend_two_stage_host` is the definition.  count[u] = min(top_k, candidates of u): it
+        can stay below top_k and can be 0 (an empty history, a history the catalogue does not hold).  There is NO back-fill
+        from the rest of the catalogue, and the list differs from `recommend`'s by design: an entry outside the candidate set
+        is never returned, however well it would score.  Category rules are not offered here.
+        `two_stage_path_for(k)` says where a request runs: "device": only the histories and the exclusion ids are shipped and
+        the whole request -- rsx_din_retrieve_candidates, rsx_predict_din_rank over [U, cap], rsx_topk_rows_counted, the
+        gather of the catalogue positions -- is ONE captured graph per (U, k, exclusion capacity, cap), one copy brings the
+        answer back; "host": `retrieve_candidates_host`, `rank_candidates` on the padded lists, `topk_rows_host` over each
+        list's valid part.  Both give the same bits."""
+        k = check_top_k(top_k)
+        U, P, Pq, single, ids, cap = self._two_stage_request("recommend_two_stage", u_iid_seq, u_icat_seq, exclude_seen, exclude)
+        padded = self._device_exclusion(ids) if self._two_stage_on_device(k, cap) else None
+        if padded is not None:
+            self.two_stage_path = "device"
+            out = self._two_stage_device(U, k, P, Pq, cap, u_iid_seq, u_icat_seq, padded, not exclude_seen)
+        else:
+            self.two_stage_path = "host"
+            pos, _, cnt = self._nbr["host"]
+            ci, cc = self._cat["host"]
+            N = self.catalogue_size
+            rows = retrieve_candidates_host(pos, cnt, ci, u_iid_seq, exclude, exclude_seen)
+            width = max(1, max(len(x) for x in rows))
+            li, lc = np.zeros((U, width), np.int32), np.zeros((U, width), np.int32)     # padded with (item 0, category 0)
+            for u, x in enumerate(rows):
+                li[u, :len(x)], lc[u, :len(x)] = ci[x], cc[x]
+            hi = u_iid_seq.reshape(U, -1) if hasattr(u_iid_seq, "reshape") else np.asarray(u_iid_seq).reshape(U, -1)
+            hc = u_icat_seq.reshape(U, -1) if hasattr(u_icat_seq, "reshape") else np.asarray(u_icat_seq).reshape(U, -1)
+            prob = self.rank_candidates(hi, hc, li, lc)["prob"].reshape(U, width)
+            kk = min(k, N)
+            out = {"prob": np.full((U, kk), np.nan, np.float32), "item": np.full((U, kk), -1, np.int32),
+                   "index": np.full((U, kk), -1, np.int32), "count": np.zeros(U, np.int32)}
+            for u, x in enumerate(rows):
+                if len(x):
+                    best = topk_rows_host(prob[u, :len(x)], kk)
+                    c = len(best["index"])
+                    at = x[best["index"]]
+                    out["prob"][u, :c], out["item"][u, :c], out["index"][u, :c], out["count"][u] = best["prob"], ci[at], at, c
         return _one_user(out) if single else out
 
     # -- offline ranking metrics over the resident catalogue (din.py; csrc/rank_count.hip) -----------------------------------
