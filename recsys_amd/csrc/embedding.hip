@@ -592,7 +592,8 @@ __device__ __forceinline__ bool segsum_wave(int wave, const float* __restrict__ 
   // The field's unique rows are dealt EVENLY to its wpf waves: rpw = ceil(nu / wpf) rows per wave (groups 0 .. rpw-1 own
   // them), so a field with a mid-sized vocabulary (say 50 rows, each a long Zipf-skewed segment) keeps 13 waves busy with 4
   // rows each instead of 4 waves with 16 -- the wave-cooperative walk of a long segment is sequential per wave.  rpw = 1
-  // (tiny vocabularies: every segment is long): group 0 owns the row and anything above 2 entries is walked by the whole wave.
+  // (tiny vocabularies: every segment is long): group 0 owns the row and anything above 2 entries is walked by the whole wave
+  // (except GPW < entries <= SEG_SHORT, below).
   const int rpw = nu <= wpf ? 1 : (nu + wpf - 1) / wpf;
   const bool spread = rpw == 1;
   const int j0 = wf * rpw;
@@ -636,8 +637,12 @@ __device__ __forceinline__ bool segsum_wave(int wave, const float* __restrict__ 
   acc = F4Z;
   a1 = 0.f;
   const int short_len = spread ? 2 : SEG_SHORT;   // a spread wave has 15 idle groups: cooperate on anything > 2
-  if (valid && L <= short_len) seg_range_sum<LPR>(c, e, beg, end, acc, a1);
-  unsigned long long todo = __ballot(valid && L > short_len && q == 0);
+  // ... where that IS the sequential sum (L <= GPW: one entry per group, added in ascending order) or the segment is long
+  // anyway.  GPW < L <= SEG_SHORT (D >= 32 only) would be cut into sub-ranges of 2..4 entries: another association than
+  // the ascending one every form promises for segments of <= SEG_SHORT entries -- those are walked by their own group.
+  const bool seq = L <= short_len || (GPW < SEG_SHORT && L > GPW && L <= SEG_SHORT);
+  if (valid && seq) seg_range_sum<LPR>(c, e, beg, end, acc, a1);
+  unsigned long long todo = __ballot(valid && !seq && q == 0);
   while (todo) {  // wave-uniform loop over the long segments owned by this wave
     const int src = __ffsll((long long)todo) - 1;  // lane (owner group, q = 0)
     todo &= todo - 1;
@@ -1140,8 +1145,9 @@ __device__ __forceinline__ bool segsum_wave_lds(int wave, const float* __restric
     }
   };
   const int short_len = spread ? 2 : SEG_SHORT;
-  if (valid && L <= short_len) range(e, beg, end, acc, a1);
-  unsigned long long todo = __ballot(valid && L > short_len && q == 0);
+  const bool seq = L <= short_len || (GPW < SEG_SHORT && L > GPW && L <= SEG_SHORT);      // (as in segsum_wave)
+  if (valid && seq) range(e, beg, end, acc, a1);
+  unsigned long long todo = __ballot(valid && !seq && q == 0);
   while (todo) {  // wave-uniform loop over the long segments owned by this wave (as in segsum_wave)
     const int src = __ffsll((long long)todo) - 1;
     todo &= todo - 1;
