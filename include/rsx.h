@@ -955,6 +955,30 @@ int rsx_din_retrieve_candidates(const int32_t* hist_item, int P, const int32_t* 
                                 const int32_t* excl, int E, int include_seeds, int32_t* cand_pos, int32_t* cand_item,
                                 int32_t* cand_cate, int32_t* n_cand, int cap, int U, rsx_stream_t stream);
 
+/* (d) rsx_rank_count_lists (csrc/rank_count_lists.hip): where given item ids stand inside per-row candidate lists, by counting.
+ * serving.Predictor.evaluate_two_stage.  Added behind rsx_version() 107 without a new number (the version stays 107): a caller
+ * that must tell the two apart looks the symbol up.
+ * Row u is one user's list: n columns of which the first n_valid[u] are LIVE (a count outside [0, n] is clamped into it);
+ * scores: row u at scores + u * ld; cand_id / cand_pos [U, n]: the item id and the catalogue position of every column, cand_pos
+ * ascending over the live columns -- what rsx_din_retrieve_candidates wrote and rsx_predict_din_rank scored.  tgt_id [U, T].
+ * For slot t with tgt_id[u, t] > 0, c is the LOWEST live column j with cand_id[u, j] == tgt_id[u, t].  With such a c:
+ *   out_score[u, t] = scores[u, c] (its bits), out_pos[u, t] = cand_pos[u, c], and
+ *   out_count[u, t] = the number of live columns j whose (scores[u, j], j) comes before (scores[u, c], c) in the ORDER of
+ *   rsx_topk_rows: the higher score, equal scores (-0.0 == +0.0) by the lower column, every NaN after every number --
+ *   the 0-based index of column c in the list rsx_topk_rows_counted selects from the row.
+ * Without one, and for a slot with tgt_id <= 0: out_count = -1, out_pos = -1, out_score = NaN (0x7fc00000).  EVERY slot of the
+ * three outputs [U, T] is written and nothing else is, so nothing needs zeroing.  Columns at and beyond n_valid[u] are never
+ * read: neither their ids nor their scores.
+ * One workgroup per row, two passes over the live columns: an integer LDS atomicMin per (slot, matching column), then
+ * rsx_rank_count_rows' count with the T keys and counters in registers.  No global atomics, no workspace, no grid-wide step;
+ * a row's outputs depend on that row's inputs only.  Deterministic.
+ * RSX_EINVAL (before any HIP call): a NULL pointer, U / n / T <= 0, ld < n.  Envelope (rsx_rank_count_lists_supported;
+ * RSX_EUNSUPPORTED outside, before any HIP call): T <= 32. */
+int rsx_rank_count_lists_supported(int n, int T);
+int rsx_rank_count_lists(const float* scores, int ld, const int32_t* cand_id, const int32_t* cand_pos, const int32_t* n_valid,
+                         const int32_t* tgt_id, int T, int32_t* out_count, int32_t* out_pos, float* out_score, int U, int n,
+                         rsx_stream_t stream);
+
 /* ---------------------------------------------------------------------------------------------
  * DCN cross layers, dcn/dcn.py:132-142: x_{l+1} = (x_l . w_l) * x0 + x_l + b_l, all L
  * layers fused per example.  dim % 4 == 0, dim <= 1024, L <= 8.

@@ -66,6 +66,14 @@ The reference exports a SavedModel whose serving signature parses serialized `tf
               `retrieve_candidates_host`, `rank_candidates`, `topk_rows_host`.  The same bits either way;
               `recommend_two_stage_host` is the definition.  No back-fill: a list can be shorter than top_k and differs from
               `recommend`'s by design.
+              `evaluate_two_stage(u_iid_seq, u_icat_seq, held_out, ks, n_neighbours=m)` scores that list offline: whether the
+              retrieval stage kept each held-out item and the exact rank of the kept ones among the user's candidates
+              (`two_stage_ranks_host` is the definition; `two_stage_metrics` adds CandRecall and the mean candidate count to
+              `ranking_metrics`), for the first m neighbours of the table already built.
+              evaluate_two_stage_path_for(T, hist_len, m) == "device": per block of users ONE graph --
+              rsx_din_retrieve_candidates, rsx_predict_din_rank, rsx_rank_count_lists (csrc/rank_count_lists.hip) -- and 12
+              bytes per (user, slot) copied back; "host": `retrieve_candidates_host`, `rank_candidates`, numpy.  The same
+              integers and probability bits either way.
 """
 import ctypes as C
 import importlib
@@ -942,6 +950,112 @@ def candidate_capacity(N, hist_len, n_neighbours):
     return (c + 63) // 64 * 64
 
 
+# ---- offline evaluation of the two-stage list (din.py): pure numpy, no device -------------------------------------------------
+RETRIEVED_PAD, RETRIEVED_MISSING = -2, -1     # `retrieved` of a padding slot / of an id outside the catalogue or excluded
+
+
+def _list_place(s, c):
+    """The number of entries of the float32 list s that precede entry c in `recommend_host`'s order, by counting: j precedes c
+    when s[j] > s[c], or they are equal (-0.0 == +0.0) and j < c; when s[c] is a NaN, every number and the NaNs before c."""
+    where = np.arange(len(s))
+    if np.isnan(s[c]):
+        return int(np.count_nonzero(~np.isnan(s) | (where < c)))
+    return int(np.count_nonzero((s > s[c]) | ((s == s[c]) & (where < c))))
+
+
+def two_stage_ranks_host(prob, nbr_pos, nbr_count, cat_item, hist_item, held_out, exclude=None, exclude_seen=True):
+    """The definition of `Predictor.evaluate_two_stage`'s ranks, in numpy.  prob: float32 [N] (one user) or [U, N], the scores of
+    ALL catalogue entries, as for `recommend_two_stage_host`; held_out: int [T] / [U, T] (`check_held_out`).  Per user the
+    candidates are `retrieve_candidates_host(...)`.  For a held-out id h > 0:
+      - h is not in the catalogue, or is a positive id of the exclusion list (`_exclusion_ids`): rank = RANK_MISSING,
+        retrieved = -1;
+      - else no candidate position holds h: rank = RANK_MISSING, retrieved = 0 -- a miss of the retrieval stage is a miss of
+        the list;
+      - else the TARGET ENTRY is the lowest CANDIDATE position that holds h -- not the lowest catalogue position: a duplicate
+        entry can be a neighbour where the first copy is not, all copies score the same bits, and the lowest candidate copy is
+        the one the list shows first -- rank = the number of candidates that precede it in `recommend_host`'s order (a higher
+        score first, equal scores -- -0.0 == +0.0 -- by the lower position, every NaN after every number): the index at which
+        that position stands in recommend_two_stage_host(..., top_k=N)['index']; retrieved = 1.
+    Padding (h <= 0): rank = RANK_PAD, retrieved = -2.
+    -> {'rank': int32 [U, T], 'retrieved': int8 [U, T], 'target_index': int32 [U, T] (the target entry's catalogue position,
+    -1 where retrieved != 1), 'target_prob': float32 [U, T] (NaN where retrieved != 1), 'n_candidates': int32 [U]}; the
+    one-user form drops the leading axis and n_candidates is an int.  Written by counting, as `target_ranks_host` is."""
+    a = np.asarray(prob, np.float32)
+    cat = np.asarray(cat_item)
+    if a.ndim not in (1, 2) or cat.ndim != 1 or a.shape[-1] != cat.shape[0] or cat.shape[0] < 1:
+        raise _lib.RsxError("two_stage_ranks_host: expected scores [N] or [U, N] over a catalogue [N], N >= 1; got %s and %s"
+                            % (a.shape, cat.shape))
+    rows = np.atleast_2d(a)
+    U, N = rows.shape
+    held = check_held_out(held_out, U, a.ndim == 1, "two_stage_ranks_host")
+    cands = retrieve_candidates_host(nbr_pos, nbr_count, cat, hist_item, exclude, exclude_seen)
+    if len(cands) != U:
+        raise _lib.RsxError("two_stage_ranks_host: %d histories for %d rows of scores" % (len(cands), U))
+    ids = _exclusion_ids(hist_item, exclude, U, exclude_seen)
+    cat = cat.astype(np.int64)
+    T = held.shape[1]
+    out = {"rank": np.full((U, T), RANK_PAD, np.int32), "retrieved": np.full((U, T), RETRIEVED_PAD, np.int8),
+           "target_index": np.full((U, T), -1, np.int32), "target_prob": np.full((U, T), np.nan, np.float32),
+           "n_candidates": np.asarray([len(x) for x in cands], np.int32)}
+    for u in range(U):
+        pos = cands[u].astype(np.int64)
+        s, cid = rows[u, pos], cat[pos]
+        known = np.isin(held[u], cat) & ~np.isin(held[u], ids[u][ids[u] > 0])
+        for t in np.flatnonzero(held[u] > 0):
+            at = np.flatnonzero(cid == held[u, t])
+            if not known[t] or not len(at):
+                out["rank"][u, t], out["retrieved"][u, t] = RANK_MISSING, 0 if known[t] else RETRIEVED_MISSING
+                continue
+            c = int(at[0])
+            out["rank"][u, t], out["retrieved"][u, t] = _list_place(s, c), 1
+            out["target_index"][u, t], out["target_prob"][u, t] = pos[c], s[c]
+    if a.ndim == 2:
+        return out
+    return {key: (int(v[0]) if key == "n_candidates" else v[0]) for key, v in out.items()}
+
+
+def two_stage_metrics(rank, retrieved, n_candidates, ks, per_user=False):
+    """`ranking_metrics(rank, ks, per_user)` unchanged, plus what the retrieval stage kept.  retrieved: int [U, T] / [T] like
+    rank (`two_stage_ranks_host`: 1 retrieved, 0 eligible and not retrieved, -1 not in the catalogue or excluded, -2 padding);
+    n_candidates: int [U] (or an int, one user).  In float64:
+      'CandRecall'        per user the slots with retrieved == 1 over the slots with retrieved >= 0, then the mean over the
+                          users with at least one such slot; NaN when no user has one
+      'CandRecall_users'  the number of those users
+      'candidates_mean'   the mean of n_candidates
+    per_user=True adds 'CandRecall_user', float64 [U], NaN for a user without an eligible slot."""
+    out = ranking_metrics(rank, ks, per_user)
+    g = np.asarray(retrieved)
+    if g.shape != np.asarray(rank).shape or not np.issubdtype(g.dtype, np.integer) or int(g.min()) < RETRIEVED_PAD or int(g.max()) > 1:
+        raise _lib.RsxError("two_stage_metrics: retrieved must be integers in [%d, 1] of rank's shape %s, got %s %s"
+                            % (RETRIEVED_PAD, np.asarray(rank).shape, g.dtype, g.shape))
+    g = np.atleast_2d(g)
+    nc = np.atleast_1d(np.asarray(n_candidates))
+    if nc.shape != (g.shape[0],) or not np.issubdtype(nc.dtype, np.integer) or int(nc.min()) < 0:
+        raise _lib.RsxError("two_stage_metrics: n_candidates must be %d non-negative integers, got %s %s" % (g.shape[0], nc.dtype, nc.shape))
+    eligible, kept = np.count_nonzero(g >= 0, axis=1), np.count_nonzero(g == 1, axis=1)
+    users = eligible > 0
+    with np.errstate(invalid="ignore", divide="ignore"):
+        per = np.where(users, kept / eligible.astype(np.float64), np.nan)
+    out["CandRecall"] = float(per[users].mean()) if users.any() else float("nan")
+    out["CandRecall_users"] = int(users.sum())
+    out["candidates_mean"] = float(nc.astype(np.float64).mean())
+    if per_user:
+        out["CandRecall_user"] = per
+    return out
+
+
+def narrow_neighbours_host(nbr_pos, nbr_count, m):
+    """The first m neighbours of every row of a table built with n >= m: (nbr_pos[:, :m], minimum(nbr_count, m)).  The rows are
+    ordered best first, so this is `item_neighbours_host(..., m)`'s table bit for bit.  RsxError unless m is an integer (no
+    bool) in [1, n]."""
+    pos, cnt = np.asarray(nbr_pos), np.asarray(nbr_count)
+    if pos.ndim != 2 or cnt.shape != (pos.shape[0],):
+        raise _lib.RsxError("narrow_neighbours_host: neighbour table %s / %s is not [N, n] with [N]" % (pos.shape, cnt.shape))
+    if isinstance(m, (bool, np.bool_)) or not isinstance(m, (int, np.integer)) or not 1 <= int(m) <= pos.shape[1]:
+        raise _lib.RsxError("n_neighbours must be an integer in [1, %d] (the table built), not %r" % (pos.shape[1], m))
+    return np.ascontiguousarray(pos[:, :int(m)]), np.minimum(cnt, int(m)).astype(cnt.dtype)
+
+
 # ---- Predictor ---------------------------------------------------------------------------------------------------------------
 class Predictor:
     """An exported model ready to answer requests.  See the module docstring for the two paths.  `table_dtype` is the
@@ -1011,6 +1125,7 @@ class Predictor:
         self._nbr = None                    # `build_neighbours`' table (din.py bundles)
         self.neighbours_path = None         # where the latest `build_neighbours` built it
         self.two_stage_path = None          # where the latest `recommend_two_stage` ran
+        self.evaluate_two_stage_path = None # where the latest `evaluate_two_stage` ranked
         if self.script == "din":
             self.rank_path = "fused" if self._rank_supported() else "layers"
             self.topk_path = "device" if self.rank_path == "fused" else "host"
@@ -1262,8 +1377,9 @@ class Predictor:
             # request buffers of one chunk: the histories [U, P], the candidates and their probabilities [U, max_candidates]
             # (a request of fewer users or candidates uses leading parts of them; graphs captured over smaller buffers go)
             dev, i32 = self.device, torch.int32
-            self._drop_graphs("rank", "rank_topk", "recommend", "eval_recommend", "two_stage")
+            self._drop_graphs("rank", "rank_topk", "recommend", "eval_recommend", "two_stage", "eval_two_stage")
             r.pop("ts", None)
+            r.pop("ets", None)
             r.pop("topk", None)
             r.pop("rec", None)
             r.pop("eval", None)
@@ -1442,7 +1558,7 @@ class Predictor:
         self._need_din("set_catalogue")
         _, n_item, n_cate, _ = self._din_sizes()
         ci, cc = check_catalogue(i_id, i_cate, n_item, n_cate)
-        self._drop_graphs("recommend", "eval_recommend", "two_stage")
+        self._drop_graphs("recommend", "eval_recommend", "two_stage", "eval_two_stage")
         self._nbr, self.neighbours_path = None, None                   # the neighbour table names positions of the old catalogue
         self._cat = {"host": (ci, cc), "dev": [torch.from_numpy(x).to(self.device) for x in (ci, cc)],
                      "first": catalogue_first_positions(ci)}       # id -> its lowest position (evaluate_recommend)
@@ -1716,8 +1832,8 @@ class Predictor:
         ci, _ = self._cat["host"]
         emb = self._est.store.embeddings["i_id"].table.detach()[:, :K].float().cpu().numpy()
         unit = unit_rows_host(emb[ci])
-        self._drop_graphs("two_stage")
-        self._nbr = None
+        self._drop_graphs("two_stage", "eval_two_stage")
+        self._nbr = None                                               # (with it go `evaluate_two_stage`'s narrowed copies)
         ids, first = self._cat["first"]
         first_pos = np.full(n_item, -1, np.int32)
         first_pos[ids] = first
@@ -1739,11 +1855,12 @@ class Predictor:
 
     def neighbours_buffer_bytes(self):
         """Device bytes of the neighbour table and the id -> first position index (0 before `build_neighbours`, or when the
-        table lives on the host only)."""
+        table lives on the host only), plus N m 4 + N 4 for every narrowed copy `evaluate_two_stage(n_neighbours=m)` keeps."""
         if self._nbr is None or "dev" not in self._nbr:
             return 0
         N, n = self.catalogue_size, self._nbr["n"]
-        return N * n * 8 + N * 4 + 4 * self._din_sizes()[1]
+        narrowed = sum(N * m * 4 + N * 4 for m, e in self._nbr.get("narrow", {}).items() if "dev" in e)
+        return N * n * 8 + N * 4 + 4 * self._din_sizes()[1] + narrowed
 
     def similar_items(self, item_ids, top_k):
         """After `build_neighbours(n)`: for every id of item_ids ([Q] integers) the kk = min(top_k, n) best neighbours of the
@@ -2083,6 +2200,201 @@ class Predictor:
                 tprob[b:e][ok] = np.take_along_axis(prob, np.where(ok, pos, 0), 1)[ok]
         out = ranking_metrics(rank, ks, per_user)
         out["rank"], out["target_prob"] = (rank[0], tprob[0]) if single else (rank, tprob)
+        return out
+
+    # -- offline evaluation of the two-stage list (din.py; csrc/rank_count_lists.hip) ----------------------------------------
+    def _eval_neighbours(self, n_neighbours):
+        """`evaluate_two_stage`'s n_neighbours -> m: None is the built n; RsxError unless an integer (no bool) in [1, built n]."""
+        n = self._nbr["n"]
+        m = n if n_neighbours is None else n_neighbours
+        if isinstance(m, (bool, np.bool_)) or not isinstance(m, (int, np.integer)) or not 1 <= int(m) <= n:
+            raise _lib.RsxError("evaluate_two_stage: n_neighbours must be None or an integer in [1, %d] (the table built), not %r"
+                                % (n, n_neighbours))
+        return int(m)
+
+    def _narrowed_neighbours(self, m):
+        """The table of the first m neighbours: `build_neighbours`' own for m == the built n, otherwise a contiguous copy kept
+        per m inside the table's record -- host (`narrow_neighbours_host`) and, when the table is on the device, pos[:, :m] and
+        count.clamp(max=m) there.  Whatever replaces the table (`set_catalogue`, `build_neighbours`) drops the copies with it."""
+        nb = self._nbr
+        if m == nb["n"]:
+            return nb
+        kept = nb.setdefault("narrow", {})
+        if m not in kept:                                            # (pos, sim, count) like the table's own; sim is not kept
+            pos, _, cnt = nb["host"]
+            hp, hc = narrow_neighbours_host(pos, cnt, m)
+            e = kept[m] = {"n": m, "host": (hp, None, hc)}
+            if "dev" in nb:
+                e["dev"] = (nb["dev"][0][:, :m].contiguous(), None, nb["dev"][2].clamp(max=m).contiguous())
+        return kept[m]
+
+    def _evaluate_two_stage_on_device(self, T, cap):
+        return self._retrieve_on_device(cap) and T <= RANK_MAX_T and bool(_lib.lib().rsx_rank_count_lists_supported(cap, T))
+
+    def evaluate_two_stage_path_for(self, T, hist_len=None, n_neighbours=None):
+        """Where `evaluate_two_stage` ranks T held-out items per user for histories of hist_len positions (default: the
+        bundle's) over the first n_neighbours of the table (default: all): "device" or "host" (None for a bundle that ranks no
+        candidates).  "device" needs `build_neighbours`' table on the device, rank_path == "fused", T <= 32 and a candidate
+        capacity of at most max_candidates.  A request that names more than 256 distinct positive exclusion ids for one user
+        still takes the host path; `evaluate_two_stage_path` records what the latest request took."""
+        if self.script != "din":
+            return None
+        if isinstance(T, (bool, np.bool_)) or not isinstance(T, (int, np.integer)) or int(T) < 1:
+            raise _lib.RsxError("evaluate_two_stage: T must be an integer >= 1, not %r" % (T,))
+        if self._nbr is None:
+            return "host"
+        m = self._eval_neighbours(n_neighbours)
+        cap = candidate_capacity(self.catalogue_size, self._din_sizes()[0] if hist_len is None else hist_len, m)
+        return "device" if self._evaluate_two_stage_on_device(int(T), cap) else "host"
+
+    def _ets_setup(self):
+        """The static buffers of a device `evaluate_two_stage` beside the rank buffers and the two-stage ones (cand_pos and the
+        exclusion ids are `_ts_setup`'s), for the users the rank buffers hold and 32 targets each: the eligible targets' item
+        ids [U, T], and ONE flat buffer with count, position and score, three [U, T], and behind them n_cand [U] of the block
+        at hand -- so everything comes back in one copy."""
+        import torch
+        r = self._rank
+        self._ts_setup(r["U"], 0)
+        t = r.get("ets")
+        if t is None:
+            n = r["U"] * RANK_MAX_T
+            t = r["ets"] = {"tgt": torch.zeros(n, dtype=torch.int32, device=self.device),
+                            "out": torch.zeros(3 * n + r["U"], dtype=torch.float32, device=self.device)}
+        return t
+
+    def _eval_two_stage_launch(self, U, T, E, cap, seeds, nb):
+        """One block of users, one chain: rsx_din_retrieve_candidates (the candidates' ids straight into the rank launch's
+        candidate buffers, as in `_two_stage_launch`; n_cand into the answer's buffer), rsx_predict_din_rank over [U, cap],
+        rsx_rank_count_lists.  The last writes every output slot, so nothing is zeroed.  Every address is fixed, so `_run`
+        captures it as ONE graph per (U, T, E, cap, seeds, m)."""
+        import torch
+        r, ts, t, L = self._rank, self._rank["ts"], self._rank["ets"], _lib.lib()
+        cat_i, cat_c = (x.data_ptr() for x in self._cat["dev"])
+        P, n_item = self._din_sizes()[:2]
+        pos, _, count = nb["dev"]
+        out = t["out"].data_ptr()
+        n_cand = out + 12 * U * T
+        stream = torch.cuda.current_stream().cuda_stream
+        _lib.check(L.rsx_din_retrieve_candidates(r["hist"][0].data_ptr(), P, self._nbr["first"].data_ptr(), n_item, pos.data_ptr(),
+                                                 count.data_ptr(), nb["n"], cat_i, cat_c, self.catalogue_size,
+                                                 ts["excl"].data_ptr(), int(E), int(seeds), ts["pos"].data_ptr(),
+                                                 r["cand"][0].data_ptr(), r["cand"][1].data_ptr(), n_cand,
+                                                 int(cap), int(U), stream), "rsx_din_retrieve_candidates")
+        self._rank_launch(U, cap)
+        _lib.check(L.rsx_rank_count_lists(r["prob"].data_ptr(), int(cap), r["cand"][0].data_ptr(), ts["pos"].data_ptr(), n_cand,
+                                          t["tgt"].data_ptr(), int(T), out, out + 4 * U * T, out + 8 * U * T, int(U), int(cap),
+                                          stream), "rsx_rank_count_lists")
+
+    def _eval_two_stage_block(self, hi, hc, P, Pq, excl, tgt, cap, seeds, nb):
+        """hi, hc: int32 [U, P'] tensors; excl: int32 [U, E] host; tgt: int32 [U, T] host (T a target capacity; 0 where the slot
+        has no eligible target) -> (count int32 [U, T], position int32 [U, T], score float32 [U, T], n_cand int32 [U])."""
+        import torch
+        U, T = tgt.shape
+        E = int(excl.shape[1])
+        with torch.no_grad():
+            r = self._rank
+            t = self._ets_setup()
+            self._rank_histories(r, U, P, Pq, hi, hc)
+            if E:
+                r["ts"]["excl"][:U * E].view(U, E).copy_(torch.from_numpy(excl), non_blocking=True)
+            t["tgt"][:U * T].copy_(torch.from_numpy(tgt.reshape(-1)), non_blocking=True)
+            self._run(("eval_two_stage", U, T, E, cap, bool(seeds), nb["n"]),
+                      lambda: self._eval_two_stage_launch(U, T, E, cap, seeds, nb))
+            h = t["out"][:3 * U * T + U].cpu().numpy()               # the ONE device-to-host copy of the block
+        ints = h.view(np.int32)
+        return (ints[:U * T].reshape(U, T).copy(), ints[U * T:2 * U * T].reshape(U, T).copy(),
+                h[2 * U * T:3 * U * T].reshape(U, T).copy(), ints[3 * U * T:].copy())
+
+    def evaluate_two_stage(self, u_iid_seq, u_icat_seq, held_out, ks=(10, 50, 100), exclude_seen=True, exclude=None,
+                           user_block=16, per_user=False, n_neighbours=None):
+        """din.py bundles, after `set_catalogue` and `build_neighbours`: did the retrieval stage keep each user's held-out
+        items, and where do the kept ones land in the list `recommend_two_stage` would return?  Histories, `exclude` and
+        held_out as in `evaluate_recommend`; `two_stage_ranks_host` is the definition of the ranks, `two_stage_metrics` of the
+        metrics -> two_stage_metrics(rank, retrieved, n_candidates, ks, per_user) plus 'rank' (int32 [U, T] / [T]: 0-based among
+        the user's candidates, RANK_MISSING = -1 for an id that was not retrieved, is not in the catalogue or is excluded,
+        RANK_PAD = -2 for padding), 'retrieved' (int8: 1 retrieved, 0 eligible and not retrieved, -1 not in the catalogue or
+        excluded, -2 padding), 'target_index' (int32: the catalogue position of the lowest CANDIDATE entry that holds the id,
+        -1 where retrieved != 1), 'target_prob' (float32, NaN there) and 'n_candidates' (int32 [U]; an int for one user).
+        n_neighbours = m (an integer in [1, the built n]; None: the built n) evaluates the first m neighbours of every row --
+        `build_neighbours(m)`'s table, from the one already built -- with cap = candidate_capacity(N, P', m).
+        `evaluate_two_stage_path_for(T, hist_len, m)` says where a request ranks.  "device" (the table on the device,
+        rank_path == "fused", cap <= max_candidates, T <= 32, at most 256 distinct positive exclusion ids per user): the host
+        classifies every slot (padding, missing / excluded, eligible) and ships the histories, the exclusion ids and the
+        eligible ids; per block of at most `user_block` users ONE captured graph per (users, target capacity, exclusion
+        capacity, cap, seeds, m) runs rsx_din_retrieve_candidates, rsx_predict_din_rank over [U, cap] and
+        rsx_rank_count_lists, and ONE copy of 12 bytes per (user, slot) plus n_cand comes back; a narrowed contiguous copy of
+        the device table is kept per m < n (`neighbours_buffer_bytes` counts it).  "host": `retrieve_candidates_host` on the
+        narrowed table, `rank_candidates` on the padded lists, then numpy.  Both give the same integers and probability bits."""
+        import torch
+        self._need_neighbours("evaluate_two_stage")
+        ks = check_ks(ks)
+        if isinstance(user_block, (bool, np.bool_)) or not isinstance(user_block, (int, np.integer)) or int(user_block) < 1:
+            raise _lib.RsxError("evaluate_two_stage: user_block must be an integer >= 1, not %r" % (user_block,))
+        user_block = int(user_block)
+        m = self._eval_neighbours(n_neighbours)
+        P, n_item, n_cate, _ = self._din_sizes()
+        shape = tuple(u_iid_seq.shape) if hasattr(u_iid_seq, "shape") else np.shape(u_iid_seq)
+        one = np.zeros((shape[0], 1) if len(shape) == 2 else 1, np.int32)      # a stand-in candidate: the histories' checks
+        U, _, Pq, single = check_rank_request(u_iid_seq, u_icat_seq, one, one, P, n_item, n_cate)
+        held = check_held_out(held_out, U, single, "evaluate_two_stage")
+        T = held.shape[1]
+        ids = _exclusion_ids(u_iid_seq, exclude, U, exclude_seen)
+        ci, cc = self._cat["host"]
+        cap = candidate_capacity(self.catalogue_size, Pq, m)
+        nb = self._narrowed_neighbours(m)
+        hi, hc = (self._dev32(x, U) if Pq else torch.zeros((U, 0), dtype=torch.int32) for x in (u_iid_seq, u_icat_seq))
+        # every slot's class, on the host: padding, missing / excluded, or eligible (what the retrieval stage may keep or lose)
+        known = _target_positions(self._cat["first"], held) >= 0
+        for u in range(U):
+            known[u] &= ~np.isin(held[u], ids[u][ids[u] > 0])
+        rank = np.where(held > 0, RANK_MISSING, RANK_PAD).astype(np.int32)
+        retrieved = np.where(held > 0, np.where(known, 0, RETRIEVED_MISSING), RETRIEVED_PAD).astype(np.int8)
+        tindex = np.full((U, T), -1, np.int32)
+        tprob = np.full((U, T), np.nan, np.float32)
+        n_cand = np.zeros(U, np.int32)
+        excl = self._device_exclusion(ids) if self._evaluate_two_stage_on_device(T, cap) else None
+        if excl is not None:
+            self.evaluate_two_stage_path = "device"
+            Tc = self._target_capacity(T)
+            tgt = np.zeros((U, Tc), np.int32)                        # slots without an eligible target: id 0, which matches nothing
+            tgt[:, :T] = np.where(known, held, 0)
+            self._rank_setup(min(U, user_block))
+            for b in range(0, U, user_block):
+                e = min(U, b + user_block)
+                count, pos, score, n_cand[b:e] = self._eval_two_stage_block(hi[b:e], hc[b:e], P, Pq, excl[b:e],
+                                                                            np.ascontiguousarray(tgt[b:e]), cap, not exclude_seen, nb)
+                ok = count[:, :T] >= 0
+                rank[b:e][ok], retrieved[b:e][ok] = count[:, :T][ok], 1
+                tindex[b:e][ok], tprob[b:e][ok] = pos[:, :T][ok], score[:, :T][ok]
+        else:
+            self.evaluate_two_stage_path = "host"
+            hist_np = hi.cpu().numpy()
+            ex_np = None
+            if exclude is not None:
+                ex_np = (exclude.detach().cpu().numpy() if hasattr(exclude, "detach") else np.asarray(exclude)).reshape(U, -1)
+            npos, _, ncnt = nb["host"]
+            for b in range(0, U, user_block):
+                e = min(U, b + user_block)
+                rows = retrieve_candidates_host(npos, ncnt, ci, hist_np[b:e], None if ex_np is None else ex_np[b:e], exclude_seen)
+                width = max(1, max(len(x) for x in rows))
+                li, lc = np.zeros((e - b, width), np.int32), np.zeros((e - b, width), np.int32)     # padded with (item 0, category 0)
+                for u, x in enumerate(rows):
+                    li[u, :len(x)], lc[u, :len(x)] = ci[x], cc[x]
+                prob = self.rank_candidates(hi[b:e], hc[b:e], li, lc)["prob"].reshape(e - b, width)
+                for u, x in enumerate(rows):
+                    n_cand[b + u] = len(x)
+                    s, cid = prob[u, :len(x)], ci[x].astype(np.int64)
+                    for t in np.flatnonzero(known[b + u]):
+                        at = np.flatnonzero(cid == held[b + u, t])
+                        if len(at):
+                            c = int(at[0])
+                            rank[b + u, t], retrieved[b + u, t] = _list_place(s, c), 1
+                            tindex[b + u, t], tprob[b + u, t] = x[c], s[c]
+        out = two_stage_metrics(rank, retrieved, n_cand, ks, per_user)
+        if single:
+            out.update(rank=rank[0], retrieved=retrieved[0], target_index=tindex[0], target_prob=tprob[0], n_candidates=int(n_cand[0]))
+        else:
+            out.update(rank=rank, retrieved=retrieved, target_index=tindex, target_prob=tprob, n_candidates=n_cand)
         return out
 
     # -- public ------------------------------------------------------------------------------------------------------------
