@@ -981,7 +981,10 @@ int rsx_rank_count_lists(const float* scores, int ld, const int32_t* cand_id, co
 
 /* ---------------------------------------------------------------------------------------------
  * DCN cross layers, dcn/dcn.py:132-142: x_{l+1} = (x_l . w_l) * x0 + x_l + b_l, all L
- * layers fused per example.  dim % 4 == 0, dim <= 1024, L <= 8.
+ * layers fused per example.  Forward: dim % 4 == 0, dim <= 1024, L <= 8.  Backward: the same, and the gradient slab of a wave,
+ * (2L + 1) * dim floats, must fit 64 KiB of LDS -- (2L + 1) * dim <= 16 384: every L <= 7 up to dim 1024, L = 8 up to dim 960
+ * (RSX_EUNSUPPORTED beyond, before any launch).  L <= 3 with 4 * (2L + 1) * dim floats <= 80 KiB (L = 3: dim <= 728) takes
+ * the four-wave form, everything else one wave per workgroup.
  * ------------------------------------------------------------------------------------------- */
 /* s[B,L] receives the per-layer scalars (saved for backward); xL (nullable) the final x_L; cz (nullable, needs wout)
  * the logit contribution <x_L, wout> of tf.layers.dense(concat[deep, x_L], 1) dcn/dcn.py:151-152.                  */
@@ -992,9 +995,14 @@ int rsx_cross_fwd(const float* x0, const float* W, const float* Bc, const float*
  * gather writes it, s / cz as rsx_cross_fwd; the same bits as the two launches.                                             */
 int rsx_gather_cross_fwd(const float* tables, const int32_t* row_off, const int32_t* ids, float* E, const float* W, const float* Bc,
                          const float* wout, float* s, float* cz, int B, int F, int D, int L, rsx_stream_t stream);
+/* Floats of backward workspace for a CAPACITY of B examples: enough for every batch b <= B, in either backward form and for the
+ * rider of rsx_tower_bwd_extra -- the largest number of (2L + 1) * dim gradient partials any such batch writes.  (The number of
+ * partials is NOT monotonic in the batch: the examples per wave step up with it, so 2 000 examples write more partials than
+ * 3 000.)  The tuning variables RSX_CROSS_EPW / RSX_CROSS_EPW4, when set, are honoured.  0 for B, dim or L <= 0.          */
 size_t rsx_cross_bwd_workspace_floats(int B, int dim, int L);
-/* Given dxL [B,dim] and/or gz [B] (gradient of cz): dX (+)= d loss/d x0, dW[L,dim], dB[L,dim], dwout[dim].
- * x_1..x_L are recomputed from s.  workspace: rsx_cross_bwd_workspace_floats() floats.                             */
+/* Given dxL [B,dim] and/or gz [B] (gradient of cz): dX (+)= d loss/d x0, dW[L,dim], dB[L,dim], dwout[dim] (WRITTEN, not added to;
+ * dwout only with gz -- without it a buffer handed in is left alone).  x_1..x_L are recomputed from s.
+ * workspace: rsx_cross_bwd_workspace_floats(B' >= B, dim, L) floats.                                                          */
 int rsx_cross_bwd(const float* x0, const float* W, const float* Bc, const float* s, const float* dxL, const float* gz,
                   const float* wout, float* dX, int accumulate, float* dW, float* dB, float* dwout, float* workspace,
                   int B, int dim, int L, rsx_stream_t stream);

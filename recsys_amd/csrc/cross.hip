@@ -169,15 +169,30 @@ static inline int cross_epw(int B) {   // examples per wave
   return B <= 512 ? 1 : (B <= 2048 ? 2 : 4);   // ~4 us of dependent latency per example: parallelism first (measured)
 }
 
+static inline int cross_epw4_rule(int B) { return B <= 1024 ? 1 : (B <= 8192 ? 2 : 4); }   // (tower.hip's rider: p.xr_epw)
 static inline int cross_epw4(int B) {   // examples per wave of cross_bwd4_k (a workgroup takes 4x that)
   static const int forced = getenv("RSX_CROSS_EPW4") ? atoi(getenv("RSX_CROSS_EPW4")) : 0;   // tuning aid
   if (forced > 0) return forced;
-  return B <= 1024 ? 1 : (B <= 8192 ? 2 : 4);
+  return cross_epw4_rule(B);
 }
 
-extern "C" size_t rsx_cross_bwd_workspace_floats(int B, int dim, int L) {   // (the one-wave form's: never less than bwd4's)
-  const int epw = cross_epw(B);
-  return (size_t)((B + epw - 1) / epw) * (size_t)(2 * L + 1) * (size_t)dim;
+// The workspace of a caller that allocates ONCE for a capacity B and then runs any batch b <= B (ops.CrossLayers): the most
+// partials any such batch writes, in either backward form and in the tower's rider.  The count is not monotonic in b -- epw
+// steps up at 512 / 2048 (one wave) and 1024 / 8192 (bwd4) -- but within a range of constant epw it is, so the candidates are
+// the last batch of every range and B itself.
+extern "C" size_t rsx_cross_bwd_workspace_floats(int B, int dim, int L) {
+  if (B <= 0 || dim <= 0 || L <= 0) return 0;
+  const int edges[5] = {512, 1024, 2048, 8192, B};
+  int rt = 0;
+  for (int i = 0; i < 5; ++i) {
+    const int b = edges[i] < B ? edges[i] : B;
+    const int e1 = cross_epw(b), e4 = 4 * cross_epw4(b), ex = 4 * cross_epw4_rule(b);
+    const int r1 = (b + e1 - 1) / e1, r4 = (b + e4 - 1) / e4, rx = (b + ex - 1) / ex;
+    rt = r1 > rt ? r1 : rt;
+    rt = r4 > rt ? r4 : rt;
+    rt = rx > rt ? rx : rt;
+  }
+  return (size_t)rt * (size_t)(2 * L + 1) * (size_t)dim;
 }
 
 extern "C" int rsx_cross_bwd_defer(const float*, const float*, const float*, const float*, const float*, const float*, const float*,
@@ -208,10 +223,12 @@ extern "C" int rsx_cross_bwd_defer(const float* x0, const float* W, const float*
     const int epw = cross_epw4(B);
     RT = (B + 4 * epw - 1) / (4 * epw);
     auto launch = [&](auto kern) {
-      static bool attr_set = false;      // (> 64 KB of dynamic LDS per workgroup)
-      if (!attr_set) {
+      // (> 64 KB of dynamic LDS per workgroup.  Per L: the three instantiations have ONE function-pointer type, so this
+      // generic lambda is one function with one set of statics -- a single flag would cover the first L of the process only)
+      static bool attr_set[4] = {false, false, false, false};
+      if (!attr_set[L]) {
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024);
-        attr_set = true;
+        attr_set[L] = true;
       }
       RSX_LAUNCH(kern, dim3(RT), dim3(256), lds4, rsx_s(stream), p, epw);
     };
@@ -229,11 +246,12 @@ extern "C" int rsx_cross_bwd_defer(const float* x0, const float* W, const float*
   }
   RSX_CHECK_LAUNCH();
   const int n = (2 * L + 1) * dim;
+  float* dwo = gz != nullptr ? dwout : nullptr;   // without gz there is no d wout: a buffer handed in anyway is left alone
   if (reduce_out != nullptr) {
-    *reduce_out = rsx_cross_reduce_job{workspace, dW, dB, dwout, RT, n, L, dim};
+    *reduce_out = rsx_cross_reduce_job{workspace, dW, dB, dwo, RT, n, L, dim};
     return RSX_OK;
   }
-  RSX_LAUNCH(cross_reduce_k, dim3((n + 15) / 16), dim3(256), 0, rsx_s(stream), workspace, RT, n, dW, dB, dwout,
+  RSX_LAUNCH(cross_reduce_k, dim3((n + 15) / 16), dim3(256), 0, rsx_s(stream), workspace, RT, n, dW, dB, dwo,
                      L, dim);
   RSX_CHECK_LAUNCH();
   return RSX_OK;

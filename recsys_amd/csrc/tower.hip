@@ -2290,11 +2290,14 @@ extern "C" int rsx_tower_bwd_layer_defer(const float* in, const float* W, const 
       if (wide || rid || lds > 80 * 1024) return RSX_EUNSUPPORTED;
       const dim3 gx(p.n_din + p.n_dw + p.n_head + p.n_xr);
       auto launch = [&](auto kern) -> int {
-        static bool attr_set = false;                             // (> 64 KB of dynamic LDS per workgroup)
-        if (!attr_set) {
+        // (> 64 KB of dynamic LDS per workgroup.  Per kernel: both instantiations have ONE function-pointer type, so this generic
+        // lambda is one function with one set of statics -- a single flag would cover the first of the two in the process only)
+        static bool attr_set[2] = {false, false};
+        const int which = N <= 64 ? 0 : 1;
+        if (!attr_set[which]) {
           if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024) != hipSuccess)
             return RSX_EUNSUPPORTED;
-          attr_set = true;
+          attr_set[which] = true;
         }
         RSX_LAUNCH(kern, gx, dim3(256), lds, rsx_s(stream), p);
         return RSX_OK;

@@ -1130,8 +1130,8 @@ class CrossLayers:
         self.dim, self.L, self.cap = int(dim), int(L), int(capacity)
         self.s = torch.empty(self.cap, self.L, device=dev)
         self.cz = torch.empty(self.cap, device=dev)
-        n = lib().rsx_cross_bwd_workspace_floats(self.cap, self.dim, self.L)
-        self.ws = torch.empty(max(n, lib().rsx_cross_bwd_workspace_floats(1024, self.dim, self.L)), device=dev)
+        # (sized for every batch up to the capacity, in either backward form: include/rsx.h)
+        self.ws = torch.empty(int(lib().rsx_cross_bwd_workspace_floats(self.cap, self.dim, self.L)), device=dev)
 
     def forward(self, x0, W, Bc, wout=None, want_xL=False):
         B = x0.shape[0]

@@ -29,7 +29,10 @@ HASH_SEED = 0xD1AD    # the `seed` argument of train_step in every test
 #   deepfm  s0 + bias c0, s1, out.W [3], out.b, both relus      (deepfm.py)
 #   dcn     the sum head: wd = the first n_last entries of a longer out.W, bd = out.b, s0 only, no relus   (dcn.py)
 #   nos0    out.W [3] / out.b with s1 and relu2 but WITHOUT s0 (and so without c0)
-Case = namedtuple("Case", "id B k0 widths rate head replicas base_seed")
+#   (tail: the dcn form's out.W has this many entries behind the tower's n_last -- dcn.py: the cross output's weights.  The cases
+#   here carry DCN_TAIL = 5 untouched ones; tests/test_gpu_cross_forms.py's rider cases carry the cross layers' dim.)
+DCN_TAIL = 5
+Case = namedtuple("Case", "id B k0 widths rate head replicas base_seed tail", defaults=(DCN_TAIL,))
 
 # The kernel every layer takes, derived from the conditions in rsx_tower_fwd_layer / rsx_tower_head /
 # rsx_tower_bwd_layer_defer (csrc/tower.hip), default knobs.  Abbreviations:
@@ -89,7 +92,6 @@ CASES = [
 CASE = {c.id: c for c in CASES}
 HASH_CASES = ("tiny17", "default", "splitA", "splitB", "b4k")      # masks=None against the host hash, bit for bit
 INFER_CASES = ("default", "fix", "splitA", "b4k")
-DCN_TAIL = 5          # the dcn form's out.W has this many entries behind the tower's n_last (dcn.py: the cross output)
 
 
 def param_shapes(case):
@@ -100,7 +102,7 @@ def param_shapes(case):
         shapes[f"dnn.gamma{i}"], shapes[f"dnn.beta{i}"] = (n,), (n,)
         d = n
     if case.head == "dcn":
-        shapes["out.W"], shapes["out.b"] = (d + DCN_TAIL, 1), (1,)
+        shapes["out.W"], shapes["out.b"] = (d + case.tail, 1), (1,)
     else:
         shapes["dnn.Wout"], shapes["dnn.bout"] = (d, 1), (1,)
         shapes["out.W"], shapes["out.b"] = (3,), (1,)
