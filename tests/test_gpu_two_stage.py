@@ -1,5 +1,5 @@
 """Two-stage DIN recommendation on the GPU: rsx_rows_dot, rsx_topk_rows_counted and rsx_din_retrieve_candidates against their
-numpy definitions in recsys_amd/serving.py -- bit for bit (uint32 views of the floats, equality of the integers) -- and
+numpy definitions in recsys_amd/serving_din.py -- bit for bit (uint32 views of the floats, equality of the integers) -- and
 `Predictor.build_neighbours` / `similar_items` / `retrieve_candidates` / `recommend_two_stage` against `item_neighbours_host`
 and `recommend_two_stage_host` over the probabilities `rank_candidates` gives for the whole catalogue.
 Embeddings are drawn from a normal distribution and some rows zeroed: every non-zero component of a unit row is far above
