@@ -12,6 +12,7 @@ Differences that are deliberate (MI355X-first):
     which removes the Python/launch overhead that dominates at batch 256.
   * MirroredStrategy (fm/fm.py:184-194) becomes one process per GPU + RCCL (recsys_amd.dist).
 """
+import collections
 import os
 import queue
 import threading
@@ -167,15 +168,17 @@ class PackedBatch:
     def key(self):
         return tuple((k, str(dt), sh) for k, dt, sh, _, _ in self.layout)
 
-    def to(self, device):
+    def over(self, flat):
+        """This batch's packing over another buffer."""
         o = PackedBatch.__new__(PackedBatch)
-        o.layout, o.nbytes, o.flat = self.layout, self.nbytes, self.flat.to(device, non_blocking=True)
+        o.layout, o.nbytes, o.flat = self.layout, self.nbytes, flat
         return o
 
+    def to(self, device):
+        return self.over(self.flat.to(device, non_blocking=True))
+
     def clone(self):
-        o = PackedBatch.__new__(PackedBatch)
-        o.layout, o.nbytes, o.flat = self.layout, self.nbytes, self.flat.clone()
-        return o
+        return self.over(self.flat.clone())
 
     def views(self):
         feats, labels = {}, None
@@ -247,6 +250,8 @@ class VariableStore:
         # (k, position, [features of the k batches]) while the Estimator runs a step that belongs to one.
         self.window_k = 1
         self.window = None
+        self.window_dp = False       # set by model code whose fused step supports optimizer windows under data parallelism
+        self.window_broken = False   # an exception interrupted a window (Estimator._train_window): the variables are poisoned
 
     def window_of_step(self):
         """-> (k, position, features of the window's batches) of the TRAIN step being built; (1, 0, None) without a window."""
@@ -349,6 +354,155 @@ def get_variable_store() -> VariableStore:
     return _CURRENT_STORE[-1]
 
 
+# -- the records of Estimator._graphs (key[0] names the kind) ---------------------------------------------------------------
+class StepGraph:
+    """One step over static inputs ("packed", "infer" and the dict-input keys): `warm` eager runs, then the batch is cloned into
+    static inputs and captured, afterwards every batch is loaded into them and the graph replayed.  load(static, *batch);
+    eager(*batch) -> the step's result; capture(*batch) -> (static inputs holding the batch, replayable, static outputs)."""
+    __slots__ = ("warm", "static", "graph", "out", "_load", "_eager", "_capture")
+
+    def __init__(self, warm, load, eager, capture):
+        self.warm, self.static, self.graph, self.out = warm, None, None, None     # warm: eager runs still to do
+        self._load, self._eager, self._capture = load, eager, capture
+
+    def run(self, *batch):
+        if self.graph is not None:
+            self._load(self.static, *batch)
+            self.graph.replay()
+            return self.out
+        if self.warm > 0:                 # eager (lazy initialisation, allocator warm-up)
+            self.warm -= 1
+            return self._eager(*batch)
+        self.static, self.graph, self.out = self._capture(*batch)
+        self.graph.replay()               # capture executes nothing: the static inputs already hold this batch, so replay once
+        return self.out
+
+
+class StagingRing:
+    """Pinned staging buffers of one size that take turns (Estimator._h2d), each with the event of the copy that last read it."""
+    __slots__ = ("bufs", "np", "evs", "used", "i")
+
+    def __init__(self, nbytes, R):
+        self.bufs = [torch.empty(nbytes, dtype=torch.uint8).pin_memory() for _ in range(R)]
+        self.np = [b.numpy() for b in self.bufs]
+        self.evs = [torch.cuda.Event() for _ in range(R)]
+        self.used, self.i = [False] * R, 0
+
+    def copy(self, dst, src):
+        i = self.i
+        self.i = (i + 1) % len(self.bufs)
+        if self.used[i]:
+            self.evs[i].synchronize()          # the copy that last read this staging buffer has run (long ago)
+        np.copyto(self.np[i], src.numpy())     # (a plain memcpy: torch's CPU copy_ of > 32 KB wakes its thread pool, ~0.4 ms)
+        dst.copy_(self.bufs[i], non_blocking=True)
+        self.evs[i].record()
+        self.used[i] = True
+
+
+class StagedWindow:
+    """One captured instance of a streaming window (Estimator._train_window_packed): its static inputs (slices of ONE device
+    allocation), for host batches the pinned staging buffer the graph's first node fetches them from, the graph and the static
+    loss of every step.  `free` / `done`: the launch that last used the instance has been issued / has run on the GPU."""
+    __slots__ = ("all", "stride", "static", "pin", "pin_np", "graph", "losses", "done", "free")
+
+    def __init__(self, dev, host):
+        self.stride = stride = (dev[0].nbytes + 255) & ~255
+        self.done, self.free = torch.cuda.Event(), threading.Event()
+        self.free.set()
+        self.all = torch.empty(len(dev) * stride, dtype=torch.uint8, device=dev[0].flat.device)
+        self.static = []
+        for i, pb in enumerate(dev):
+            self.static.append(pb.over(self.all[i * stride:i * stride + pb.nbytes]))
+            self.static[i].flat.copy_(pb.flat)
+        self.pin = self.pin_np = self.graph = self.losses = None
+        if host:
+            self.pin = torch.empty(len(dev) * stride, dtype=torch.uint8).pin_memory()
+            self.pin_np = self.pin.numpy()
+            self.pin.copy_(self.all)    # (the staging buffer starts as this window's batches: the graph's first node reads it)
+            torch.cuda.synchronize()
+
+    def fetch(self):
+        """The captured window's first node: staging buffer -> static inputs.  The kernel reads the pinned buffer through the
+        device's mapping of host memory, right after plain host stores: that needs coherent (fine-grained) pinned allocations,
+        torch's default.  RSX_WINDOW_STAGE=memcpy (automatic under HIP_HOST_COHERENT=0) makes the node a hipMemcpyAsync
+        instead (0.0696 vs 0.0680 ms per DeepFM step)."""
+        if _lib.form("window_stage") == "memcpy" or os.environ.get("HIP_HOST_COHERENT", "1") == "0":
+            self.all.copy_(self.pin, non_blocking=True)
+        else:
+            _lib.check(_lib.lib().rsx_copy_bytes(self.all.data_ptr(), self.pin.data_ptr(), self.all.numel(),
+                                                 torch.cuda.current_stream().cuda_stream), "rsx_copy_bytes")
+
+    def stage(self, pbs):
+        """Host half of a window (the training thread): the staging buffer <- the window's batches."""
+        self.free.wait()                   # the launch that last used this instance has been issued (and `done` recorded)
+        self.free.clear()
+        self.done.synchronize()            # ... and the GPU has finished it (two windows ago): its first node read the buffer
+        stride, pin = self.stride, self.pin_np
+        for i, pb in enumerate(pbs):       # (plain memcpys: torch's CPU copy_ of > 32 KB wakes its thread pool, ~0.4 ms)
+            np.copyto(pin[i * stride:i * stride + pb.nbytes], pb.flat.numpy())
+
+    def launch(self):
+        """Device half of a window (the launch thread, or in line): ONE graph replay -- staged batches in, all steps -> loss of
+        the last step."""
+        self.graph.replay()
+        self.done.record()
+        self.free.set()
+        return self.losses[-1]
+
+
+class WindowSets:
+    """The "packedwin" entry of one window signature: `warm` eager windows still to run, then the StagedWindow instances that
+    take turns (sets[0] is the next one; the deque is rotated when it is taken)."""
+    __slots__ = ("warm", "sets")
+
+    def __init__(self):
+        self.warm, self.sets = 1, collections.deque()
+
+
+class ResidentPlan:
+    """The graphs of train_resident over ONE list of resident batches, which they read in place: the plan keeps the batches
+    alive, and a list that differs in any batch has a plan of its own.  `graphs`: (first, count) -> (graph, static loss of its
+    last step), the groups, heads and tails of resident_schedule.  Data parallel with eager collectives ("resident-dp"):
+    `steps` = one (segmented step, loss) per batch, `graphs`: first -> (segmented window of K steps, losses)."""
+    __slots__ = ("batches", "spg", "warm", "loss", "graphs", "steps", "K")
+
+    def __init__(self, batches, spg):
+        self.batches, self.spg, self.graphs, self.steps, self.K = tuple(batches), spg, {}, None, 0
+        self.warm, self.loss = 2, None         # eager warm-up steps still to run; the loss of the last step run
+
+
+def resident_schedule(start, steps, n, spg):
+    """`steps` steps over n resident batches in order, from batch start % n, in graphs of spg steps -> [(first, count, kind)]:
+    a "head" up to the next group boundary (first call: the two eager warm-up steps leave the stream at batch 2), the full
+    "group"s, then ONE "tail" holding the remaining (< spg) steps."""
+    sched, pos, left = [], start % n, steps
+    if pos % spg and left > 0:
+        cnt = min(spg - pos % spg, left)
+        sched.append((pos, cnt, "head"))
+        pos, left = (pos + cnt) % n, left - cnt
+    while left >= spg:
+        if spg < left < spg + spg // 2 and pos + left <= n:
+            # a full group + a short tail (20 steps at 16 per graph): ONE graph for both -- a graph launch costs ~9 us of
+            # start-up and ~8 us at its end on this stack
+            sched.append((pos, left, "tail"))
+            return sched
+        sched.append((pos, spg, "group"))
+        pos, left = (pos + spg) % n, left - spg
+    if left:
+        sched.append((pos, left, "tail"))
+    return sched
+
+
+def window_lengths(count, K):
+    """The optimizer windows (<= K steps each) of a graph of `count` steps, as EVEN as possible, longest first (20 steps: 7 + 7
+    + 6 rather than 8 + 8 + 4: a window's ONE sweep costs 57 us + ~3 us per step, so short windows are the dear ones)."""
+    out = []
+    for nwin in range(-(-count // K), 0, -1):
+        out.append(-(-count // nwin))
+        count -= out[-1]
+    return out
+
+
 class Estimator:
     MAX_INFER_GRAPHS = 32      # EVAL / PREDICT input signatures that get a captured graph (and an entry in _graphs) at most
 
@@ -421,13 +575,13 @@ class Estimator:
         return losses
 
     def _check_consistent(self, what):
-        if getattr(self.store, "window_broken", False):
+        if self.store.window_broken:
             raise _lib.RsxError("Estimator.%s: an optimizer window was interrupted by an exception; the variables are between two "
                            "window boundaries (untouched rows ahead of the touched ones).  Restore from a checkpoint." % what)
 
     def _window_len(self):
         """Steps per optimizer window: what the model supports (store.window_k), RSX_ADAM_WINDOW overrides (1 = off)."""
-        if not self.store.built or (self.store.dp is not None and not getattr(self.store, "window_dp", False)):
+        if not self.store.built or (self.store.dp is not None and not self.store.window_dp):
             return 1
         k = int(os.environ.get("RSX_ADAM_WINDOW", self.params.get("adam_window", self.store.window_k)))
         return max(1, min(k, self.store.window_k))
@@ -443,11 +597,11 @@ class Estimator:
             return False
         return self.store.dp is None or self.store.graph_safe_dp or self._dp_capture()
 
-    def _capture(self, fn):
+    def _capture(self, fn, segment=True):
         """-> (replayable, fn's result).  Data-parallel steps become graph segments with eager RCCL calls between
-        them (dist.SegmentedGraph); single-process steps one HIP graph."""
+        them (dist.SegmentedGraph); single-process steps one HIP graph, and so does an fn without collectives (segment=False)."""
         torch.cuda.synchronize()
-        if self.store.dp is not None and not self._dp_capture():
+        if segment and self.store.dp is not None and not self._dp_capture():
             from .dist import SegmentedGraph
             seg = SegmentedGraph()
             return seg, seg.capture(fn)
@@ -484,23 +638,20 @@ class Estimator:
         key = self._shape_key(features, labels)
         g = self._graphs.get(key)
         if g is None:
-            g = {"warm": 0}
-            self._graphs[key] = g
-        if "graph" not in g:
-            if g["warm"] < 2:
-                g["warm"] += 1
-                return self._train_eager(features, labels)
-            g["feat"] = {k: v.clone() for k, v in features.items()}
-            g["lab"] = labels.clone()
-            graph, g["loss"] = self._capture_step(g["feat"], g["lab"])
-            g["graph"] = graph      # capture executes nothing: the static buffers already hold this
-            graph.replay()          # batch (cloned above), so replay once to apply its step
-            return g["loss"]
-        for k, v in features.items():
-            g["feat"][k].copy_(v, non_blocking=True)
-        g["lab"].copy_(labels, non_blocking=True)
-        g["graph"].replay()
-        return g["loss"]
+            def load(static, features, labels):          # one copy per tensor
+                for k, v in features.items():
+                    static[0][k].copy_(v, non_blocking=True)
+                static[1].copy_(labels, non_blocking=True)
+
+            def capture(features, labels):
+                static = {k: v.clone() for k, v in features.items()}, labels.clone()
+                return (static,) + self._capture_step(*static)
+
+            g = self._graphs[key] = StepGraph(2, load, self._train_eager, capture)
+        return g.run(features, labels)
+
+    def _on_device(self, pb):
+        return pb if pb.flat.device == self.store.device else pb.to(self.store.device)
 
     def _h2d(self, static, pb):
         """One batch -> the graph's static input buffer, ONE copy.  A pageable host batch (what an input pipeline hands over)
@@ -511,43 +662,30 @@ class Estimator:
         if src.device.type == "cpu" and not src.is_pinned() and torch.cuda.is_available():
             ring = self._ring.get(pb.nbytes)
             if ring is None:
-                R = 4 * max(2, self.store.window_k)
-                bufs = [torch.empty(pb.nbytes, dtype=torch.uint8).pin_memory() for _ in range(R)]
-                ring = {"bufs": bufs, "np": [b.numpy() for b in bufs], "evs": [torch.cuda.Event() for _ in range(R)],
-                        "used": [False] * R, "i": 0}
-                self._ring[pb.nbytes] = ring
-            i = ring["i"]
-            ring["i"] = (i + 1) % len(ring["bufs"])
-            if ring["used"][i]:
-                ring["evs"][i].synchronize()         # the copy that last read this staging buffer has run (long ago)
-            np.copyto(ring["np"][i], src.numpy())    # (a plain memcpy: torch's CPU copy_ of > 32 KB wakes its thread pool, ~0.4 ms)
-            static.flat.copy_(ring["bufs"][i], non_blocking=True)
-            ring["evs"][i].record()
-            ring["used"][i] = True
+                ring = self._ring[pb.nbytes] = StagingRing(pb.nbytes, 4 * max(2, self.store.window_k))
+            ring.copy(static.flat, src)
             return
         static.flat.copy_(src, non_blocking=True)
 
     def _train_step_packed(self, pb):
-        key = ("packed",) + pb.key()
-        g = self._graphs.setdefault(key, {"warm": 0}) if self._use_graph() else None
-        if g is not None and "graph" in g:
-            # ONE copy per step, host or device -> the graph's static input buffer
-            self._h2d(g["static"], pb)
-            g["graph"].replay()
-            return g["loss"]
-        if pb.flat.device != self.store.device:
-            pb = pb.to(self.store.device)
-        if g is None:
+        if not self._use_graph():
+            if pb.flat.device != self.store.device:      # (in line: this is the eager step's timed path)
+                pb = pb.to(self.store.device)
             return self._train_eager(*pb.views())
-        if "graph" not in g:
-            if g["warm"] < 2:
-                g["warm"] += 1
-                return self._train_eager(*pb.views())
-            g["static"] = pb.clone()
-            graph, g["loss"] = self._capture_step(*g["static"].views())
-            g["graph"] = graph
-            graph.replay()
-            return g["loss"]
+        key = ("packed",) + pb.key()
+        g = self._graphs.get(key)
+        if g is None:
+            g = self._graphs[key] = self._packed_step(2, self._train_eager, self._capture_step)
+        return g.run(pb)
+
+    def _packed_step(self, warm, eager, capture):
+        """A StepGraph over ONE packed static buffer, loaded by ONE copy per batch, host or device (_h2d).  eager(features, labels)
+        runs a batch as it is; capture(features, labels) -> (replayable, static outputs) over the views of the static buffer."""
+        def clone_and_capture(pb):
+            static = self._on_device(pb).clone()
+            return (static,) + capture(*static.views())
+
+        return StepGraph(warm, self._h2d, lambda pb: eager(*self._on_device(pb).views()), clone_and_capture)
 
     def train_resident(self, batches, steps, steps_per_graph=8):
         """Train `steps` steps over a list of HBM-resident PackedBatch objects (cycled in order).  Groups of
@@ -558,127 +696,100 @@ class Estimator:
         if self._use_graph() and self.store.dp is not None and not self._dp_capture():
             # data-parallel with eager collectives: one segmented step per RESIDENT batch, reading its buffer in place
             # (no per-step input copy); steps cannot be grouped because the collectives sit between the segments
-            key = ("resident-dp", id(batches[0]), n)
+            key = ("resident-dp",) + tuple(map(id, batches))
             g = self._graphs.get(key)
             done = 0
             if g is None:
                 for s in range(min(2, steps)):
                     self._train_eager(*batches[s % n].views())
                 done = min(2, steps)
-                g = {"steps": [self._capture_step(*b.views()) for b in batches], "wins": {}}
+                g = ResidentPlan(batches, 0)
+                g.steps = [self._capture_step(*b.views()) for b in batches]
                 # optimizer windows (model code that supports them under data parallelism sets store.window_dp): K consecutive
                 # resident batches as ONE segmented capture -- the ids of all K batches are all-gathered at its start
                 K = self._window_len()
                 if K > 1 and n % K == 0:
                     for i in range(0, n, K):
-                        g["wins"][i] = self._capture(
+                        g.graphs[i] = self._capture(
                             lambda i=i: self._train_window([batches[i + j].views() for j in range(K)]))
-                    g["K"] = K
+                    g.K = K
                 self._graphs[key] = g
             loss = None
             s = done
+            K = g.K
             while s < steps:
-                K = g.get("K", 0)
                 if K and (s % n) % K == 0 and steps - s >= K:
-                    seg, losses = g["wins"][s % n]
+                    seg, losses = g.graphs[s % n]
                     seg.replay()
                     loss = losses[-1]
                     s += K
                     continue
-                seg, loss = g["steps"][s % n]
+                seg, loss = g.steps[s % n]
                 # RSX_DP_PREFETCH=1: the next batch's ids all-gather is issued underneath this step (not after the last one:
                 # nothing would consume it before the buffers may be refilled).  Off by default: through RCCL at world 1 the
                 # async launch + stream hand-over costs 7 us more than it hides; whether real xGMI latency reverses that can
                 # only be measured on a multi-GPU node.
-                nxt = g["steps"][(s + 1) % n][0] if (s + 1 < steps and _lib.form("dp_prefetch") == "1") else None
+                nxt = g.steps[(s + 1) % n][0] if (s + 1 < steps and _lib.form("dp_prefetch") == "1") else None
                 seg.replay(nxt)
                 s += 1
-            return loss if loss is not None else g["steps"][0][1]
-        # (data parallel with captured collectives -- dist.dp_capture, the default over RCCL: they sit in the groups' graphs like any
-        # other launch)
-        dp_eager = self.store.dp is not None and not self._dp_capture()
-        if not self._use_graph() or n % steps_per_graph != 0 or steps_per_graph <= 1 or dp_eager:
+            return loss if loss is not None else g.steps[0][1]
+        g = self._resident_plan(batches, steps_per_graph)
+        if g is None:
             for s in range(steps):
                 loss = self._train_step(batches[s % n])
             return loss
-        key = ("resident", id(batches[0]), n, steps_per_graph)
+        done = 0
+        while g.warm > 0 and done < steps:                     # eager warm-up (allocator, lazy init), first call only
+            g.loss = self._train_eager(*batches[done % n].views())
+            g.warm -= 1
+            done += 1
+        # Every graph is captured before anything is replayed, and a caller that times this function calls prepare_resident()
+        # first, so no capture ever falls inside a timed region.
+        for graph, loss in self._resident_schedule(g, done, steps - done):
+            graph.replay()
+            g.loss = loss
+        return g.loss
+
+    def _resident_plan(self, batches, spg):
+        """-> the ResidentPlan of exactly these batches in this order, None where train_resident runs them step by step.  (The
+        key holds every batch's id and the plan every batch, so equal ids are the same live objects.)
+        Data parallel with captured collectives (dist.dp_capture, the default over RCCL) plans like a single process: they sit
+        in the groups' graphs like any other launch."""
+        dp_eager = self.store.dp is not None and not self._dp_capture()
+        if not self._use_graph() or spg <= 1 or len(batches) % spg != 0 or dp_eager:
+            return None
+        key = ("resident", spg) + tuple(map(id, batches))
         g = self._graphs.get(key)
         if g is None:
-            g = {"groups": {}, "tails": {}, "loss": None, "warm": 0}
-            self._graphs[key] = g
-        done = 0
-        while g["warm"] < 2 and done < steps:                  # eager warm-up (allocator, lazy init), first call only
-            g["loss"] = self._train_eager(*batches[done % n].views())
-            g["warm"] += 1
-            done += 1
-        # The schedule is a function of (start, count) only: a head graph up to the next group boundary (first call: the
-        # two eager warm-up steps leave the stream at batch 2), full groups, then ONE tail graph holding the remaining
-        # (< steps_per_graph) steps -- batches are consumed strictly in order.  Every graph is captured before anything is
-        # replayed, and a caller that times this function calls prepare_resident() first, so no capture ever falls
-        # inside a timed region.
-        for graph, loss in self._resident_schedule(g, batches, done, steps - done, steps_per_graph):
-            graph.replay()
-            g["loss"] = loss
-        return g["loss"]
+            g = self._graphs[key] = ResidentPlan(batches, spg)
+        return g
 
-    def _resident_schedule(self, g, batches, start, steps, spg):
-        n = len(batches)
+    def _resident_schedule(self, g, start, steps):
+        """-> the (graph, static loss of its last step) of every entry of resident_schedule, captured where the plan does not
+        hold it yet.  Optimizer windows never cross a graph: the resident batches ARE the look-ahead."""
+        def steps_of(first, count):
+            for w in window_lengths(count, self._window_len()):
+                loss = self._train_window([g.batches[first + j].views() for j in range(w)])[-1]
+                first += w
+            return loss
 
-        def capture(first, count):
-            torch.cuda.synchronize()
-            graph = torch.cuda.CUDAGraph()
-            K = self._window_len()
-            # (data parallel with captured collectives: see _capture -- a communicator thread may poll events meanwhile)
-            kw = {"capture_error_mode": "thread_local"} if self.store.dp is not None else {}
-            with _lib.capture_gc_guard(), torch.cuda.graph(graph, **kw):
-                k = 0
-                nwin = -(-count // K)    # windows of the graph, as EVEN as possible (20 steps: 7 + 7 + 6 rather than 8 + 8 + 4:
-                while k < count:         # a window's ONE sweep costs 57 us + ~3 us per step, so short windows are the dear ones)
-                    w = -(-(count - k) // nwin)      # optimizer windows never cross a graph: the resident batches ARE the look-ahead
-                    loss = self._train_window([batches[first + k + j].views() for j in range(w)])[-1]
-                    k += w
-                    nwin -= 1
-            return graph, loss        # `loss`: the static output of the graph's last step
-
-        def partial(first, count):
-            if (first, count) not in g["tails"]:
-                g["tails"][(first, count)] = capture(first, count)
-            return g["tails"][(first, count)]
-
-        sched, pos, left = [], start % n, steps
-        if pos % spg and left > 0:
-            cnt = min(spg - pos % spg, left)
-            sched.append(partial(pos, cnt))
-            pos, left = (pos + cnt) % n, left - cnt
-        while left >= spg:
-            if spg < left < spg + spg // 2 and pos + left <= n:
-                # a full group + a short tail (20 steps at 16 per graph): ONE graph for both -- a graph launch costs ~9 us of
-                # start-up and ~8 us at its end on this stack
-                sched.append(partial(pos, left))
-                pos, left = (pos + left) % n, 0
-                break
-            gi = pos // spg
-            if gi not in g["groups"]:
-                g["groups"][gi] = capture(pos, spg)
-            sched.append(g["groups"][gi])
-            pos, left = (pos + spg) % n, left - spg
-        if left:
-            sched.append(partial(pos, left))
+        sched = []
+        for first, count, _ in resident_schedule(start, steps, len(g.batches), g.spg):
+            if (first, count) not in g.graphs:
+                g.graphs[(first, count)] = self._capture(lambda: steps_of(first, count))
+            sched.append(g.graphs[(first, count)])
         return sched
 
     def prepare_resident(self, batches, steps, steps_per_graph=8):
         """Capture every HIP graph train_resident(batches, steps, steps_per_graph) will replay, so that a timed region
         afterwards is pure replay.  Capturing itself executes nothing -- but when the resident graphs are still cold this runs
         the TWO eager warm-up training steps first (lazy initialisation, allocator warm-up): real optimizer steps."""
-        n = len(batches)
-        dp_eager = self.store.dp is not None and not self._dp_capture()
-        if not self._use_graph() or n % steps_per_graph != 0 or steps_per_graph <= 1 or dp_eager:
+        g = self._resident_plan(batches, steps_per_graph)
+        if g is None:
             return
-        g = self._graphs.get(("resident", id(batches[0]), n, steps_per_graph))
-        if g is None or g["warm"] < 2:
+        if g.warm > 0:
             self.train_resident(batches, 2, steps_per_graph)       # the two eager warm-up steps
-            g = self._graphs[("resident", id(batches[0]), n, steps_per_graph)]
-        self._resident_schedule(g, batches, 0, steps, steps_per_graph)
+        self._resident_schedule(g, 0, steps)
 
     def _maybe_restore(self):
         if self._restored or not self.model_dir or not self.store.built:
@@ -704,82 +815,42 @@ class Estimator:
         launcher (Estimator.train, opt-in): the replay is handed to the launch thread; -> None (the loss is the launch's)."""
         host = all(pb.flat.device.type == "cpu" for pb in pbs)
         key = ("packedwin", len(pbs), host) + pbs[0].key()
-        g = self._graphs.setdefault(key, {"warm": 0, "sets": [], "turn": 0})
-        if len(g["sets"]) == self._window_sets:
+        g = self._graphs.get(key)
+        if g is None:
+            g = self._graphs[key] = WindowSets()
+        if len(g.sets) == self._window_sets:
+            st = g.sets[0]
+            g.sets.rotate(-1)
             if host:
-                st = self._stage_window(g, pbs)
+                st.stage(pbs)
                 if launcher is not None:
-                    launcher.submit(lambda: self._launch_staged(st))
+                    launcher.submit(st.launch)
                     return None
-                return self._launch_staged(st)
+                return st.launch()
             if launcher is not None:
                 launcher.drain()
-            st = g["sets"][g["turn"]]
-            g["turn"] = (g["turn"] + 1) % len(g["sets"])
-            for sb, pb in zip(st["static"], pbs):          # device-resident batches: one D2D copy each, in stream order
+            for sb, pb in zip(st.static, pbs):             # device-resident batches: one D2D copy each, in stream order
                 self._h2d(sb, pb)
-            st["graph"].replay()
-            return st["losses"][-1]
+            st.graph.replay()
+            return st.losses[-1]
         if launcher is not None:
             launcher.drain()
-        dev = [pb if pb.flat.device == self.store.device else pb.to(self.store.device) for pb in pbs]
-        if g["warm"] < 1:
-            g["warm"] += 1
+        dev =[self._on_device(pb) for pb in pbs]
+        if g.warm > 0:
+            g.warm -= 1
             return self._train_window([pb.views() for pb in dev])[-1]
-        stride = (dev[0].nbytes + 255) & ~255
-        st = {"done": torch.cuda.Event(), "stride": stride, "free": threading.Event(),
-              "all": torch.empty(len(dev) * stride, dtype=torch.uint8, device=self.store.device)}
-        st["free"].set()
-        st["static"] = []
-        for i, pb in enumerate(dev):
-            sb = PackedBatch.__new__(PackedBatch)
-            sb.layout, sb.nbytes, sb.flat = pb.layout, pb.nbytes, st["all"][i * stride:i * stride + pb.nbytes]
-            sb.flat.copy_(pb.flat)
-            st["static"].append(sb)
-        if host:
-            st["pin"] = torch.empty(len(dev) * stride, dtype=torch.uint8).pin_memory()
-            st["pin_np"] = st["pin"].numpy()
-            st["pin"].copy_(st["all"])  # (the staging buffer starts as this window's batches: the graph's first node reads it)
-            torch.cuda.synchronize()
-
-        # The kernel node reads the pinned staging buffer through the device's mapping of host memory, right after plain host
-        # stores: that needs coherent (fine-grained) pinned allocations, torch's default.  RSX_WINDOW_STAGE=memcpy (automatic
-        # under HIP_HOST_COHERENT=0) makes the first node a hipMemcpyAsync instead (0.0696 vs 0.0680 ms per DeepFM step).
-        stage_memcpy = _lib.form("window_stage") == "memcpy" or os.environ.get("HIP_HOST_COHERENT", "1") == "0"
+        st = StagedWindow(dev, host)
 
         def window():
-            if host and stage_memcpy:
-                st["all"].copy_(st["pin"], non_blocking=True)
-            elif host:                  # first node: the staged batches, fetched from pinned host memory by a kernel
-                _lib.check(_lib.lib().rsx_copy_bytes(st["all"].data_ptr(), st["pin"].data_ptr(), st["all"].numel(),
-                                                     torch.cuda.current_stream().cuda_stream), "rsx_copy_bytes")
-            return self._train_window([sb.views() for sb in st["static"]])
+            if host:                    # first node: the staged batches, fetched from pinned host memory
+                st.fetch()
+            return self._train_window([sb.views() for sb in st.static])
 
-        st["graph"], st["losses"] = self._capture(window)
-        st["graph"].replay()            # capture executes nothing: the inputs already hold this window's batches
-        st["done"].record(torch.cuda.current_stream())
-        g["sets"].append(st)
-        return st["losses"][-1]
-
-    def _stage_window(self, g, pbs):
-        """Host half of a window (the training thread): the next instance's staging buffer <- the window's batches."""
-        st = g["sets"][g["turn"]]
-        g["turn"] = (g["turn"] + 1) % len(g["sets"])
-        st["free"].wait()                  # the launch that last used this instance has been issued (and `done` recorded)
-        st["free"].clear()
-        st["done"].synchronize()           # ... and the GPU has finished it (two windows ago): its first node read the buffer
-        stride, pin = st["stride"], st["pin_np"]
-        for i, pb in enumerate(pbs):       # (plain memcpys: torch's CPU copy_ of > 32 KB wakes its thread pool, ~0.4 ms)
-            np.copyto(pin[i * stride:i * stride + pb.nbytes], pb.flat.numpy())
-        return st
-
-    def _launch_staged(self, st):
-        """Device half of a window (the launch thread, or in line): ONE graph replay -- staged batches in, all steps -> loss of
-        the last step."""
-        st["graph"].replay()
-        st["done"].record()
-        st["free"].set()
-        return st["losses"][-1]
+        st.graph, st.losses = self._capture(window)
+        st.graph.replay()               # capture executes nothing: the inputs already hold this window's batches
+        st.done.record(torch.cuda.current_stream())
+        g.sets.append(st)
+        return st.losses[-1]
 
     def train(self, input_fn, steps=None, max_steps=None):
         self._check_consistent("train")       # (a poisoned store must be restored from a checkpoint, not trained on)
@@ -894,48 +965,27 @@ class Estimator:
         if not self.store.built:          # variables are created by the first model_fn call
             self._call_model_fn(self._to_device(features), self._to_device(labels) if has_lab else None, ModeKeys.PREDICT)
         self._maybe_restore()
+
+        def forward(f, l):                # the eager forward over device tensors -> (prob, loss, labels, features)
+            spec = self._call_model_fn(f, l if mode == ModeKeys.EVAL else None, mode)
+            return spec.predictions["prob"], spec.loss, (l if has_lab else None), f
+
         if not self._use_graph():
-            f, l = self._to_device(features), (self._to_device(labels) if has_lab else None)
-            self._infer_features = f
-            spec = self._call_model_fn(f, l if mode == ModeKeys.EVAL else None, mode)
-            return spec.predictions["prob"], spec.loss, l
-        pb = PackedBatch(features, labels if has_lab else np.zeros(0, np.float32))
-        key = ("infer", mode, has_lab) + pb.key()
-        g = self._graphs.get(key)
-        if g is None:
-            if self._n_infer_graphs >= self.MAX_INFER_GRAPHS:
-                # a serving loop with ever-new request sizes: stop capturing (and stop remembering signatures), stay eager
-                dev = pb if pb.flat.device == self.store.device else pb.to(self.store.device)
-                f, l = dev.views()
-                self._infer_features = f
-                spec = self._call_model_fn(f, l if mode == ModeKeys.EVAL else None, mode)
-                return spec.predictions["prob"], spec.loss, (l if has_lab else None)
-            g = self._graphs[key] = {"warm": 0}
-            self._n_infer_graphs += 1
-        if "graph" in g:
-            self._h2d(g["static"], pb)
-            g["graph"].replay()
-            self._infer_features = g["features"]
-            return g["prob"], g["loss"], g["labels"]
-        dev = pb if pb.flat.device == self.store.device else pb.to(self.store.device)
-        if g["warm"] < 1:                 # first batch of this signature: eager (lazy initialisation, allocator warm-up)
-            g["warm"] += 1
-            f, l = dev.views()
-            self._infer_features = f
-            spec = self._call_model_fn(f, l if mode == ModeKeys.EVAL else None, mode)
-            return spec.predictions["prob"], spec.loss, (l if has_lab else None)
-        g["static"] = dev.clone()
-        f, l = g["static"].views()
-        torch.cuda.synchronize()
-        graph = torch.cuda.CUDAGraph()
-        kw = {"capture_error_mode": "thread_local"} if self.store.dp is not None else {}
-        with _lib.capture_gc_guard(), torch.cuda.graph(graph, **kw):
-            spec = self._call_model_fn(f, l if mode == ModeKeys.EVAL else None, mode)
-        g["prob"], g["loss"], g["labels"] = spec.predictions["prob"], spec.loss, (l if has_lab else None)
-        g["features"] = self._infer_features = f
-        g["graph"] = graph
-        graph.replay()                    # capture executes nothing: the static buffers already hold this batch
-        return g["prob"], g["loss"], g["labels"]
+            out = forward(self._to_device(features), self._to_device(labels) if has_lab else None)
+        else:
+            pb = PackedBatch(features, labels if has_lab else np.zeros(0, np.float32))
+            key = ("infer", mode, has_lab) + pb.key()
+            g = self._graphs.get(key)
+            if g is None and self._n_infer_graphs < self.MAX_INFER_GRAPHS:
+                # the first batch of a signature runs eagerly, the second is captured (one graph also under data parallelism:
+                # the forward has no collectives)
+                g = self._graphs[key] = self._packed_step(
+                    1, forward, lambda f, l: self._capture(lambda: forward(f, l), segment=False))
+                self._n_infer_graphs += 1
+            # (no record: a serving loop with ever-new request sizes -- stop capturing and remembering signatures, stay eager)
+            out = g.run(pb) if g is not None else forward(*self._on_device(pb).views())
+        self._infer_features = out[3]
+        return out[:3]
 
     def evaluate(self, input_fn, steps=None):
         """Estimator.evaluate (fm/fm.py:216-221): AUC-200 / Accuracy / mean batch loss accumulated ON DEVICE by one

@@ -304,9 +304,9 @@ def capture_both(est, pred, ids):
             pb = pred.predict({"ids": ids})["prob"]
     err = float(np.abs(pa - pb).max())
     assert err <= 2e-5, (B, err)                 # (faster and different is not faster)
-    ga = [g for k, g in est._graphs.items() if k[0] == "infer" and "graph" in g and g["static"].views()[0]["ids"].shape[0] == B]
+    ga = [g for k, g in est._graphs.items() if k[0] == "infer" and g.graph is not None and g.static.views()[0]["ids"].shape[0] == B]
     assert len(ga) == 1 and "graph" in pred._graphs[B]
-    return ga[0]["graph"], pred._graphs[B]["graph"], err
+    return ga[0].graph, pred._graphs[B]["graph"], err
 
 
 def time_replays(graph, n):

@@ -107,10 +107,10 @@ def capture_both(pred, req):
         pa, pb = answer_a(pred, req), answer_b(pred, req)
     err = float(np.abs(pa - pb).max())
     assert err <= 2e-5, (C, err)                 # (faster and different is not faster)
-    ga = [g for k, g in pred._est._graphs.items() if k[0] == "infer" and "graph" in g
-          and g["static"].views()[0]["i_id"].shape[0] == C]
+    ga = [g for k, g in pred._est._graphs.items() if k[0] == "infer" and g.graph is not None
+          and g.static.views()[0]["i_id"].shape[0] == C]
     assert len(ga) == 1 and "graph" in pred._graphs[("rank", 1, C)]
-    return ga[0]["graph"], pred._graphs[("rank", 1, C)]["graph"], err
+    return ga[0].graph, pred._graphs[("rank", 1, C)]["graph"], err
 
 
 def host_select(prob, k):

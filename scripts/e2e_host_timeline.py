@@ -11,7 +11,7 @@ import torch
 
 from recsys_amd import deepfm, synthetic
 from recsys_amd import input_pipeline as ip
-from recsys_amd.estimator import Estimator, PackedBatch, RunConfig
+from recsys_amd.estimator import Estimator, PackedBatch, RunConfig, StagedWindow
 from recsys_amd.feature_columns import CriteoLayout, build_feature_columns
 
 lin, emb = build_feature_columns(16, "indicator_all")
@@ -51,7 +51,7 @@ with tempfile.TemporaryDirectory() as d:
 
     torch.cuda.Event.synchronize = timed_sync
     gpu_ev = []
-    orig_launch = est._launch_staged
+    orig_launch = StagedWindow.launch
 
     def timed_launch(st):
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -61,7 +61,7 @@ with tempfile.TemporaryDirectory() as d:
         gpu_ev.append((e0, e1))
         return r
 
-    est._launch_staged = timed_launch
+    StagedWindow.launch = timed_launch
     T = {"read": 0.0, "pack": 0.0, "window": 0.0}
     nwin = 300
     torch.cuda.synchronize()

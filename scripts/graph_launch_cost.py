@@ -25,8 +25,8 @@ for w in range(8):
     est._train_window_packed(pbs[w * K:(w + 1) * K])
 torch.cuda.synchronize()
 key = [k for k in est._graphs if k[0] == "packedwin"][0]
-sets = est._graphs[key]["sets"]
-g0, g1 = sets[0]["graph"], sets[1]["graph"]
+sets = est._graphs[key].sets
+g0, g1 = sets[0].graph, sets[1].graph
 for mode in ("idle", "busy"):
     ts = []
     for rep in range(20):

@@ -110,7 +110,7 @@ def test_loopback_dp_inside_optimizer_windows_matches_the_oracle(kind, world, B,
     from tests.parity_util import synth_ids
     layers, D = ((32, 16), 16) if kind != "fm" else ((), 16)
     est, P, row_off = _build(kind, world, B, layers, D, 0.0, exchange, monkeypatch)
-    assert est.store.window_k >= k and getattr(est.store, "window_dp", False)
+    assert est.store.window_k >= k and est.store.window_dp
     P64 = {n: v.astype(np.float64) for n, v in P.items()}
     om = _oracle_model(kind, P64, row_off, layers, 0.0)
     opt = nn.AdamTF1(dtype=np.float64)
