@@ -300,6 +300,15 @@ typedef struct {
    *                       the powers have been advanced since).                                                              */
   int32_t window_block_u;
   int32_t alphas_from_state;
+  /* rsx_adam_slice_run of a WINDOW sweep, TABLE_TF1_COLD rows of 4 .. 256 floats (a power of two; otherwise ignored): != 0
+   * selects the form that classifies the rows of a block before it updates any.  A row whose m is +0 throughout receives
+   * var - (+0) from every update, so only its v moves, by 1 + w products with beta2: such a row has its v stored alone
+   * (every v in [+0, +inf]), or nothing at all (v all +0: a row no gradient has reached), and var is never read.  The
+   * full updates run on the remaining rows only, compacted into full waves.  The shortcuts apply only while lr's step
+   * sizes, beta1, beta2 and eps are finite without a sign and beta2, eps > 0; otherwise every row takes the full updates.
+   * Stateless -- every launch classifies from the m and v it loads -- and bit-identical to 0, the one-pass form.  Riders
+   * ignore it.                                                                                                          */
+  int32_t window_compact;
 } rsx_adam_slice;
 int64_t rsx_adam_num_blocks(const rsx_adam_seg* segs_h, int nseg);
 int64_t rsx_adam_num_blocks_u(const rsx_adam_seg* segs_h, int nseg, int window_block_u);

@@ -50,6 +50,7 @@ FORMS = {
     "input_thread": ("0", "the input iterator on a thread of its own"),
     "launch_thread": ("0", "streaming windows issued by a thread of their own"),
     "adam_window_large": ("4", "steps per optimizer window above the small-batch threshold"),
+    "window_compact": ("1", "the window sweep classifies rows first and runs Adam only on rows with moments (0: one pass over all)"),
 }
 
 
@@ -80,7 +81,8 @@ class AdamSeg(C.Structure):
 class AdamSlice(C.Structure):
     _fields_ = [("segs", C.POINTER(AdamSeg)), ("nseg", C.c_int32), ("lr", C.c_float), ("beta1", C.c_float),
                 ("beta2", C.c_float), ("eps", C.c_float), ("state", C.c_void_p), ("blk_lo", C.c_uint32),
-                ("blk_hi", C.c_uint32), ("window_block_u", C.c_int32), ("alphas_from_state", C.c_int32)]
+                ("blk_hi", C.c_uint32), ("window_block_u", C.c_int32), ("alphas_from_state", C.c_int32),
+                ("window_compact", C.c_int32)]
 
 
 class ExampleBlocks(C.Structure):

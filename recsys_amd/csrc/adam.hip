@@ -63,15 +63,22 @@ __global__ __launch_bounds__(ADAM_T) void adam_slice_k(const AdamSlice s) { adam
 #ifndef RSX_ADAM_WIN_OCC
 #define RSX_ADAM_WIN_OCC 3      // waves per SIMD the window sweep is compiled for.  3 = 168 registers, no spills at NW = 7; 4 (128 registers, spills at NW = 7) measured equal up to 6-step windows and 3 us slower per 8-step sweep (76.6 vs 73.5 us; DeepFM step 0.0668 -> 0.0659 ms; scripts/ab_window_occ.sh, profiles/r03_q_ab_window_occ.txt)
 #endif
-template <int NW>
+// COMPACT: the form that classifies the rows first and runs the updates on the live ones only (adam_device.h)
+template <int NW, bool COMPACT>
 __global__ __launch_bounds__(ADAM_T, RSX_ADAM_WIN_OCC) void adam_window_k(const AdamSlice s) {
   // (the window's step sizes for the lazy window pass: state words 8.., adam_device.h)
   if (blockIdx.x == 0 && threadIdx.x == 0 && s.blk_lo == 0 && !s.args.alpha_src) adam_publish_step_sizes<NW>(s.args);
-  adam_window_block<NW>(s.args, s.blk_lo + blockIdx.x);
+  if constexpr (COMPACT) {
+    __shared__ uint32_t lds[WIN_LIST_WORDS];
+    adam_window_block<NW, ADAM_U, true>(s.args, s.blk_lo + blockIdx.x, threadIdx.x, lds);
+  } else {
+    adam_window_block<NW>(s.args, s.blk_lo + blockIdx.x);
+  }
 }
 template <int NW>
-static void launch_window(const AdamSlice& s, hipStream_t st) {
-  RSX_LAUNCH(adam_window_k<NW>, dim3(s.n_blk), dim3(ADAM_T), 0, st, s);
+static void launch_window(const AdamSlice& s, const bool compact, hipStream_t st) {
+  if (compact) RSX_LAUNCH((adam_window_k<NW, true>), dim3(s.n_blk), dim3(ADAM_T), 0, st, s);
+  else RSX_LAUNCH((adam_window_k<NW, false>), dim3(s.n_blk), dim3(ADAM_T), 0, st, s);
 }
 
 extern "C" int rsx_adam_slice_run(const rsx_adam_slice* slice_h, rsx_stream_t stream) {
@@ -80,16 +87,23 @@ extern "C" int rsx_adam_slice_run(const rsx_adam_slice* slice_h, rsx_stream_t st
   if (rc != RSX_OK) return rc;
   if (s.n_blk == 0) return RSX_OK;
   if (s.args.win_u != 0) return RSX_EUNSUPPORTED;      // small window blocks exist as riders only (rsx_tower_head)
+  // the compact form needs every table row inside one wave's consecutive lanes: 1 .. 64 float4, a power of two
+  bool compact = slice_h->window_compact != 0;
+  for (int k = 0; k < s.args.nseg; ++k) {
+    const int lpr = s.args.seg[k].d >> 2;
+    if (s.args.seg[k].kind == RSX_ADAM_TABLE_TF1_COLD && (lpr > 64 || (lpr & (lpr - 1)) != 0)) compact = false;
+  }
   const dim3 grid(s.n_blk), block(ADAM_T);
+  hipStream_t st = rsx_s(stream);
   switch (s.args.nw) {
-    case 0: RSX_LAUNCH(adam_slice_k, grid, block, 0, rsx_s(stream), s); break;
-    case 1: launch_window<1>(s, rsx_s(stream)); break;
-    case 2: launch_window<2>(s, rsx_s(stream)); break;
-    case 3: launch_window<3>(s, rsx_s(stream)); break;
-    case 4: launch_window<4>(s, rsx_s(stream)); break;
-    case 5: launch_window<5>(s, rsx_s(stream)); break;
-    case 6: launch_window<6>(s, rsx_s(stream)); break;
-    default: launch_window<7>(s, rsx_s(stream)); break;
+    case 0: RSX_LAUNCH(adam_slice_k, grid, block, 0, st, s); break;
+    case 1: launch_window<1>(s, compact, st); break;
+    case 2: launch_window<2>(s, compact, st); break;
+    case 3: launch_window<3>(s, compact, st); break;
+    case 4: launch_window<4>(s, compact, st); break;
+    case 5: launch_window<5>(s, compact, st); break;
+    case 6: launch_window<6>(s, compact, st); break;
+    default: launch_window<7>(s, compact, st); break;
   }
   RSX_CHECK_LAUNCH();
   return RSX_OK;

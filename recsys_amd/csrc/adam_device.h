@@ -440,12 +440,45 @@ __device__ __forceinline__ bool adam_win_guard4(const float4& var, const float4&
 //     window: from ~4 steps per window on the kernel is VALU-bound, not HBM-bound.)
 //   - blocks of the other kinds (the first-order vector, ...): adam_block.
 // U = float4 per lane of a block (== a.win_u, or ADAM_U when that is 0: the host picks the instantiation)
-template <int NW, int U = ADAM_U>
-__device__ __forceinline__ void adam_window_block(const AdamArgs& a, const uint32_t blk, const int tid = threadIdx.x) {
+//
+// COMPACT (rsx_adam_slice.window_compact; the stand-alone sweep only, rows of 4 .. 256 floats, a power of two): a row whose m
+// is +0 throughout receives var - (+0) from every update -- var keeps its bits, m stays +0, and v only takes its 1 + NW
+// products with b2 -- so the chain runs on the other rows only, and on FULL waves of them:
+//   phase 1  slot maps, m and v of the block (not var), the same pipeline.  The lanes of a row vote (ballots):
+//              void  m and v all 0x00000000:                                       nothing more is loaded, nothing is stored
+//              idle  m all 0x00000000, every v in [+0, +inf] (sign clear, no NaN): v = v * b2, 1 + NW times, stored; var and
+//                    m are neither loaded nor stored
+//              live  every other untouched row: its float4s' offsets go to a list in LDS (ballot + mbcnt, one counter bump per
+//                    wave and batch)
+//   phase 2  the list, densely: 64 * HB entries per wave and batch, var / m / v loaded by index (m and v again, from the
+//            cache), then finish() as it is -- guard, packed chain, IEEE redo.  At most one wave of the workgroup is partly
+//            filled; waves beyond the list's end do nothing.
+//   A wave whose first batch holds nothing but live rows (and skipped ones) classifies no further: it lists nothing and
+//   runs the one-pass pipeline over its lanes of the block instead (after phase 2), which is right for rows of any class.
+// The shortcuts hold under a launch-uniform gate on the hyper-parameters (win_shortcut_gate: otherwise every untouched row
+// is live and 0 / 0, 0 * inf give the NaNs of the IEEE form).  Each launch derives every row's class from what it loads.
+// (Not a bit of difference for any state arithmetic produces; a SIGNALLING NaN weight under an all-zero m keeps its payload
+// here where var - 0 would quiet it.)
+constexpr int WIN_LIST_WORDS = ADAM_T * ADAM_U + 1;     // the list of live float4s (offsets in the block) and its length
+// May the compact form take a row with m == +0 throughout as one whose var does not move?  m * b1 = +0, alpha_j * (+0) = +0,
+// v * b2 stays in [+0, +inf], sqrt + eps in (0, +inf], (+0) / that = +0, var - (+0) = var: finite hyper-parameters WITHOUT a
+// sign (a negative b1 or step size makes the numerator -0, and -0 - (-0) = +0), b2 and eps above zero (inf * 0, 0 / 0).
+template <int NW>
+__device__ __forceinline__ bool win_shortcut_gate(const AdamArgs& a, const float alpha0, const AlphaW& aw) {
+  auto plus_finite = [](const float x) { return __float_as_uint(x) < 0x7f800000u; };      // +0 .. FLT_MAX
+  bool ok = plus_finite(a.eps) && a.eps > 0.f && plus_finite(a.b1) && plus_finite(a.b2) && a.b2 > 0.f && plus_finite(alpha0);
+#pragma unroll
+  for (int j = 0; j < NW; ++j) ok = ok && plus_finite(aw.get(j));
+  return ok;
+}
+template <int NW, int U = ADAM_U, bool COMPACT = false>
+__device__ __forceinline__ void adam_window_block(const AdamArgs& a, const uint32_t blk, const int tid = threadIdx.x,
+                                                  uint32_t* const lds = nullptr /* COMPACT: WIN_LIST_WORDS words of LDS */) {
   constexpr int nw = NW;        // == a.nw (the host picks the instantiation)
   constexpr int HB = RSX_ADAM_WIN_HB;
   constexpr int NB = U / HB;
   static_assert(U % HB == 0 && U <= ADAM_U, "U");
+  static_assert(!COMPACT || (U == ADAM_U && ADAM_T % 64 == 0), "the compact form: full-size blocks of whole waves");
   int si = 0;
 #pragma unroll 1
   for (int k = 1; k < a.nseg; ++k)
@@ -490,7 +523,21 @@ __device__ __forceinline__ void adam_window_block(const AdamArgs& a, const uint3
     int t[HB];
     bool live[HB];
   };
-  auto issue = [&](const int b, Batch& B) {
+  auto load_state = [&](Batch& B, const bool with_var) {
+#pragma unroll
+    for (int u = 0; u < HB; ++u) {
+#if RSX_ADAM_NT
+      if (with_var) B.var[u] = __builtin_nontemporal_load(&var4[B.ec[u]]);
+      B.m[u] = __builtin_nontemporal_load(&m4[B.ec[u]]);
+      B.v[u] = __builtin_nontemporal_load(&v4[B.ec[u]]);
+#else
+      if (with_var) B.var[u] = var4[B.ec[u]];
+      B.m[u] = m4[B.ec[u]];
+      B.v[u] = v4[B.ec[u]];
+#endif
+    }
+  };
+  auto issue = [&](const int b, Batch& B, const bool with_var = true) {
 #pragma unroll
     for (int u = 0; u < HB; ++u) {
       const long long e = base + (long long)(b * HB + u) * ADAM_T + tid;
@@ -502,18 +549,7 @@ __device__ __forceinline__ void adam_window_block(const AdamArgs& a, const uint3
 #pragma unroll
       for (int l = 0; l < NW; ++l) B.t[u] &= swb[l * sws + (int)row];
     }
-#pragma unroll
-    for (int u = 0; u < HB; ++u) {
-#if RSX_ADAM_NT
-      B.var[u] = __builtin_nontemporal_load(&var4[B.ec[u]]);
-      B.m[u] = __builtin_nontemporal_load(&m4[B.ec[u]]);
-      B.v[u] = __builtin_nontemporal_load(&v4[B.ec[u]]);
-#else
-      B.var[u] = var4[B.ec[u]];
-      B.m[u] = m4[B.ec[u]];
-      B.v[u] = v4[B.ec[u]];
-#endif
-    }
+    load_state(B, with_var);
   };
   auto store = [&](const Batch& B) {
 #pragma unroll
@@ -533,10 +569,10 @@ __device__ __forceinline__ void adam_window_block(const AdamArgs& a, const uint3
   };
   // Batches in which some element of the wave leaves the packed forms' domain are left untouched by the pipeline and redone
   // in the IEEE form after it, from memory (a wave-uniform decision; the hot loop then holds the packed form only).
-  uint32_t redo = fast_ok ? 0u : (1u << NB) - 1u;
+  // (bit b: batch b of the block; COMPACT, bit NB + b: batch b of the list)
+  uint32_t redo = 0u;
   auto finish = [&](const int b, Batch& B) {
-    if (!fast_ok) return;
-    bool bad = false;
+    bool bad = !fast_ok;
 #pragma unroll
     for (int u = 0; u < HB; ++u) bad |= adam_win_guard4(B.var[u], B.m[u], B.v[u], m_lo_bits);
     if (__builtin_amdgcn_ballot_w64(bad) != 0ull) {
@@ -571,7 +607,130 @@ __device__ __forceinline__ void adam_window_block(const AdamArgs& a, const uint3
     }
     store(B);
   };
-  {
+  // COMPACT, phase 2: batch b of the list is entries [b * ADAM_T * HB, ...), 64 * HB consecutive ones per wave; the wave that
+  // takes the first ones rotates with the block (a short list keeps one wave busy: not the same SIMD's every time)
+  const int lane = tid & 63;
+  const uint32_t wave_first = (((uint32_t)__builtin_amdgcn_readfirstlane(tid >> 6) + blk) % (ADAM_T / 64u)) * (64u * HB);
+  uint32_t n_live = 0u;
+  auto listed = [&](const int b) { return (uint32_t)b * (ADAM_T * HB) + wave_first < n_live; };      // (wave-uniform)
+  auto issue_listed = [&](const int b, Batch& B) {
+#pragma unroll
+    for (int u = 0; u < HB; ++u) {
+      const uint32_t idx = (uint32_t)b * (ADAM_T * HB) + wave_first + (uint32_t)u * 64u + (uint32_t)lane;
+      B.live[u] = idx < n_live;
+      B.ec[u] = base + (B.live[u] ? lds[idx] : 0u);      // (beyond the list: the block's first float4, loaded and dropped)
+      B.t[u] = -1;
+    }
+    load_state(B, true);
+  };
+  if constexpr (COMPACT) {
+    const bool gate = win_shortcut_gate<NW>(a, h.alpha, aw);
+    const unsigned long long row_lanes = (lpr >= 64 ? ~0ull : (1ull << lpr) - 1ull) << (lane & ~(lpr - 1));
+    uint32_t* const list_n = lds + ADAM_T * U;
+    if (tid == 0) *list_n = 0u;
+    __syncthreads();
+    // the row's lanes vote: untouched (some update is due), still (void or idle: var and m keep their bits), row_v0 (void)
+    auto vote = [&](const Batch& B, const int u, bool& untouched, bool& still, bool& row_v0) {
+      const uint32_t mx = __float_as_uint(B.m[u].x), my = __float_as_uint(B.m[u].y), mz = __float_as_uint(B.m[u].z),
+                     mw = __float_as_uint(B.m[u].w);
+      const uint32_t vx = __float_as_uint(B.v[u].x), vy = __float_as_uint(B.v[u].y), vz = __float_as_uint(B.v[u].z),
+                     vw = __float_as_uint(B.v[u].w);
+      const uint32_t v_top = max(max(vx, vy), max(vz, vw));         // <= the bits of +inf: no sign, no NaN
+      const bool row_m0 = (__builtin_amdgcn_ballot_w64((mx | my | mz | mw) != 0u) & row_lanes) == 0ull;
+      const bool row_vok = (__builtin_amdgcn_ballot_w64(v_top > 0x7f800000u) & row_lanes) == 0ull;
+      row_v0 = (__builtin_amdgcn_ballot_w64((vx | vy | vz | vw) != 0u) & row_lanes) == 0ull;
+      untouched = B.live[u] && B.t[u] < 0;
+      still = gate && row_m0 && row_vok;
+    };
+    // Is every row of this wave's first batch that has updates due a live one (and is there one)?  Then the wave takes the
+    // one-pass pipeline for its share of the block (right for any rows): where the tables have filled up, the compact form
+    // costs the one-pass form's time and a look at one batch
+    auto wave_dense = [&](const Batch& B) {
+      unsigned long long due = 0ull, spared = 0ull;
+#pragma unroll
+      for (int u = 0; u < HB; ++u) {
+        bool untouched, still, row_v0;
+        vote(B, u, untouched, still, row_v0);
+        due |= __builtin_amdgcn_ballot_w64(untouched);
+        spared |= __builtin_amdgcn_ballot_w64(untouched && still);
+      }
+      return !gate || (due != 0ull && spared == 0ull);
+    };
+    auto classify = [&](const Batch& B) {
+      unsigned long long lm[HB];
+      bool is_live[HB];
+      uint32_t total = 0u;
+#pragma unroll
+      for (int u = 0; u < HB; ++u) {
+        bool untouched, still, row_v0;
+        vote(B, u, untouched, still, row_v0);
+        is_live[u] = untouched && !still;
+        lm[u] = __builtin_amdgcn_ballot_w64(is_live[u]);
+        total += (uint32_t)__popcll(lm[u]);
+        if (untouched && still && !row_v0) {                        // idle: v alone moves
+          float4 v = B.v[u];
+#pragma unroll
+          for (int j = 0; j < 1 + NW; ++j) {
+            v.x = v.x * h.b2;
+            v.y = v.y * h.b2;
+            v.z = v.z * h.b2;
+            v.w = v.w * h.b2;
+          }
+#if RSX_ADAM_NT
+          __builtin_nontemporal_store(v, &v4[B.ec[u]]);
+#else
+          v4[B.ec[u]] = v;
+#endif
+        }
+      }
+      if (total != 0u) {                                            // (wave-uniform)
+        uint32_t at = 0u;
+        if (lane == 0) at = atomicAdd(list_n, total);
+        at = (uint32_t)__builtin_amdgcn_readfirstlane((int)at);
+#pragma unroll
+        for (int u = 0; u < HB; ++u) {
+          const uint32_t before = __builtin_amdgcn_mbcnt_hi((uint32_t)(lm[u] >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)lm[u], 0u));
+          if (is_live[u]) lds[at + before] = (uint32_t)(B.ec[u] - base);
+          at += (uint32_t)__popcll(lm[u]);
+        }
+      }
+    };
+    bool dense;
+    {
+      Batch bt[2];
+      issue(0, bt[0], false);
+      dense = wave_dense(bt[0]);                                    // (wave-uniform)
+      if (!dense) {
+#pragma unroll
+        for (int b = 0; b < NB; ++b) {
+          if (b + 1 < NB) issue(b + 1, bt[(b + 1) & 1], false);
+          classify(bt[b & 1]);
+        }
+      }
+    }
+    __syncthreads();
+    n_live = (uint32_t)__builtin_amdgcn_readfirstlane((int)*list_n);
+    {
+      Batch bt[2];
+      if (listed(0)) issue_listed(0, bt[0]);
+#pragma unroll
+      for (int b = 0; b < NB; ++b) {
+        if (b + 1 < NB && listed(b + 1)) issue_listed(b + 1, bt[(b + 1) & 1]);
+        if (listed(b)) finish(NB + b, bt[b & 1]);
+      }
+    }
+    // (after the list, not before the barrier: the other waves do not wait for it, and with the two pipelines' live ranges
+    // apart the kernel needs no scratch)
+    if (dense) {                                                    // the one-pass form's pipeline for this wave's lanes
+      Batch bt[2];
+      issue(0, bt[0]);
+#pragma unroll
+      for (int b = 0; b < NB; ++b) {
+        if (b + 1 < NB) issue(b + 1, bt[(b + 1) & 1]);
+        finish(b, bt[b & 1]);
+      }
+    }
+  } else {
     Batch bt[2];
     issue(0, bt[0]);
 #pragma unroll
@@ -583,10 +742,11 @@ __device__ __forceinline__ void adam_window_block(const AdamArgs& a, const uint3
   redo = __builtin_amdgcn_readfirstlane(redo);
   if (redo != 0u) {
 #pragma unroll 1
-    for (int b = 0; b < NB; ++b) {
+    for (int b = 0; b < (COMPACT ? 2 * NB : NB); ++b) {
       if (!(redo >> b & 1u)) continue;
       Batch B;
-      issue(b, B);
+      if (COMPACT && b >= NB) issue_listed(b - NB, B);
+      else issue(b, B);
 #pragma unroll
       for (int u = 0; u < HB; ++u) {     // (unrolled: a dynamically indexed register array is demoted to scratch)
         F4_APPLY(adam_sparse1, B.var[u], B.m[u], B.v[u], F4Z, false, h);

@@ -718,6 +718,7 @@ class AdamTF1:
                 sl.state, sl.blk_lo, sl.blk_hi = self.state.data_ptr(), lo, hi
                 sl.window_block_u = int(window_block_u)
                 sl.alphas_from_state = 1 if (window_block_u and lo > 0) else 0
+                sl.window_compact = 0 if window_block_u else int(_lib.form("window_compact") != "0")
                 sl._keep = arr
                 out.append(sl)
             else:

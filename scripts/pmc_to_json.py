@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """profiles/<tag>_pmc_FETCH_SIZE_deepfm.txt + <tag>_pmc_WRITE_SIZE_deepfm.txt (scripts/pmc.sh, separate --pmc passes) ->
 profiles/pmc_adam_window_k.json and profiles/pmc_adam_multi_k.json, the files bench.py's `roofline.traffic` reads.
-usage: python scripts/pmc_to_json.py r06_z 6"""
+usage: python scripts/pmc_to_json.py r06_z 6      (the tag may be any prefix: window_compact 7)"""
 import json
 import os
 import re
@@ -26,13 +26,14 @@ n_sparse = R * D + R                    # table elements + the first-order vecto
 n_dense = 72903 + 1                     # deepfm.py's dense arena (624x100 + 100x100 + ... ; bench.py prints the exact figure)
 for kern, key, alg in (("adam_window_k<7>", "adam_window_k", 24 * n_sparse + 4 * 8 * R),
                        ("adam_multi_k", "adam_multi_k", 24 * n_sparse + 32 * n_dense)):
-    fk = next((k for k in fetch if k.startswith("void " + kern) or k.startswith(kern)), None)
-    wk = next((k for k in write if k.startswith("void " + kern) or k.startswith(kern)), None)
+    stem = kern.rstrip(">")             # (adam_window_k<7, true>: the compact form of the sweep, the default)
+    fk = next((k for k in fetch if k.startswith("void " + stem) or k.startswith(stem)), None)
+    wk = next((k for k in write if k.startswith("void " + stem) or k.startswith(stem)), None)
     if fk is None or wk is None:
         print("no rows for", kern)
         continue
     f, w = fetch[fk], write[wk]
-    out = {"kernel": kern, "model": "deepfm",
+    out = {"kernel": fk[5:].split("(")[0] if fk.startswith("void ") else kern, "model": "deepfm",
            "command": "rocprofv3 --pmc <CTR> --kernel-trace --output-format csv -- python bench.py --no_cpu_baseline --no_configs "
                       "--steps 64 --warmup 32  (one counter per pass: scripts/pmc.sh)",
            "FETCH_SIZE_kb_per_launch": f, "WRITE_SIZE_kb_per_launch": w,
