@@ -988,6 +988,60 @@ int rsx_rank_count_lists(const float* scores, int ld, const int32_t* cand_id, co
                          const int32_t* tgt_id, int T, int32_t* out_count, int32_t* out_pos, float* out_score, int U, int n,
                          rsx_stream_t stream);
 
+/* (e) rsx_din_retrieve_candidates_rules (csrc/retrieve.hip): (c) with category filters.
+ * serving.Predictor.recommend_two_stage / retrieve_candidates with categories / exclude_categories.  Added behind
+ * rsx_version() 107 without a new number, as (d) was: a caller that must tell looks the symbol up.
+ * The arguments of (c), and behind include_seeds: allow [U, Wg] (uint32, device), Wg = ceil(G / 32) words per row, bit (g & 31)
+ * of word (g >> 5) of row u set = category g is ALLOWED for user u -- the bitmap layout of rsx_topk_rows_rules -- and G, the
+ * number of categories.  A position is a candidate of u only when, beside (c)'s conditions, its cat_cate is inside [0, G) and
+ * has its bit set in allow[u, :].  A position that fails is not a candidate at all: it is not counted in n_cand, not written,
+ * and leaves no gap -- the outputs are what (c) writes for the filtered set, padding included.  The SEEDS are not filtered: a
+ * history item of a denied category still contributes its neighbour row (and, with include_seeds, is then dropped itself).
+ * A row of allow with every bit of [0, G) set gives (c)'s outputs bit for bit when every cat_cate is inside [0, G); a row of
+ * zeros gives n_cand = 0 and padding only.  allow == NULL: G is ignored and (c)'s kernel runs -- positions, ids, categories,
+ * padding and counts are (c)'s bit for bit.
+ * The kernel is (c)'s with the user's allow row staged once in LDS (4 Wg bytes behind (c)'s plan) and one more test in the pass
+ * that clears the excluded bits of the LDS bitmap.  One workgroup per user, no global atomics, no workspace, no grid-wide
+ * step; a row's outputs depend on that row's history, exclusion row and allow row and on the shared tables only.  Deterministic.
+ * RSX_EINVAL (before any HIP call): (c)'s cases; G <= 0 when allow is given.  Envelope
+ * (rsx_din_retrieve_candidates_rules_supported; RSX_EUNSUPPORTED outside, before any HIP call): (c)'s, and 1 <= G <= 65 536 --
+ * an allow row of at most 8 KB, so that the largest plan (N = 2^20: 134 720 bytes) stays at 142 912 of the 163 840 bytes. */
+int rsx_din_retrieve_candidates_rules_supported(int N, int P, int n_nbr, int E, int G);
+int rsx_din_retrieve_candidates_rules(const int32_t* hist_item, int P, const int32_t* first_pos, int n_item,
+                                      const int32_t* nbr_pos, const int32_t* nbr_count, int n_nbr, const int32_t* cat_item,
+                                      const int32_t* cat_cate, int N, const int32_t* excl, int E, int include_seeds,
+                                      const uint32_t* allow, int G, int32_t* cand_pos, int32_t* cand_item, int32_t* cand_cate,
+                                      int32_t* n_cand, int cap, int U, rsx_stream_t stream);
+
+/* (f) rsx_topk_lists_capped (csrc/topk_capped.hip): (b) with a per-category cap over PER-ROW categories.
+ * serving.Predictor.recommend_two_stage with max_per_category.  Added behind rsx_version() 107 without a new number.
+ * The contract of (b) -- scores, ld, n_valid, the running list out_val / out_idx [U, k], state [U, 2] = {filled, next_index}
+ * zeroed by the host when a request starts -- with these additions.  Every entry of row u has a category:
+ * cate[u * ld_cate + a] for the entry of ABSOLUTE index a (next_index + j for new score j) -- for a request fed in one call,
+ * the cand_cate [U, cap] that (c) / (e) wrote.  A cate row must cover every index fed so far, ld_cate >= next_index + n, and
+ * stay unchanged over the request: under a cap the running list's entries are looked up again on every call.
+ *   CAP: 1 <= m <= 16 keeps at most m entries of one category in row u's list, by definition (b) of rsx_topk_rows_rules: take
+ *   the row's LIVE entries (j < n_valid[u]) over all calls of the request in the ORDER of rsx_topk_rows; walk them and keep an
+ *   entry unless m kept entries of its category precede it; the list holds the first k kept ones.  The cap counts entries, not
+ *   ids.  filled = the number kept, at most k: it can stay below k while live entries remain.  The running list of k entries
+ *   is exact for rsx_topk_rows_rules' reason: an entry that left the capped top k of what was fed so far never returns.
+ * A live entry whose category is outside [0, G), or whose absolute index is at or beyond ld_cate, is LEFT OUT (key 0, never
+ * used as an index); so is a list entry that is found so on a later call.  Columns at and beyond n_valid[u] are never read:
+ * neither their scores nor their categories.  next_index advances by n.
+ * With m == 0 (cate, ld_cate and G are then ignored; cate may be NULL) the outputs and the state are (b)'s, bit for bit.
+ * ONE workgroup per row, in place, no workspace, no grid-wide step, no global atomics, no floating-point atomics; a row's result
+ * depends on its scores, its count, its state and its own cate row only.  The m-th largest key of every category is found by
+ * m rounds of 64-bit integer LDS atomicMax over two [G] arrays (keys are unique and max is commutative: independent of the
+ * order threads run in); the keys' categories are cached in LDS, 16 bits each.  Deterministic.  Threads: rsx_topk_rows_threads.
+ * RSX_EINVAL (before any HIP call): a NULL pointer that is needed (cate when m > 0), U / n / k <= 0, ld < n, m < 0, and with
+ * m > 0: G <= 0 or ld_cate < n.  Envelope (rsx_topk_lists_capped_supported(n, k, G, m); RSX_EUNSUPPORTED outside, before any HIP
+ * call): that of (b), m <= 16, and with m > 0: G <= 65 535 and an LDS plan of at most 160 KB,
+ * 8 (n + k) + 16 k + 1 056 + 16 G + 2 (n + k) <= 163 840 -- for G = 802 and k = 1 024 that is n + k <= 13 356; a list of 3 328
+ * columns then takes 73 792 bytes.  With m == 0 it is rsx_topk_rows_supported(n, k) (G >= 0). */
+int rsx_topk_lists_capped_supported(int n, int k, int G, int m);
+int rsx_topk_lists_capped(const float* scores, int ld, const int32_t* n_valid, const int32_t* cate, int ld_cate, int G, int m,
+                          int U, int n, int k, float* out_val, int32_t* out_idx, int32_t* state, rsx_stream_t stream);
+
 /* ---------------------------------------------------------------------------------------------
  * DCN cross layers, dcn/dcn.py:132-142: x_{l+1} = (x_l . w_l) * x0 + x_l + b_l, all L
  * layers fused per example.  Forward: dim % 4 == 0, dim <= 1024, L <= 8.  Backward: the same, and the gradient slab of a wave,

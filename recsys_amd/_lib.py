@@ -407,6 +407,10 @@ _SIGS = {
     "rsx_din_retrieve_candidates": (_I, [_P, _I, _P, _I, _P, _P, _I, _P, _P, _I, _P, _I, _I, _P, _P, _P, _P, _I, _I, _P]),
     "rsx_rank_count_lists_supported": (_I, [_I, _I]),
     "rsx_rank_count_lists": (_I, [_P, _I, _P, _P, _P, _P, _I, _P, _P, _P, _I, _I, _P]),
+    "rsx_din_retrieve_candidates_rules_supported": (_I, [_I, _I, _I, _I, _I]),
+    "rsx_din_retrieve_candidates_rules": (_I, [_P, _I, _P, _I, _P, _P, _I, _P, _P, _I, _P, _I, _I, _P, _I, _P, _P, _P, _P, _I, _I, _P]),
+    "rsx_topk_lists_capped_supported": (_I, [_I, _I, _I, _I]),
+    "rsx_topk_lists_capped": (_I, [_P, _I, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P]),
     "rsx_criteo_parse_examples_supported": (_I, [_I, _I]),
     "rsx_criteo_parse_examples": (_I, [_P, C.c_int64, _P, _I, C.POINTER(ParseSpec), _P, _P, _P]),
     "rsx_criteo_parse_dev_h": (_I, [_P, C.c_int64, _P, _I, C.POINTER(ParseSpec), _P, _P]),

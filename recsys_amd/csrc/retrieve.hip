@@ -14,6 +14,13 @@
 //       totals) and writes its positions in ascending order; the slots from the count to cap are padded with -1 / 0 / 0.
 // No global atomics, no workspace; deterministic.  A count above cap cannot occur when cap >= min(N, P (n + 1)); the kernel
 // nevertheless writes no slot at or beyond cap and stores n_cand = min(count, cap).
+//
+// rsx_din_retrieve_candidates_rules is the same body with RULES compiled in (`if constexpr`: the plain kernel holds nothing of
+// it): the user's row of the category bitmap allow[u, :Wg], Wg = ceil(G / 32), is staged in LDS behind the waves' totals in (1),
+// and the pass of (4) that clears the excluded bits also clears a position whose cat_cate is outside [0, G) or has a clear bit
+// in that row -- before the count, so a disallowed position is neither counted nor written.  The seeds are untouched: a
+// history item of a denied category still contributes its neighbours.  LDS: the plain plan + 4 Wg bytes; G <= 65 536 (8 KB)
+// keeps the largest plan, N = 2^20, at 142 912 bytes of the 163 840.
 #include "topk_device.h"         // tk_excl_sort, tk_excluded, launch_big_lds
 
 namespace {
@@ -37,10 +44,15 @@ struct RetrieveArgs {
   int W, wpt;                   // bitmap words; words per thread
 };
 
+struct RetrieveRulesArgs : RetrieveArgs {
+  const uint32_t* allow;        // [U, Wg]: bit g of row u set = category g is allowed for user u
+  int G, Wg;
+};
+
 // LDS, in words behind the bitmap [W]: seed ids in history order [128], their first positions [128], the seed ids sorted [128],
-// the exclusion ids unsorted [256] and sorted [256], the waves' totals [16]
-__global__ __launch_bounds__(RT_T) void din_retrieve_k(const RetrieveArgs p) {
-  extern __shared__ unsigned long long rt_lds64[];
+// the exclusion ids unsorted [256] and sorted [256], the waves' totals [16] (RULES: the user's allow row [Wg])
+template <bool RULES, class Args>
+__device__ __forceinline__ void din_retrieve_body(const Args& p, unsigned long long* rt_lds64) {
   unsigned* bm = reinterpret_cast<unsigned*>(rt_lds64);
   int* seed = reinterpret_cast<int*>(bm + p.W);
   int* spos = seed + RT_PMAX;
@@ -54,6 +66,10 @@ __global__ __launch_bounds__(RT_T) void din_retrieve_k(const RetrieveArgs p) {
 
   // (1)
   for (int w = tid; w < p.W; w += RT_T) bm[w] = 0u;
+  if constexpr (RULES) {
+    unsigned* alw = reinterpret_cast<unsigned*>(wsum + RT_NW);
+    for (int w = tid; w < p.Wg; w += RT_T) alw[w] = p.allow[u * (size_t)p.Wg + w];
+  }
   for (int t = tid; t < P; t += RT_T) {
     const int v = p.hist_item[u * (size_t)P + t];
     int at = -1;
@@ -100,7 +116,14 @@ __global__ __launch_bounds__(RT_T) void din_retrieve_k(const RetrieveArgs p) {
     while (m) {
       const int b = __ffs((int)m) - 1;
       m &= m - 1u;
-      if (E > 0 && tk_excluded(exs, E, p.cat_item[w * 32 + b])) keep &= ~(1u << b);
+      bool out = E > 0 && tk_excluded(exs, E, p.cat_item[w * 32 + b]);
+      if constexpr (RULES) {
+        const unsigned* alw = reinterpret_cast<const unsigned*>(wsum + RT_NW);
+        const int c = p.cat_cate[w * 32 + b];
+        if (c < 0 || c >= p.G) out = true;
+        else if (!((alw[c >> 5] >> (c & 31)) & 1u)) out = true;
+      }
+      if (out) keep &= ~(1u << b);
     }
     bm[w] = keep;
     mine += __popc(keep);
@@ -144,8 +167,46 @@ __global__ __launch_bounds__(RT_T) void din_retrieve_k(const RetrieveArgs p) {
   if (tid == 0) p.n_cand[u] = cnt;
 }
 
+__global__ __launch_bounds__(RT_T) void din_retrieve_k(const RetrieveArgs p) {
+  extern __shared__ unsigned long long rt_lds64[];
+  din_retrieve_body<false>(p, rt_lds64);
+}
+
+__global__ __launch_bounds__(RT_T) void din_retrieve_rules_k(const RetrieveRulesArgs p) {
+  extern __shared__ unsigned long long rt_lds64[];
+  din_retrieve_body<true>(p, rt_lds64);
+}
+
+constexpr int RT_GMAX = 1 << 16;
+
 inline bool retrieve_envelope(int N, int P, int nn, int E) {
   return N >= 1 && N <= RT_NMAX && P >= 1 && P <= RT_PMAX && nn >= 1 && nn <= RT_NBRMAX && E >= 0 && E <= RT_EMAX;
+}
+
+// The checks and the launch of both entries; allow == nullptr: the plain kernel.
+inline int retrieve_launch(const int32_t* hist_item, int P, const int32_t* first_pos, int n_item, const int32_t* nbr_pos,
+                           const int32_t* nbr_count, int n_nbr, const int32_t* cat_item, const int32_t* cat_cate, int N,
+                           const int32_t* excl, int E, int include_seeds, const uint32_t* allow, int G, int32_t* cand_pos,
+                           int32_t* cand_item, int32_t* cand_cate, int32_t* n_cand, int cap, int U, rsx_stream_t stream) {
+  if (!hist_item || !first_pos || !nbr_pos || !nbr_count || !cat_item || !cat_cate || !cand_pos || !cand_item || !cand_cate ||
+      !n_cand || U <= 0 || P <= 0 || n_item <= 0 || n_nbr <= 0 || N <= 0 || E < 0 || cap <= 0)
+    return RSX_EINVAL;
+  if (E > 0 && !excl) return RSX_EINVAL;
+  if (allow && G <= 0) return RSX_EINVAL;
+  if (!retrieve_envelope(N, P, n_nbr, E)) return RSX_EUNSUPPORTED;
+  if (allow && G > RT_GMAX) return RSX_EUNSUPPORTED;
+  RetrieveRulesArgs p;
+  p.hist_item = hist_item; p.first_pos = first_pos; p.nbr_pos = nbr_pos; p.nbr_count = nbr_count;
+  p.cat_item = cat_item; p.cat_cate = cat_cate; p.excl = excl;
+  p.cand_pos = cand_pos; p.cand_item = cand_item; p.cand_cate = cand_cate; p.n_cand = n_cand;
+  p.P = P; p.n_item = n_item; p.N = N; p.nn = n_nbr; p.E = E; p.cap = cap; p.include_seeds = include_seeds ? 1 : 0;
+  p.W = (N + 31) / 32;
+  p.wpt = (p.W + RT_T - 1) / RT_T;
+  p.allow = allow; p.G = allow ? G : 0; p.Wg = (p.G + 31) / 32;
+  const size_t lds = 4 * ((size_t)p.W + 3 * RT_PMAX + 2 * RT_EMAX + RT_NW + (size_t)p.Wg);
+  if (lds > (size_t)PR_MAX_LDS) return RSX_EUNSUPPORTED;
+  if (!allow) return launch_big_lds<din_retrieve_k>(static_cast<const RetrieveArgs&>(p), (unsigned)U, RT_T, lds, rsx_s(stream));
+  return launch_big_lds<din_retrieve_rules_k>(p, (unsigned)U, RT_T, lds, rsx_s(stream));
 }
 
 }  // namespace
@@ -157,19 +218,20 @@ extern "C" int rsx_din_retrieve_candidates(const int32_t* hist_item, int P, cons
                                            const int32_t* cat_cate, int N, const int32_t* excl, int E, int include_seeds,
                                            int32_t* cand_pos, int32_t* cand_item, int32_t* cand_cate, int32_t* n_cand, int cap,
                                            int U, rsx_stream_t stream) {
-  if (!hist_item || !first_pos || !nbr_pos || !nbr_count || !cat_item || !cat_cate || !cand_pos || !cand_item || !cand_cate ||
-      !n_cand || U <= 0 || P <= 0 || n_item <= 0 || n_nbr <= 0 || N <= 0 || E < 0 || cap <= 0)
-    return RSX_EINVAL;
-  if (E > 0 && !excl) return RSX_EINVAL;
-  if (!retrieve_envelope(N, P, n_nbr, E)) return RSX_EUNSUPPORTED;
-  RetrieveArgs p;
-  p.hist_item = hist_item; p.first_pos = first_pos; p.nbr_pos = nbr_pos; p.nbr_count = nbr_count;
-  p.cat_item = cat_item; p.cat_cate = cat_cate; p.excl = excl;
-  p.cand_pos = cand_pos; p.cand_item = cand_item; p.cand_cate = cand_cate; p.n_cand = n_cand;
-  p.P = P; p.n_item = n_item; p.N = N; p.nn = n_nbr; p.E = E; p.cap = cap; p.include_seeds = include_seeds ? 1 : 0;
-  p.W = (N + 31) / 32;
-  p.wpt = (p.W + RT_T - 1) / RT_T;
-  const size_t lds = 4 * ((size_t)p.W + 3 * RT_PMAX + 2 * RT_EMAX + RT_NW);
-  if (lds > (size_t)PR_MAX_LDS) return RSX_EUNSUPPORTED;
-  return launch_big_lds<din_retrieve_k>(p, (unsigned)U, RT_T, lds, rsx_s(stream));
+  return retrieve_launch(hist_item, P, first_pos, n_item, nbr_pos, nbr_count, n_nbr, cat_item, cat_cate, N, excl, E, include_seeds,
+                         nullptr, 0, cand_pos, cand_item, cand_cate, n_cand, cap, U, stream);
+}
+
+extern "C" int rsx_din_retrieve_candidates_rules_supported(int N, int P, int n_nbr, int E, int G) {
+  return retrieve_envelope(N, P, n_nbr, E) && G >= 1 && G <= RT_GMAX ? 1 : 0;
+}
+
+extern "C" int rsx_din_retrieve_candidates_rules(const int32_t* hist_item, int P, const int32_t* first_pos, int n_item,
+                                                 const int32_t* nbr_pos, const int32_t* nbr_count, int n_nbr,
+                                                 const int32_t* cat_item, const int32_t* cat_cate, int N, const int32_t* excl, int E,
+                                                 int include_seeds, const uint32_t* allow, int G, int32_t* cand_pos,
+                                                 int32_t* cand_item, int32_t* cand_cate, int32_t* n_cand, int cap, int U,
+                                                 rsx_stream_t stream) {
+  return retrieve_launch(hist_item, P, first_pos, n_item, nbr_pos, nbr_count, n_nbr, cat_item, cat_cate, N, excl, E, include_seeds,
+                         allow, G, cand_pos, cand_item, cand_cate, n_cand, cap, U, stream);
 }

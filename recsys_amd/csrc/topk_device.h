@@ -4,7 +4,8 @@
 // adds the exclusion of new scores by id (topk_excl.hip's head); TK_RULES adds the category rules on top of that
 // (topk_rules.hip's head).  Each addition is compiled in with `if constexpr`, so a kernel holds nothing of the modes above it.
 // TK_COUNTED (topk_counted.hip: rsx_topk_rows_counted) is TK_PLAIN with a per-row count of valid new scores; it stands beside
-// the three, not above them, and is compiled in the same way.
+// the three, not above them, and is compiled in the same way.  TK_CAPPED (topk_capped.hip: rsx_topk_lists_capped) is TK_COUNTED with
+// TK_RULES' cap over per-row categories; the cap's rounds are one function (tk_cap) that both compile in.
 #pragma once
 #include "predict_device.h"      // launch_big_lds, PR_MAX_LDS
 
@@ -16,7 +17,7 @@ constexpr int TK_T_SMALL = 256, TK_T_BIG = 1024;
 constexpr int TK_SMALL_KEYS = 1024;     // up to this many keys a workgroup of 256 threads, above it 1024
 constexpr int TK_EMAX = 256;             // largest exclusion list of a row (EXCL)
 constexpr int TK_MMAX = 16;              // largest per-category cap (RULES)
-constexpr int TK_PLAIN = 0, TK_EXCL = 1, TK_RULES = 2, TK_COUNTED = -1;
+constexpr int TK_PLAIN = 0, TK_EXCL = 1, TK_RULES = 2, TK_COUNTED = -1, TK_CAPPED = -2;
 
 struct TopkArgs {
   const float* scores;
@@ -29,6 +30,12 @@ struct TopkArgs {
 
 struct TopkCountedArgs : TopkArgs {
   const int32_t* n_valid;                // [U]: new score j of row u is left out when j >= n_valid[u]
+};
+
+struct TopkCappedArgs : TopkCountedArgs {
+  const int32_t* cate;                   // [U, ld_cate]: row u's categories by absolute index, cate[u * ld_cate + a]
+  int ld_cate, G, m;                     // columns of a cate row, categories, cap (0: none)
+  int oThr, oCat;                        // LDS (m > 0): as TopkRulesArgs'
 };
 
 struct TopkExclArgs : TopkArgs {
@@ -86,16 +93,57 @@ __device__ __forceinline__ bool tk_excluded(const int* exs, const int E, const i
   return id > 0 && lo < E && exs[lo] == id;
 }
 
+// The cap (RULES, CAPPED).  thr[g] = the m-th largest key of category g among the T keys (0 when g holds fewer than m live keys),
+// found in m rounds: in round r every live key below its category's threshold of round r - 1 (round 0: every live key) is max-ed
+// into the category's slot.  Keys are unique and max is commutative, so the thresholds do not depend on the order threads run
+// in.  (The plain read before the atomic only spares the atomic where it could change nothing: a slot only grows inside a
+// round.)  A key below its threshold has m category mates above it and takes key 0 -- an entry of the running list included.
+// kcat: the keys' categories, each inside [0, G) wherever the key is not 0; thr: two [G] arrays; left: an LDS counter.  Every
+// thread of the workgroup calls it, after writing its keys and categories and before any barrier; -> the number of keys left.
+__device__ __forceinline__ int tk_cap(unsigned long long* keys, const unsigned short* kcat, unsigned long long* thr, const int G,
+                                      const int m, const int T, unsigned* left_at, const int tid, const int NT) {
+  unsigned long long* cur = thr;
+  unsigned long long* prev = cur + G;
+  for (int g = tid; g < 2 * G; g += NT) cur[g] = 0ull;
+  if (tid == 0) *left_at = 0u;
+  __syncthreads();
+  for (int r = 0; r < m; ++r) {
+    if (r >= 2) {                                                    // this round's slots held the thresholds of round r - 2
+      for (int g = tid; g < G; g += NT) cur[g] = 0ull;
+      __syncthreads();
+    }
+    for (int i = tid; i < T; i += NT) {
+      const unsigned long long key = keys[i];
+      if (key == 0ull) continue;
+      const int c = kcat[i];
+      if (r > 0 && key >= prev[c]) continue;
+      if (key > __hip_atomic_load(&cur[c], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)) atomicMax(&cur[c], key);
+    }
+    __syncthreads();
+    unsigned long long* t = cur; cur = prev; prev = t;
+  }
+  unsigned left = 0u;
+  for (int i = tid; i < T; i += NT) {
+    const unsigned long long key = keys[i];
+    if (key == 0ull) continue;
+    if (key < prev[kcat[i]]) keys[i] = 0ull; else ++left;
+  }
+  if (left) atomicAdd(left_at, left);
+  __syncthreads();
+  return (int)*left_at;
+}
+
 template <int MODE, class Args>
 __device__ __forceinline__ void topk_rows_body(const Args& p, unsigned long long* tk_lds) {
-  constexpr bool EXCL = MODE >= TK_EXCL, RULES = MODE == TK_RULES, COUNTED = MODE == TK_COUNTED;
+  constexpr bool EXCL = MODE >= TK_EXCL, RULES = MODE == TK_RULES, CAPPED = MODE == TK_CAPPED,
+                 COUNTED = MODE == TK_COUNTED || CAPPED;
   unsigned long long* keys = tk_lds;
   char* base = reinterpret_cast<char*>(tk_lds);
   unsigned long long* sel = reinterpret_cast<unsigned long long*>(base + p.oSel);
   float* oldv = reinterpret_cast<float*>(base + p.oOldV);
   int* oldi = reinterpret_cast<int*>(base + p.oOldI);
   unsigned* hist = reinterpret_cast<unsigned*>(base + p.oHist);
-  unsigned* misc = reinterpret_cast<unsigned*>(base + p.oMisc);      // 0: bin, 1: rank inside the bin, 2: the bin's count, 3: compaction cursor (EXCL: 4: new scores kept; RULES: 5: keys left under the cap)
+  unsigned* misc = reinterpret_cast<unsigned*>(base + p.oMisc);      // 0: bin, 1: rank inside the bin, 2: the bin's count, 3: compaction cursor (EXCL: 4: new scores kept; RULES, CAPPED: 5: keys left under the cap)
 
   const int tid = threadIdx.x, NT = blockDim.x, lane = tid & 63;
   const int n = p.n, k = p.k;
@@ -126,6 +174,20 @@ __device__ __forceinline__ void topk_rows_body(const Args& p, unsigned long long
       for (int i = tid; i < filled; i += NT) {
         const int ix = oi[i];
         const int c = (ix >= 0 && ix < next0) ? p.cate[ix] : -1;
+        const bool ok = c >= 0 && c < p.G;
+        kcat[i] = (unsigned short)(ok ? c : 0);
+        if (!ok) keys[i] = 0ull;
+      }
+    }
+  }
+  if constexpr (CAPPED) {
+    // The same with the row's own categories, cate[row, index]; an index at or beyond ld_cate is not one the caller gave.
+    if (p.m > 0) {
+      unsigned short* kcat = reinterpret_cast<unsigned short*>(base + p.oCat);
+      const int32_t* cg = p.cate + row * (size_t)p.ld_cate;
+      for (int i = tid; i < filled; i += NT) {
+        const int ix = oi[i];
+        const int c = (ix >= 0 && ix < next0 && ix < p.ld_cate) ? cg[ix] : -1;
         const bool ok = c >= 0 && c < p.G;
         kcat[i] = (unsigned short)(ok ? c : 0);
         if (!ok) keys[i] = 0ull;
@@ -167,43 +229,9 @@ __device__ __forceinline__ void topk_rows_body(const Args& p, unsigned long long
     want = Te < k ? Te : k;
     if constexpr (RULES) {
       if (p.m > 0) {
-        // The cap.  thr[g] = the m-th largest key of category g in the union (0 when g holds fewer than m keys), found in m
-        // rounds: in round r every live key below its category's threshold of round r - 1 (round 0: every live key) is
-        // max-ed into the category's slot.  Keys are unique and max is commutative, so the thresholds do not depend on the
-        // order threads run in.  (The plain read before the atomic only spares the atomic where it could change nothing:
-        // a slot only grows inside a round.)  A key below its threshold has m category mates above it and takes key 0 --
-        // an entry of the running list included.  want counts what is left.
-        const int G = p.G, m = p.m;
-        unsigned long long* cur = reinterpret_cast<unsigned long long*>(base + p.oThr);
-        unsigned long long* prev = cur + G;
-        const unsigned short* kcat = reinterpret_cast<const unsigned short*>(base + p.oCat);
-        for (int g = tid; g < 2 * G; g += NT) cur[g] = 0ull;
-        if (tid == 0) misc[5] = 0u;
-        __syncthreads();
-        for (int r = 0; r < m; ++r) {
-          if (r >= 2) {                                              // this round's slots held the thresholds of round r - 2
-            for (int g = tid; g < G; g += NT) cur[g] = 0ull;
-            __syncthreads();
-          }
-          for (int i = tid; i < T; i += NT) {
-            const unsigned long long key = keys[i];
-            if (key == 0ull) continue;
-            const int c = kcat[i];
-            if (r > 0 && key >= prev[c]) continue;
-            if (key > __hip_atomic_load(&cur[c], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)) atomicMax(&cur[c], key);
-          }
-          __syncthreads();
-          unsigned long long* t = cur; cur = prev; prev = t;
-        }
-        unsigned left = 0u;
-        for (int i = tid; i < T; i += NT) {
-          const unsigned long long key = keys[i];
-          if (key == 0ull) continue;
-          if (key < prev[kcat[i]]) keys[i] = 0ull; else ++left;
-        }
-        if (left) atomicAdd(&misc[5], left);
-        __syncthreads();
-        const int Tl = (int)misc[5];
+        // The cap (tk_cap): a key with m category mates above it takes key 0; want counts what is left.
+        const int Tl = tk_cap(keys, reinterpret_cast<const unsigned short*>(base + p.oCat),
+                              reinterpret_cast<unsigned long long*>(base + p.oThr), p.G, p.m, T, &misc[5], tid, NT);
         want = Tl < k ? Tl : k;
       }
     }
@@ -212,8 +240,29 @@ __device__ __forceinline__ void topk_rows_body(const Args& p, unsigned long long
     int nv = p.n_valid[row];
     nv = nv < 0 ? 0 : (nv > n ? n : nv);
     want = filled + nv < k ? filled + nv : k;
-    for (int j = tid; j < n; j += NT) keys[filled + j] = j < nv ? tk_key(sc[j], next0 + j) : 0ull;
-    __syncthreads();
+    if constexpr (CAPPED) {
+      if (p.m > 0) {
+        // A live new score needs a category inside [0, G) -- else key 0 -- and caches it; behind the count neither the score
+        // nor the category is read.  Then the cap over the union; want counts what is left.
+        unsigned short* kcat = reinterpret_cast<unsigned short*>(base + p.oCat);
+        const int32_t* cg = p.cate + row * (size_t)p.ld_cate;
+        for (int j = tid; j < n; j += NT) {
+          int c = -1;
+          if (j < nv && (long long)next0 + j < p.ld_cate) c = cg[next0 + j];
+          const bool ok = c >= 0 && c < p.G;
+          keys[filled + j] = ok ? tk_key(sc[j], next0 + j) : 0ull;
+          kcat[filled + j] = (unsigned short)(ok ? c : 0);
+        }
+        const int Tl = tk_cap(keys, kcat, reinterpret_cast<unsigned long long*>(base + p.oThr), p.G, p.m, T, &misc[5], tid, NT);
+        want = Tl < k ? Tl : k;
+      } else {
+        for (int j = tid; j < n; j += NT) keys[filled + j] = j < nv ? tk_key(sc[j], next0 + j) : 0ull;
+        __syncthreads();
+      }
+    } else {
+      for (int j = tid; j < n; j += NT) keys[filled + j] = j < nv ? tk_key(sc[j], next0 + j) : 0ull;
+      __syncthreads();
+    }
   } else {
     want = T < k ? T : k;
     for (int j = tid; j < n; j += NT) keys[filled + j] = tk_key(sc[j], next0 + j);
@@ -224,7 +273,7 @@ __device__ __forceinline__ void topk_rows_body(const Args& p, unsigned long long
   // (zeros) sit among no more than k kept ones (filled + kept < k < filled + n included) -- the want-th largest key is a real
   // one, every zero is smaller, and a bin that holds a zero is never "taken whole", so `key >= prefix` admits no zero.
   // RULES: the same argument, wherever the zeros sit -- under a cap entries of the running list become zeros too.
-  // COUNTED: EXCL's argument with the zeros behind the row's count.
+  // COUNTED: EXCL's argument with the zeros behind the row's count.  CAPPED: RULES' argument.
   const int nsel = (EXCL || COUNTED) ? want : k;
   const bool select = (EXCL || COUNTED) ? (T > want && want > 0) : (T > k);
   const unsigned long long* src = keys;                            // the survivors: everything when the union is no longer than k
@@ -344,6 +393,21 @@ inline long long topk_rules_layout(TopkRulesArgs* p) {
     if (p->G <= 0 || p->G > 65535) return -1;                  // (16 bits of category cache a key)
     p->oThr = (int)o; o += 16ll * p->G;
     p->oCat = (int)o; o += 2ll * (p->n + p->k);              // (last: nothing behind it needs an alignment)
+  }
+  return o;
+}
+
+// CAPPED: without a cap (m == 0) the plan is rsx_topk_rows_counted's; a cap adds 16 bytes behind misc (the counter of the keys
+// left), the two threshold arrays and the category cache.  -1: not a plan (m outside [0, 16], G outside [1, 65 535] under a cap).
+inline long long topk_capped_layout(TopkCappedArgs* p) {
+  long long o = topk_layout(p);
+  p->oThr = p->oCat = 0;
+  if (p->m < 0 || p->m > TK_MMAX) return -1;
+  if (p->m > 0) {
+    if (p->G <= 0 || p->G > 65535) return -1;
+    o += 16;
+    p->oThr = (int)o; o += 16ll * p->G;
+    p->oCat = (int)o; o += 2ll * (p->n + p->k);
   }
   return o;
 }

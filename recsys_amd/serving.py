@@ -458,7 +458,7 @@ class Predictor(DinRanking):
         self._rank = None
         self.catalogue_size = None          # N of the latest `set_catalogue` (din.py bundles)
         self.recommend_path = None          # where the latest `recommend` selected
-        self.rules_on_device = True         # False: a `recommend` with a category rule takes the host path
+        self.rules_on_device = True         # False: a `recommend` / `recommend_two_stage` with a category rule takes the host path
         self.evaluate_recommend_path = None # where the latest `evaluate_recommend` ranked
         self._cat = None
         self._nbr = None                    # `build_neighbours`' table (din.py bundles)

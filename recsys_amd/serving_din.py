@@ -38,6 +38,11 @@ one-launch and layers paths, `_run` and `predict*`, and imports every public nam
               `retrieve_candidates_host`, `rank_candidates`, `topk_rows_host`.  The same bits either way;
               `recommend_two_stage_host` is the definition.  No back-fill: a list can be shorter than top_k and differs from
               `recommend`'s by design.
+              `recommend_two_stage(..., categories=, exclude_categories=, max_per_category=m)` puts `recommend`'s category
+              rules on that list, restricted to the candidates: a disallowed entry is not retrieved, not scored and not counted
+              (rsx_din_retrieve_candidates_rules, csrc/retrieve.hip, with the bitmap beside the exclusion ids) and the cap is
+              applied over the candidates' own categories (rsx_topk_lists_capped, csrc/topk_capped.hip), still ONE graph and one
+              copy back; `rules_on_device = False` sends such requests to the host path.  The same bits either way.
               `evaluate_two_stage(u_iid_seq, u_icat_seq, held_out, ks, n_neighbours=m)` scores that list offline: whether the
               retrieval stage kept each held-out item and the exact rank of the kept ones among the user's candidates
               (`two_stage_ranks_host` is the definition; `two_stage_metrics` adds CandRecall and the mean candidate count to
@@ -291,15 +296,8 @@ def recommend_host(prob, cat_item, hist_item, exclude, top_k, exclude_seen=True,
     a, cat, rows = _catalogue_scores("recommend_host", prob, cat_item)
     U, N = rows.shape
     ids = _exclusion_ids(hist_item, exclude, U, exclude_seen)
-    m = check_max_per_category(max_per_category)
-    only = check_category_list(categories, "categories", U, a.ndim == 1, n_cate)
-    deny = check_category_list(exclude_categories, "exclude_categories", U, a.ndim == 1, n_cate)
-    rules = m is not None or only is not None or deny is not None
-    if rules:
-        cc = None if cat_cate is None else np.asarray(cat_cate)
-        if cc is None or cc.shape != cat.shape or not np.issubdtype(cc.dtype, np.integer):
-            raise _lib.RsxError("recommend_host: a category rule needs cat_cate, integers [N] like cat_item; got %s"
-                                % (None if cc is None else (cc.dtype, cc.shape),))
+    cc, only, deny, m = _category_rules("recommend_host", U, a.ndim == 1, cat, cat_cate, categories, exclude_categories,
+                                        max_per_category, n_cate)
     kk = min(k, N)
     out = {"prob": np.full((U, kk), np.nan, np.float32), "item": np.full((U, kk), -1, np.int32),
            "index": np.full((U, kk), -1, np.int32), "count": np.zeros(U, np.int32)}
@@ -311,21 +309,40 @@ def recommend_host(prob, cat_item, hist_item, exclude, top_k, exclude_seen=True,
             gone |= np.isin(cc, deny[u][deny[u] >= 0])
         pos = np.flatnonzero(~gone)
         order = pos[np.lexsort((pos, -rows[u, pos]))]
-        if m is None:
-            order = order[:kk]
-        else:                                                          # the cap: the plain greedy walk
-            taken, keep = {}, []
-            for p in order:
-                g = int(cc[p])
-                if taken.get(g, 0) < m:
-                    taken[g] = taken.get(g, 0) + 1
-                    keep.append(p)
-                    if len(keep) == kk:
-                        break
-            order = np.asarray(keep, order.dtype)
+        order = order[:kk] if m is None else _capped_walk(order, cc, m, kk)
         c = len(order)
         out["prob"][u, :c], out["item"][u, :c], out["index"][u, :c], out["count"][u] = rows[u, order], cat[order], order, c
     return out if a.ndim == 2 else _one_user(out)
+
+
+def _capped_walk(order, cc, m, kk):
+    """The cap, as the plain greedy walk: `order` (catalogue positions, best first) walked once, a position kept only when
+    fewer than m kept positions of its category cc[position] precede it, until kk are kept -> the kept positions."""
+    taken, keep = {}, []
+    for p in order:
+        g = int(cc[p])
+        if taken.get(g, 0) < m:
+            taken[g] = taken.get(g, 0) + 1
+            keep.append(p)
+            if len(keep) == kk:
+                break
+    return np.asarray(keep, order.dtype)
+
+
+def _category_rules(what, U, single, cat, cat_cate, categories, exclude_categories, max_per_category, n_cate):
+    """The category arguments of a host definition checked -> (cc, only, deny, m): the two lists (`check_category_list`), the
+    cap (`check_max_per_category`) and, when any of them is given, cat_cate as an integer array [N] like cat (RsxError
+    otherwise); cc is None when no rule is given."""
+    m = check_max_per_category(max_per_category)
+    only = check_category_list(categories, "categories", U, single, n_cate)
+    deny = check_category_list(exclude_categories, "exclude_categories", U, single, n_cate)
+    if m is None and only is None and deny is None:
+        return None, None, None, None
+    cc = None if cat_cate is None else np.asarray(cat_cate)
+    if cc is None or cc.shape != cat.shape or not np.issubdtype(cc.dtype, np.integer):
+        raise _lib.RsxError("%s: a category rule needs cat_cate, integers [N] like cat_item; got %s"
+                            % (what, None if cc is None else (cc.dtype, cc.shape)))
+    return cc, only, deny, m
 
 
 def _one_user(out):
@@ -528,13 +545,18 @@ def check_neighbours(nbr_pos, nbr_count, N):
     return pos, cnt
 
 
-def retrieve_candidates_host(nbr_pos, nbr_count, cat_item, hist_item, exclude=None, exclude_seen=True):
+def retrieve_candidates_host(nbr_pos, nbr_count, cat_item, hist_item, exclude=None, exclude_seen=True, cat_cate=None,
+                             categories=None, exclude_categories=None, n_cate=None):
     """The definition of `Predictor.retrieve_candidates`, in numpy.  nbr_pos [N, n] / nbr_count [N]: `item_neighbours_host`'s
     table; cat_item int [N]; hist_item [P'] / [U, P']; exclude None or [E'] / [U, E'].  Per user: the SEEDS are the positive
     history ids that occur in the catalogue, each resolved to its lowest position (`catalogue_first_positions`); the candidates
     are the union of the seeds' neighbour rows -- with exclude_seen=False joined by every position whose item id is a seed id
     -- without every position whose item id is a positive id of the exclusion list (`_exclusion_ids`: the history when
-    exclude_seen, then `exclude`; the list `recommend` uses).  -> a list of U int32 arrays: the sorted distinct positions."""
+    exclude_seen, then `exclude`; the list `recommend` uses).  -> a list of U int32 arrays: the sorted distinct positions.
+    CATEGORY FILTERS (off by default; they need cat_cate: int [N], the category of every catalogue entry).  categories /
+    exclude_categories: `recommend_host`'s lists ([G'] / [U, G'], negative ids padding, 0 a real category, an empty `categories`
+    allows nothing, ids >= n_cate refused when n_cate is given).  A position whose category is not ALLOWED for the user is not
+    a candidate at all.  The seeds are not filtered: a history item of a denied category still contributes its neighbours."""
     cat = np.asarray(cat_item).astype(np.int64)
     N = cat.shape[0]
     pos, cnt = check_neighbours(nbr_pos, nbr_count, N)
@@ -542,6 +564,8 @@ def retrieve_candidates_host(nbr_pos, nbr_count, cat_item, hist_item, exclude=No
     if h.ndim not in (1, 2):
         raise _lib.RsxError("retrieve_candidates_host: expected histories [P] or [U, P], got %s" % (h.shape,))
     U = 1 if h.ndim == 1 else h.shape[0]
+    cc, only, deny, _ = _category_rules("retrieve_candidates_host", U, h.ndim == 1, cat, cat_cate, categories, exclude_categories,
+                                        None, n_cate)
     ids = _exclusion_ids(h, exclude, U, exclude_seen)
     index = catalogue_first_positions(cat)
     hist = h.reshape(U, -1).astype(np.int64)
@@ -555,20 +579,33 @@ def retrieve_candidates_host(nbr_pos, nbr_count, cat_item, hist_item, exclude=No
         if not exclude_seen:
             mark |= np.isin(cat, cat[at])
         mark &= ~np.isin(cat, ids[u][ids[u] > 0])
+        if only is not None:
+            mark &= np.isin(cc, only[u][only[u] >= 0])
+        if deny is not None:
+            mark &= ~np.isin(cc, deny[u][deny[u] >= 0])
         out.append(np.flatnonzero(mark).astype(np.int32))
     return out
 
 
-def recommend_two_stage_host(prob, nbr_pos, nbr_count, cat_item, hist_item, exclude, top_k, exclude_seen=True):
+def recommend_two_stage_host(prob, nbr_pos, nbr_count, cat_item, hist_item, exclude, top_k, exclude_seen=True, cat_cate=None,
+                             categories=None, exclude_categories=None, max_per_category=None, n_cate=None):
     """The definition of `Predictor.recommend_two_stage`, in numpy.  prob: float32 [N] (one user) or [U, N], the scores of ALL
     catalogue entries (`rank_candidates` over the whole catalogue).  `recommend_host`'s order (higher score first, equal ones
     by the lower position, NaN last) restricted to the positions `retrieve_candidates_host` gives ->
     `recommend_host`'s dictionary, kk = min(top_k, N), count[u] = min(top_k, candidates of u): it can stay below top_k and can
-    be 0 -- nothing is filled in from the rest of the catalogue."""
+    be 0 -- nothing is filled in from the rest of the catalogue.
+    CATEGORY RULES (`recommend_host`'s, restricted to the retrieved candidates; all off by default, any of them needs cat_cate).
+    categories / exclude_categories filter the candidates as `retrieve_candidates_host` does: a disallowed entry is not
+    retrieved, not scored and not counted.  max_per_category = m: walk the user's candidates in the order above and keep an
+    entry only when fewer than m kept entries of its category precede it; stop at top_k.  The cap counts entries, not ids, and
+    count[u] can stay below top_k while candidates remain; there is still no back-fill."""
     k = check_top_k(top_k)
     a, cat, rows = _catalogue_scores("recommend_two_stage_host", prob, cat_item)
     U, N = rows.shape
-    cands = retrieve_candidates_host(nbr_pos, nbr_count, cat, hist_item, exclude, exclude_seen)
+    cc, _, _, m = _category_rules("recommend_two_stage_host", U, a.ndim == 1, cat, cat_cate, categories, exclude_categories,
+                                  max_per_category, n_cate)
+    cands = retrieve_candidates_host(nbr_pos, nbr_count, cat, hist_item, exclude, exclude_seen, cat_cate=cc, categories=categories,
+                                     exclude_categories=exclude_categories, n_cate=n_cate)
     if len(cands) != U:
         raise _lib.RsxError("recommend_two_stage_host: %d histories for %d rows of scores" % (len(cands), U))
     kk = min(k, N)
@@ -576,7 +613,8 @@ def recommend_two_stage_host(prob, nbr_pos, nbr_count, cat_item, hist_item, excl
            "index": np.full((U, kk), -1, np.int32), "count": np.zeros(U, np.int32)}
     for u, pos in enumerate(cands):
         pos = pos.astype(np.int64)
-        order = pos[np.lexsort((pos, -rows[u, pos]))][:kk]
+        order = pos[np.lexsort((pos, -rows[u, pos]))]
+        order = order[:kk] if m is None else _capped_walk(order, cc, m, kk)
         c = len(order)
         out["prob"][u, :c], out["item"][u, :c], out["index"][u, :c], out["count"][u] = rows[u, order], cat[order], order, c
     return out if a.ndim == 2 else _one_user(out)
@@ -1269,22 +1307,40 @@ class DinRanking:
     def _two_stage_on_device(self, k, cap):
         return self._retrieve_on_device(cap) and k <= TOPK_MAX_K and bool(_lib.lib().rsx_topk_rows_supported(cap, k))
 
-    def two_stage_path_for(self, top_k, hist_len=None):
+    def _two_stage_rules_on_device(self, k, cap, m):
+        """A two-stage request with a category rule (m: the cap, None or 0 for none): the plain request's conditions, the
+        switch, m <= 16, and the envelopes of rsx_din_retrieve_candidates_rules and rsx_topk_lists_capped for this bundle's
+        n_cate (each asked whether or not the request needs it: the answer is one per (k, cap, m))."""
+        m = int(m or 0)
+        if not (self.rules_on_device and self._two_stage_on_device(k, cap) and m <= RULES_MAX_M):
+            return False
+        P, _, G, _ = self._din_sizes()
+        L = _lib.lib()
+        return (bool(L.rsx_din_retrieve_candidates_rules_supported(self.catalogue_size, P, self._nbr["n"], 0, G))
+                and bool(L.rsx_topk_lists_capped_supported(cap, k, G, m)))
+
+    def two_stage_path_for(self, top_k, hist_len=None, max_per_category=None, rules=False):
         """Where `recommend_two_stage(..., top_k=top_k)` runs for histories of hist_len positions (default: the bundle's):
         "device" or "host" (None for a bundle that ranks no candidates).  "device" needs `build_neighbours`' table on the
         device, rank_path == "fused", k <= 1024 and a candidate capacity -- min(N, hist_len (n + 1)) rounded up to 64 -- of at
         most max_candidates.  A request that names more than 256 distinct positive exclusion ids for one user still takes the
-        host path; `two_stage_path` records what the latest request took."""
+        host path; `two_stage_path` records what the latest request took.  With max_per_category or rules=True (a request that
+        names categories / exclude_categories) the answer is that of a request with a category rule: "device" needs
+        `rules_on_device`, a cap of at most 16 and the envelopes of rsx_din_retrieve_candidates_rules and rsx_topk_lists_capped
+        as well."""
         def on_device():
-            k = check_top_k(top_k)
-            return self._nbr is not None and self._two_stage_on_device(
-                k, self._two_stage_cap(self._din_sizes()[0] if hist_len is None else hist_len))
+            k, m = check_top_k(top_k), check_max_per_category(max_per_category)
+            if self._nbr is None:
+                return False
+            cap = self._two_stage_cap(self._din_sizes()[0] if hist_len is None else hist_len)
+            return self._two_stage_rules_on_device(k, cap, m) if m is not None or rules else self._two_stage_on_device(k, cap)
         return self._path_for(on_device)
 
-    def _ts_setup(self, U, k):
+    def _ts_setup(self, U, k, rules=False):
         """The static buffers of a device two-stage request beside the rank buffers: cand_pos [U, max_candidates], n_cand [U],
         the exclusion ids [U, 256], and ONE flat buffer that holds out_val [U, k], behind it the catalogue positions [U, k] and
-        state [U, 2] (so the answer and `filled` come back in one copy) and, last, out_idx [U, k], which stays on the device."""
+        state [U, 2] (so the answer and `filled` come back in one copy) and, last, out_idx [U, k], which stays on the device.
+        The category bitmap [U, ceil(n_cate / 32)] joins them with the first request that names a category filter (rules)."""
         import torch
         Ub, dev, i32 = self._rank["U"], self.device, torch.int32
 
@@ -1295,63 +1351,96 @@ class DinRanking:
             if k:
                 t["buf"] = torch.zeros(3 * Ub * k + 2 * Ub, dtype=torch.float32, device=dev)
             return t
-        return self._scratch("ts", ("two_stage",), Ub * k, alloc)
+        t = self._scratch("ts", ("two_stage",), Ub * k, alloc)
+        if rules and "allow" not in t:
+            t["allow"] = torch.zeros(Ub * ((self._din_sizes()[2] + 31) // 32), dtype=i32, device=dev)
+        return t
 
-    def _retrieve_launch(self, U, E, cap, seeds, nb, n_cand_ptr):
+    def _retrieve_launch(self, U, E, cap, seeds, nb, n_cand_ptr, bitmap=False):
         """rsx_din_retrieve_candidates over the U histories in place and the table `nb` (the built one or a narrowed copy): the
-        positions into r["ts"]["pos"], the ids straight into the rank launch's candidate buffers, the counts to n_cand_ptr."""
+        positions into r["ts"]["pos"], the ids straight into the rank launch's candidate buffers, the counts to n_cand_ptr.
+        bitmap: rsx_din_retrieve_candidates_rules with the category bitmap of r["ts"]["allow"] instead."""
         import torch
         r, t = self._rank, self._rank["ts"]
         cat_i, cat_c = (x.data_ptr() for x in self._cat["dev"])
-        P, n_item = self._din_sizes()[:2]
+        P, n_item, G = self._din_sizes()[:3]
         pos, _, count = nb["dev"]
-        _lib.check(_lib.lib().rsx_din_retrieve_candidates(
-            r["hist"][0].data_ptr(), P, self._nbr["first"].data_ptr(), n_item, pos.data_ptr(), count.data_ptr(), nb["n"], cat_i,
-            cat_c, self.catalogue_size, t["excl"].data_ptr(), int(E), int(seeds), t["pos"].data_ptr(), r["cand"][0].data_ptr(),
-            r["cand"][1].data_ptr(), n_cand_ptr, int(cap), int(U), torch.cuda.current_stream().cuda_stream),
-            "rsx_din_retrieve_candidates")
+        L = _lib.lib()
+        head = (r["hist"][0].data_ptr(), P, self._nbr["first"].data_ptr(), n_item, pos.data_ptr(), count.data_ptr(), nb["n"], cat_i,
+                cat_c, self.catalogue_size, t["excl"].data_ptr(), int(E), int(seeds))
+        tail = (t["pos"].data_ptr(), r["cand"][0].data_ptr(), r["cand"][1].data_ptr(), n_cand_ptr, int(cap), int(U),
+                torch.cuda.current_stream().cuda_stream)
+        if bitmap:
+            _lib.check(L.rsx_din_retrieve_candidates_rules(*head, t["allow"].data_ptr(), G, *tail), "rsx_din_retrieve_candidates_rules")
+        else:
+            _lib.check(L.rsx_din_retrieve_candidates(*head, *tail), "rsx_din_retrieve_candidates")
 
-    def _two_stage_launch(self, U, k, E, cap, seeds):
+    def _two_stage_launch(self, U, k, E, cap, seeds, rules=None):
         """The whole request, one chain: the state's zeroing, rsx_din_retrieve_candidates (the candidates' ids straight into
         the rank launch's candidate buffers), rsx_predict_din_rank over [U, cap], rsx_topk_rows_counted, and the gather that
         turns the selected columns into catalogue positions.  Every address is fixed, so `_run` captures it as ONE graph per
-        (U, k, E, cap, seeds).  k = 0: the retrieval alone (`retrieve_candidates`)."""
+        (U, k, E, cap, seeds).  k = 0: the retrieval alone (`retrieve_candidates`).
+        rules = (bitmap present, m) for a request with a category rule: with a bitmap rsx_din_retrieve_candidates_rules takes
+        the retrieval's place, and with m > 0 rsx_topk_lists_capped the selection's, over the candidate categories the
+        retrieval wrote into the rank launch's buffer [U, cap]."""
         import torch
         r, t = self._rank, self._rank["ts"]
+        bitmap, m = rules or (False, 0)
         if k:
             t["buf"][2 * U * k:2 * U * k + 2 * U].zero_()
-        self._retrieve_launch(U, E, cap, seeds, self._nbr, t["n_cand"].data_ptr())
+        self._retrieve_launch(U, E, cap, seeds, self._nbr, t["n_cand"].data_ptr(), bitmap)
         if not k:
             return
         self._rank_launch(U, cap)
         val = t["buf"].data_ptr()
         state, idx = val + 8 * U * k, val + 8 * U * k + 8 * U
-        _lib.check(_lib.lib().rsx_topk_rows_counted(r["prob"].data_ptr(), int(cap), t["n_cand"].data_ptr(), int(U), int(cap),
-                                                    int(k), val, idx, state, torch.cuda.current_stream().cuda_stream),
-                   "rsx_topk_rows_counted")
+        L, stream = _lib.lib(), torch.cuda.current_stream().cuda_stream
+        if m:
+            _lib.check(L.rsx_topk_lists_capped(r["prob"].data_ptr(), int(cap), t["n_cand"].data_ptr(), r["cand"][1].data_ptr(),
+                                               int(cap), self._din_sizes()[2], int(m), int(U), int(cap), int(k), val, idx, state,
+                                               stream), "rsx_topk_lists_capped")
+        else:
+            _lib.check(L.rsx_topk_rows_counted(r["prob"].data_ptr(), int(cap), t["n_cand"].data_ptr(), int(U), int(cap), int(k),
+                                               val, idx, state, stream), "rsx_topk_rows_counted")
         ints = t["buf"].view(torch.int32)
         col = ints[2 * U * k + 2 * U:3 * U * k + 2 * U].view(U, k).clamp(0, cap - 1).long()     # (past `filled`: unspecified)
         torch.gather(t["pos"][:U * cap].view(U, cap), 1, col, out=ints[U * k:2 * U * k].view(U, k))
 
-    def _two_stage_device(self, U, k, P, Pq, cap, u_iid_seq, u_icat_seq, ids, seeds):
+    def _two_stage_device(self, U, k, P, Pq, cap, u_iid_seq, u_icat_seq, ids, seeds, rules=None):
         """ids: int32 [U, E] host, E one of the exclusion capacities.  k = 0 -> (cand_pos [U, cap], n_cand [U]); otherwise the
-        answer of `recommend_two_stage_host` for U users."""
+        answer of `recommend_two_stage_host` for U users.  rules: None, or (bitmap: uint32 [U, W] host or None, m: the cap or
+        0) of a request with a category rule; its graph's key ends in (bitmap present, m), a plain request's key is unchanged."""
         import torch
         with torch.no_grad():
             r = self._rank_setup(U)
-            t = self._ts_setup(U, k)
+            how = None if rules is None else (rules[0] is not None, int(rules[1]))
+            t = self._ts_setup(U, k, bool(how and how[0]))
             self._rank_histories(r, U, P, Pq, u_iid_seq, u_icat_seq)
             E = _ship_exclusion(t["excl"], ids, U)
-            self._run(("two_stage", U, k, E, cap, bool(seeds)), lambda: self._two_stage_launch(U, k, E, cap, seeds))
+            if how and how[0]:
+                W = rules[0].shape[1]
+                t["allow"][:U * W].view(U, W).copy_(torch.from_numpy(rules[0].view(np.int32)), non_blocking=True)
+            self._run(("two_stage", U, k, E, cap, bool(seeds)) + (how or ()),
+                      lambda: self._two_stage_launch(U, k, E, cap, seeds, how))
             if not k:
                 return t["pos"][:U * cap].view(U, cap).cpu().numpy(), t["n_cand"][:U].cpu().numpy()
             h = t["buf"][:2 * U * k + 2 * U].cpu().numpy()           # the ONE device-to-host copy: pairs and `filled`
         return self._unpack_list(h, U, k)
 
-    def _two_stage_request(self, what, u_iid_seq, u_icat_seq, exclude_seen, exclude):
+    def _two_stage_request(self, what, u_iid_seq, u_icat_seq, exclude_seen, exclude, categories=None, exclude_categories=None,
+                           max_per_category=None):
+        """-> (U, P, Pq, single, ids, cap, rules): rules is None for a request without a category rule, else (bitmap: uint32
+        [U, W] or None when no list is given, m: the cap or 0) -- what `recommend` makes of the same three arguments."""
         self._need_neighbours(what)
         U, P, Pq, single, ids = self._history_request(what, u_iid_seq, u_icat_seq, exclude_seen, exclude)
-        return U, P, Pq, single, ids, self._two_stage_cap(Pq)
+        n_cate = self._din_sizes()[2]
+        m = check_max_per_category(max_per_category)
+        only = check_category_list(categories, "categories", U, single, n_cate)
+        deny = check_category_list(exclude_categories, "exclude_categories", U, single, n_cate)
+        rules = None
+        if m is not None or only is not None or deny is not None:
+            rules = (category_bitmap(only, deny, n_cate) if only is not None or deny is not None else None, m or 0)
+        return U, P, Pq, single, ids, self._two_stage_cap(Pq), rules
 
     def _rank_lists_host(self, hi, hc, rows):
         """rows: per user the catalogue positions of a candidate list (`retrieve_candidates_host`) -> prob float32 [U, width]:
@@ -1363,18 +1452,27 @@ class DinRanking:
             li[u, :len(x)], lc[u, :len(x)] = ci[x], cc[x]
         return self.rank_candidates(hi, hc, li, lc)["prob"].reshape(len(rows), width)
 
-    def retrieve_candidates(self, u_iid_seq, u_icat_seq, exclude_seen=True, exclude=None):
+    def retrieve_candidates(self, u_iid_seq, u_icat_seq, exclude_seen=True, exclude=None, categories=None, exclude_categories=None):
         """After `build_neighbours`: the catalogue positions stage two of `recommend_two_stage` would score for these histories
         ([P'] or [U, P']) -- `retrieve_candidates_host` is the definition -> {'index': int32 [U, cap], ascending, -1 beyond the
         count; 'count': int32 [U]}, cap = min(N, P' (n + 1)) rounded up to 64.  One user: index cut to count, count an int.
-        With held-out items this measures the candidate recall of the retrieval stage."""
-        U, P, Pq, single, ids, cap = self._two_stage_request("retrieve_candidates", u_iid_seq, u_icat_seq, exclude_seen, exclude)
-        padded = self._device_exclusion(ids) if self._retrieve_on_device(cap) else None
+        With held-out items this measures the candidate recall of the retrieval stage.  categories / exclude_categories
+        (`recommend`'s lists) keep only / drop the positions of those categories: the filtered positions come back, on the
+        device through rsx_din_retrieve_candidates_rules when `rules_on_device` and its envelope allow."""
+        U, P, Pq, single, ids, cap, rules = self._two_stage_request("retrieve_candidates", u_iid_seq, u_icat_seq, exclude_seen,
+                                                                    exclude, categories, exclude_categories)
+        on_device = self._retrieve_on_device(cap)
+        if on_device and rules is not None:
+            on_device = self.rules_on_device and bool(_lib.lib().rsx_din_retrieve_candidates_rules_supported(
+                self.catalogue_size, self._din_sizes()[0], self._nbr["n"], 0, self._din_sizes()[2]))
+        padded = self._device_exclusion(ids) if on_device else None
         if padded is not None:
-            index, count = self._two_stage_device(U, 0, P, Pq, cap, u_iid_seq, u_icat_seq, padded, not exclude_seen)
+            index, count = self._two_stage_device(U, 0, P, Pq, cap, u_iid_seq, u_icat_seq, padded, not exclude_seen, rules)
         else:
             pos, _, cnt = self._nbr["host"]
-            rows = retrieve_candidates_host(pos, cnt, self._cat["host"][0], u_iid_seq, exclude, exclude_seen)
+            ci, cc = self._cat["host"]
+            rows = retrieve_candidates_host(pos, cnt, ci, u_iid_seq, exclude, exclude_seen, cat_cate=cc, categories=categories,
+                                            exclude_categories=exclude_categories, n_cate=self._din_sizes()[2])
             index = np.full((U, cap), -1, np.int32)
             count = np.zeros(U, np.int32)
             for u, x in enumerate(rows):
@@ -1383,30 +1481,46 @@ class DinRanking:
             return {"index": index[0, :int(count[0])], "count": int(count[0])}
         return {"index": index, "count": count}
 
-    def recommend_two_stage(self, u_iid_seq, u_icat_seq, top_k, exclude_seen=True, exclude=None):
+    def recommend_two_stage(self, u_iid_seq, u_icat_seq, top_k, exclude_seen=True, exclude=None, categories=None,
+                            exclude_categories=None, max_per_category=None):
         """din.py bundles, after `set_catalogue` and `build_neighbours`: `recommend` over a RETRIEVED candidate set instead of
         the whole catalogue.  Stage one takes the neighbour rows of the history's items (`retrieve_candidates`), stage two scores
         those candidates exactly as `rank_candidates` scores them and returns the top_k best -- `recommend`'s result dictionary
         and one-user / U-user forms; `recommend_two_stage_host` is the definition.  count[u] = min(top_k, candidates of u): it
         can stay below top_k and can be 0 (an empty history, a history the catalogue does not hold).  There is NO back-fill
         from the rest of the catalogue, and the list differs from `recommend`'s by design: an entry outside the candidate set
-        is never returned, however well it would score.  Category rules are not offered here.
+        is never returned, however well it would score.
         `two_stage_path_for(k)` says where a request runs: "device": only the histories and the exclusion ids are shipped and
         the whole request -- rsx_din_retrieve_candidates, rsx_predict_din_rank over [U, cap], rsx_topk_rows_counted, the
         gather of the catalogue positions -- is ONE captured graph per (U, k, exclusion capacity, cap), one copy brings the
         answer back; "host": `retrieve_candidates_host`, `rank_candidates` on the padded lists, `topk_rows_host` over each
-        list's valid part.  Both give the same bits."""
+        list's valid part.  Both give the same bits.
+        CATEGORY RULES (`recommend`'s arguments, `recommend_two_stage_host` defines them; a request without one is exactly
+        the request above -- its graph key, its launches, its bits).  categories / exclude_categories keep only / drop the
+        CANDIDATES of those categories: a disallowed entry is not retrieved, not scored and not counted, while a history item
+        of a denied category still contributes its neighbours.  max_per_category = m keeps at most m entries of one category
+        in the list, walking the candidates best first; count[u] can stay below top_k and nothing is filled in.
+        `two_stage_path_for(k, hist_len, m, rules=True)` says where such a request runs: "device" (the conditions above,
+        `rules_on_device`, m <= 16, the two kernels' envelopes): the lists are folded into a bitmap [U, ceil(n_cate / 32)]
+        that is shipped with the exclusion ids; with a list rsx_din_retrieve_candidates_rules takes the retrieval's place and
+        with a cap rsx_topk_lists_capped (csrc/topk_capped.hip) the selection's, over the candidate categories the retrieval
+        wrote; still ONE captured graph, per (U, k, exclusion capacity, cap, seeds, bitmap present, m), and one copy back.
+        "host": `retrieve_candidates_host` with the lists, `rank_candidates` on the padded lists, the greedy walk of
+        `recommend_host`.  Both give the same bits."""
         k = check_top_k(top_k)
-        U, P, Pq, single, ids, cap = self._two_stage_request("recommend_two_stage", u_iid_seq, u_icat_seq, exclude_seen, exclude)
-        padded = self._device_exclusion(ids) if self._two_stage_on_device(k, cap) else None
+        U, P, Pq, single, ids, cap, rules = self._two_stage_request("recommend_two_stage", u_iid_seq, u_icat_seq, exclude_seen,
+                                                                    exclude, categories, exclude_categories, max_per_category)
+        on_device = self._two_stage_on_device(k, cap) if rules is None else self._two_stage_rules_on_device(k, cap, rules[1])
+        padded = self._device_exclusion(ids) if on_device else None
         if padded is not None:
             self.two_stage_path = "device"
-            out = self._two_stage_device(U, k, P, Pq, cap, u_iid_seq, u_icat_seq, padded, not exclude_seen)
+            out = self._two_stage_device(U, k, P, Pq, cap, u_iid_seq, u_icat_seq, padded, not exclude_seen, rules)
         else:
             self.two_stage_path = "host"
             pos, _, cnt = self._nbr["host"]
-            ci = self._cat["host"][0]
-            rows = retrieve_candidates_host(pos, cnt, ci, u_iid_seq, exclude, exclude_seen)
+            ci, cc = self._cat["host"]
+            rows = retrieve_candidates_host(pos, cnt, ci, u_iid_seq, exclude, exclude_seen, cat_cate=cc, categories=categories,
+                                            exclude_categories=exclude_categories, n_cate=self._din_sizes()[2])
             hi, hc = (x.reshape(U, -1) if hasattr(x, "reshape") else np.asarray(x).reshape(U, -1) for x in (u_iid_seq, u_icat_seq))
             prob = self._rank_lists_host(hi, hc, rows)
             kk = min(k, self.catalogue_size)
@@ -1414,7 +1528,12 @@ class DinRanking:
                    "index": np.full((U, kk), -1, np.int32), "count": np.zeros(U, np.int32)}
             for u, x in enumerate(rows):
                 if len(x):
-                    best = topk_rows_host(prob[u, :len(x)], kk)
+                    if rules is not None and rules[1]:                 # the cap: every candidate in order, then the walk
+                        best = topk_rows_host(prob[u, :len(x)], len(x))
+                        keep = _capped_walk(best["index"], cc[x], rules[1], kk)
+                        best = {"prob": prob[u, keep], "index": keep}
+                    else:
+                        best = topk_rows_host(prob[u, :len(x)], kk)
                     c = len(best["index"])
                     at = x[best["index"]]
                     out["prob"][u, :c], out["item"][u, :c], out["index"][u, :c], out["count"][u] = best["prob"], ci[at], at, c
