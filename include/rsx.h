@@ -1719,6 +1719,35 @@ int rsx_auc_group_finalize(uint64_t* keys, int64_t n, int group_bits, void* work
 int rsx_auc_group_records(const uint64_t* keys, int64_t n, const void* workspace, const uint64_t* header, uint64_t* records,
                           int64_t record_capacity, rsx_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Calibration tables (csrc/calibration.hip): the integers behind a reliability table, ECE / MCE, predicted-over-observed CTR and
+ * the same per group.  Opt-in, beside the rank statistics above (which it never changes).
+ * Definition, in integers.  positive: label > 0.5f.  valid: 0 <= p <= 1 by rsx_auc_exact_append's bit test (-0.0 is +0.0) and,
+ * when n_groups > 0, 0 <= g < n_groups with g = groups[i * group_stride]; an invalid example enters no table and is counted in
+ * invalid[0].  Of a valid example
+ *   bin  b = min(n_bins - 1, int(p * float(n_bins)))   one fp32 multiply, rounded to nearest, then truncated
+ *   q    = uint64(double(p) * 2^32)                    exact product, truncated; q <= 2^32
+ * and a table row is uint64[3] = {count, positives, sum of q}: bins[b] and group_table[g].  Sums of q hold 2^31 examples.  The
+ * host divides (metrics.calibration_from_table).  The words depend on neither batch sizes, batch order nor the order threads run
+ * in (integer atomics only).
+ *   rsx_calibration_update      one launch per eval batch for both tables (n_bins == 0: no bin table; n_groups == 0: no group
+ *                               table and `groups` is not read; one of the two must be asked for): at most 256 workgroups of 256
+ *                               threads stride over the examples; the bin table goes through an LDS histogram and one global
+ *                               integer atomic per non-zero entry, the group table takes 64-bit global integer atomics, the
+ *                               invalid count one atomic per workgroup.  The group column is read in place (int32, stride in
+ *                               elements >= 1).  Nothing is allocated, nothing synchronises and nothing is zeroed: the caller
+ *                               zeroes bins, group_table and invalid once.  n == 0 is a no-op.
+ *   rsx_calibration_max_bins    the cap on n_bins (1024; the least is 2)
+ *   rsx_calibration_max_groups  the cap on n_groups (2^22: the group table is 24 bytes per group)
+ * RSX_EINVAL (before any HIP call): a NULL pointer that the request needs, n / n_bins / n_groups < 0, both tables off,
+ * group_stride < 1 with a group table, a table not 8-byte aligned.  RSX_EUNSUPPORTED: n_bins == 1 or above its cap, n_groups
+ * above its cap, n > 2^31. */
+int rsx_calibration_max_bins(void);
+int rsx_calibration_max_groups(void);
+int rsx_calibration_update(const float* prob, const float* labels, const int32_t* groups, int64_t group_stride, int64_t n,
+                           int n_bins, int64_t n_groups, uint64_t* bins, uint64_t* group_table, uint64_t* invalid,
+                           rsx_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

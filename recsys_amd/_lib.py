@@ -434,6 +434,9 @@ _SIGS = {
     "rsx_auc_group_append": (_I, [_P, _P, _P, C.c_int64, C.c_int64, _I, _P, _P, _P]),
     "rsx_auc_group_finalize": (_I, [_P, C.c_int64, _I, _P, C.c_size_t, _P, _P]),
     "rsx_auc_group_records": (_I, [_P, C.c_int64, _P, _P, _P, C.c_int64, _P]),
+    "rsx_calibration_max_bins": (_I, []),
+    "rsx_calibration_max_groups": (_I, []),
+    "rsx_calibration_update": (_I, [_P, _P, _P, C.c_int64, C.c_int64, _I, C.c_int64, _P, _P, _P, _P]),
 }
 
 _lib = None

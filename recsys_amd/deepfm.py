@@ -226,6 +226,13 @@ def define_flags(p=None):
                    help="evaluate() also reports GAUC, the exact AUC of every group's examples weighted by the group's examples "
                         "(the DIN paper's per-user AUC): the source key of an embedding column, e.g. u_id with --feature_set "
                         "uid_iid or _c14 with the Criteo set.  Single replica only")
+    p.add_argument("--calibration_bins", type=int, default=0,
+                   help="evaluate() also reports ECE, MCE, PCOC (predicted over observed CTR) and NE (normalized entropy) from a "
+                        "reliability table of this many equal-width bins (2..1024), binned on the GPU; 0: off.  Single replica "
+                        "only")
+    p.add_argument("--calibration_key", default=None,
+                   help="evaluate() also reports GCE, the example-weighted |mean prediction - observed CTR| of every id of this "
+                        "column (--group_auc_key's names, e.g. _c16).  Single replica only")
     p.add_argument("--feature_set", default="criteo", choices=["criteo", "uid_iid"],
                    help="criteo: the 39-field pipeline of fm.py (BASELINE configs); uid_iid: deepfm.py as committed "
                         "(int64 u_id / i_id hashed into 500000 / 100000 buckets, int64 label)")
@@ -314,7 +321,9 @@ def run_main(model_fn, FLAGS, make_params_fn):
     config = RunConfig(save_checkpoints_steps=FLAGS.save_checkpoints_steps, keep_checkpoint_max=5,
                        log_step_count_steps=FLAGS.log_steps, adam_mode=FLAGS.adam_mode, optimizer=optimizer,
                        optimizer_hparams=optimizer_hparams, exact_auc=bool(getattr(FLAGS, "exact_auc", False)),
-                       group_auc_key=getattr(FLAGS, "group_auc_key", None) or None)
+                       group_auc_key=getattr(FLAGS, "group_auc_key", None) or None,
+                       calibration_bins=int(getattr(FLAGS, "calibration_bins", 0) or 0),
+                       calibration_key=getattr(FLAGS, "calibration_key", None) or None)
     est = Estimator(model_fn, FLAGS.model_dir, params, config)
     shard = None
     if FLAGS.mirror:

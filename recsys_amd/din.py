@@ -595,6 +595,13 @@ def define_flags():
     p.add_argument("--group_auc_key", default=None, choices=("i_id", "i_cate"),
                    help="evaluate() also reports GAUC, the exact AUC of every group's examples weighted by the group's examples: "
                         "per target item or per target category (the reference's schema has no user id).  Single replica only")
+    p.add_argument("--calibration_bins", type=int, default=0,
+                   help="evaluate() also reports ECE, MCE, PCOC (predicted over observed CTR) and NE (normalized entropy) from a "
+                        "reliability table of this many equal-width bins (2..1024), binned on the GPU; 0: off.  Single replica "
+                        "only")
+    p.add_argument("--calibration_key", default=None, choices=("i_id", "i_cate"),
+                   help="evaluate() also reports GCE, the example-weighted |mean prediction - observed CTR| per target item or "
+                        "per target category.  Single replica only")
     return p
 
 
@@ -618,7 +625,8 @@ def main(argv=None):
               "max_batch_size": FLAGS.batch_size, "hist_len": FLAGS.hist_len}
     cfg = RunConfig(save_checkpoints_steps=FLAGS.save_checkpoints_steps, keep_checkpoint_max=5,
                     log_step_count_steps=FLAGS.log_steps, exact_auc=FLAGS.exact_auc,
-                    group_auc_key=FLAGS.group_auc_key)
+                    group_auc_key=FLAGS.group_auc_key, calibration_bins=FLAGS.calibration_bins,
+                    calibration_key=FLAGS.calibration_key)
     est = Estimator(model_fn, FLAGS.model_dir, params, cfg)
     shard = None
     if FLAGS.mirror:

@@ -69,6 +69,12 @@ class RunConfig:
     # by the group's examples (the DIN paper's per-user AUC; metrics.GroupAUC).  The key of an embedding column of the layout
     # (Criteo scripts, --feature_set uid_iid: e.g. "u_id") or "i_id" / "i_cate" (din.py); None: everything as before.  Single replica
     group_auc_key: Optional[str] = None
+    # evaluate() also reports "ECE", "MCE", "PCOC" and "NE" from a reliability table of this many equal-width bins (0: off; 2..1024)
+    # and, with calibration_key (group_auc_key's names), "GCE" and "GCE_groups" from one (count, positives, sum of p) row per id of
+    # that column -- metrics.Calibration: one more launch per batch, one more device->host copy.  Both off: everything as before.
+    # Single replica
+    calibration_bins: int = 0
+    calibration_key: Optional[str] = None
 
 
 @dataclass
@@ -508,6 +514,7 @@ class Estimator:
 
     def __init__(self, model_fn, model_dir=None, params=None, config: Optional[RunConfig] = None):
         self._n_infer_graphs = 0
+        self.last_calibration = None      # the latest evaluate()'s full metrics.Calibration result (table, records), if asked for
         self.model_fn = model_fn
         self.model_dir = model_dir
         self.params = dict(params or {})
@@ -994,7 +1001,10 @@ class Estimator:
         RunConfig.exact_auc adds "AUC_exact" (metrics.ExactAUC: one more launch per batch, one sort and one more device->host
         copy at the end; nan, with a WARNING line, when a probability was outside [0, 1]); single replica only.
         RunConfig.group_auc_key adds "GAUC", "GAUC_groups" and "GAUC_skipped_examples" (metrics.GroupAUC: one more launch per
-        batch; at the end one sort, the header's copy, one records launch and the records' copy); single replica only."""
+        batch; at the end one sort, the header's copy, one records launch and the records' copy); single replica only.
+        RunConfig.calibration_bins adds "ECE", "MCE", "PCOC" and "NE" (NE from this call's loss), RunConfig.calibration_key "GCE"
+        and "GCE_groups" (metrics.Calibration: one more launch per batch for both, one more device->host copy at the end; nan,
+        with a WARNING line, when an example was invalid); the full result stays in `last_calibration`; single replica only."""
         self._check_consistent("evaluate")
         exact = bool(getattr(self.config, "exact_auc", False))
         if exact:                         # refused before the first batch is read
@@ -1003,6 +1013,12 @@ class Estimator:
         if gkey:                          # an unknown key and a second rank are refused before the first batch is read, too
             _metrics.check_group_auc_world(1 if self.store.dp is None else self.store.dp.world)
             group_of, group_bits = self._group_auc_source(gkey)
+        cbins, ckey = int(getattr(self.config, "calibration_bins", 0) or 0), getattr(self.config, "calibration_key", None)
+        cal = None                        # metrics.Calibration: a bad setting is refused here, before the first batch is read
+        if cbins or ckey:
+            _metrics.check_calibration_world(1 if self.store.dp is None else self.store.dp.world)
+            cal_group_of, cal_groups = self._group_column(ckey, "calibration_key") if ckey else (None, None)
+            cal = _metrics.Calibration(self.store.device, cbins or None, cal_groups)
         met = _metrics.EvalMetrics(self.store.device)
         ex = None                         # metrics.ExactAUC, sized by the first batch: the append launches follow met.update's
         ga = None                         # metrics.GroupAUC, likewise
@@ -1027,6 +1043,8 @@ class Estimator:
                         # the device copy of the batch that _infer_step just used (the graph's static buffer or the eager
                         # copy): ids[:, slot] is read in place, behind the forward on the same stream
                         ga.update(group_of(getattr(self, "_infer_features", None) or features), lab, prob)
+                    if cal is not None:   # the same device copy of the batch, the same stream
+                        cal.update(lab, prob, cal_group_of(getattr(self, "_infer_features", None) or features) if ckey else None)
                     n += 1
         finally:
             _close_iter(it)
@@ -1052,14 +1070,32 @@ class Estimator:
                 print("WARNING:group_auc_key %s: %d examples have a probability outside [0, 1] or not finite, or an id outside "
                       "[0, 2^%d); GAUC is nan" % (gkey, gr["invalid"], group_bits), flush=True)
             line += ", GAUC = %.7g" % res["GAUC"]
+        if cal is not None:
+            cr = self.last_calibration = cal.result(loss=res["loss"], per_group=True)
+            if cbins:
+                res.update({k: v for k, v in _metrics.calibration_reported(cr).items() if k in ("ECE", "MCE", "PCOC", "NE")})
+                line += ", ECE = %.7g, PCOC = %.7g, NE = %.7g" % (res["ECE"], res["PCOC"], res["NE"])
+            if ckey:
+                res["GCE"] = _metrics.group_calibration_reported(cr)["GCE"]
+                res["GCE_groups"] = cr["GCE_groups"]
+                line += ", GCE = %.7g" % res["GCE"]
+            if cr["invalid"] and self._is_chief():
+                print("WARNING:calibration: %d of %d examples have a probability outside [0, 1] or not finite%s; the calibration "
+                      "figures are nan" % (cr["invalid"], cr["invalid"] + cr["examples"],
+                                           ", or a %s id outside [0, %d)" % (ckey, cal_groups) if ckey else ""), flush=True)
         if self._is_chief():
             print(line, flush=True)
         return res
 
     def _group_auc_source(self, key):
-        """RunConfig.group_auc_key -> (features -> the batch's group ids, group_bits).  Criteo scripts and --feature_set uid_iid:
-        the key of an embedding column of the layout; the group is the column's table-local id, ids[:, slot] of the batch as it
-        is (host or device, no copy here).  din.py: i_id / i_cate."""
+        """RunConfig.group_auc_key -> (features -> the batch's group ids, group_bits)."""
+        group_of, n_rows = self._group_column(key, "group_auc_key")
+        return group_of, min(31, max(1, (n_rows - 1).bit_length()))
+
+    def _group_column(self, key, setting):
+        """The key of RunConfig.group_auc_key / calibration_key -> (features -> the batch's group ids, the column's row count).
+        Criteo scripts and --feature_set uid_iid: the key of an embedding column of the layout; the group is the column's
+        table-local id, ids[:, slot] of the batch as it is (host or device, no copy here).  din.py: i_id / i_cate."""
         cols = self.params.get("embedding_feature_columns")
         if cols is not None:
             from .feature_columns import CriteoLayout
@@ -1072,12 +1108,11 @@ class Estimator:
                     "i_cate": ("i_cate", int(self.params.get("n_cate", din.N_CATE)) + 1)}
             allowed = list(rows)
         if key not in rows:
-            raise _metrics.RsxError("group_auc_key %r is not a feature of this model; allowed: %s" % (key, ", ".join(allowed)))
+            raise _metrics.RsxError("%s %r is not a feature of this model; allowed: %s" % (setting, key, ", ".join(allowed)))
         where, n_rows = rows[key]
-        bits = min(31, max(1, (n_rows - 1).bit_length()))
         if cols is not None:
-            return (lambda features: features["ids"][:, where]), bits
-        return (lambda features: features[where]), bits
+            return (lambda features: features["ids"][:, where]), n_rows
+        return (lambda features: features[where]), n_rows
 
     def _is_chief(self):
         return self.store.dp is None or getattr(self.store.dp, "rank", 0) == 0

@@ -10,7 +10,10 @@ Opt-in beside it (RunConfig.exact_auc): `ExactAUC`, the exact tie-aware rank sta
 reference's serving client reports, deepfm/grpc_client.py:84) from a device-wide key sort (csrc/auc_exact.hip); `exact_auc_host`
 states its definition in numpy.  And beside that (RunConfig.group_auc_key): `GroupAUC`, the same statistic per group, weighted by the
 group's examples -- the DIN paper's GAUC (csrc/auc_group.hip); `group_auc_records_host` is its definition in numpy and
-`group_auc_from_records` the one place that divides."""
+`group_auc_from_records` the one place that divides.  Those three are rank statistics; whether a probability of 0.03 means 3 % is
+what `Calibration` answers (RunConfig.calibration_bins / calibration_key): a reliability table and a per-group table of (count,
+positives, fixed-point sum of p), one launch per batch (csrc/calibration.hip); `calibration_bins_host` / `calibration_groups_host`
+are their definitions in numpy and `calibration_from_table` (ECE, MCE, PCOC, NE) / `group_calibration_from_table` (GCE) divide."""
 import ctypes as C
 
 import numpy as np
@@ -407,4 +410,218 @@ class GroupAUC:
         res = group_auc_from_records(rec, self.header)
         if per_group:
             res["records"] = rec
+        return res
+
+
+# ---- calibration: reliability bins, ECE / MCE / PCOC / NE and the same per group (include/rsx.h rsx_calibration_*) -------------
+CALIBRATION_MIN_BINS = 2
+CALIBRATION_Q_ONE = 1 << 32             # the fixed-point 1.0 of q
+_NAN = float("nan")
+
+
+def _calibration_inputs(labels, prob):
+    y = np.ascontiguousarray(np.asarray(labels, np.float32).reshape(-1))
+    p = np.ascontiguousarray(np.asarray(prob, np.float32).reshape(-1))
+    if y.size != p.size:
+        raise ValueError("labels and predictions differ in size")
+    u = p.view(np.uint32).copy()
+    u[u == 0x80000000] = 0              # -0.0 is +0.0
+    return y > np.float32(0.5), u.view(np.float32), u <= 0x3F800000
+
+
+def calibration_bin_host(prob, n_bins):
+    """The bin of every VALID fp32 probability: min(N - 1, int32(p * float32(N))) -- one fp32 multiply, rounded to nearest, then
+    truncated.  The arithmetic is the definition: a p one ulp below k / N may land in bin k."""
+    p = np.asarray(prob, np.float32)
+    return np.minimum(np.int32(int(n_bins) - 1), (p * np.float32(int(n_bins))).astype(np.int32))
+
+
+def calibration_q_host(prob):
+    """The fixed-point form of every VALID fp32 probability: uint64(float64(p) * 2**32) -- the product is exact in fp64 and the
+    conversion truncates; q(1.0) = 2**32.  A 64-bit sum of q is good for 2^31 examples."""
+    return (np.asarray(prob, np.float32).astype(np.float64) * float(CALIBRATION_Q_ONE)).astype(np.uint64)
+
+
+def _calibration_rows(index, rows, pos, q):
+    table = np.zeros((rows, 3), np.int64)
+    np.add.at(table[:, 0], index, 1)
+    np.add.at(table[:, 1], index, pos.astype(np.int64))
+    np.add.at(table[:, 2], index, q.astype(np.int64))
+    return table
+
+
+def calibration_bins_host(labels, prob, n_bins):
+    """The documented definition of the bin table, in numpy.  An example is valid when 0 <= p <= 1 (exact_auc_keys_host's bit
+    test, -0.0 as +0.0) and positive when y > 0.5.
+    -> (table int64 [n_bins, 3] = (count, positives, q_sum) per bin, the number of invalid examples).  The q sums are 64-bit
+    integers, good for 2^31 examples."""
+    n_bins = int(n_bins)
+    if not CALIBRATION_MIN_BINS <= n_bins <= 1024:
+        raise ValueError("n_bins must be in 2..1024")
+    pos, p, valid = _calibration_inputs(labels, prob)
+    pos, p = pos[valid], p[valid]
+    return _calibration_rows(calibration_bin_host(p, n_bins), n_bins, pos, calibration_q_host(p)), int(valid.size - valid.sum())
+
+
+def calibration_groups_host(groups, labels, prob, n_groups):
+    """The documented definition of the group table, in numpy: an example is valid when its probability is (as above) and its
+    group id (any integer dtype, normalised by _group_ids_int32) lies in [0, n_groups).
+    -> (table int64 [n_groups, 3] = (count, positives, q_sum) per group, the number of invalid examples)"""
+    n_groups = int(n_groups)
+    if n_groups < 1:
+        raise ValueError("n_groups must be positive")
+    pos, p, valid = _calibration_inputs(labels, prob)
+    g = _group_ids_int32(groups).astype(np.int64)
+    if g.size != p.size:
+        raise ValueError("groups and predictions differ in size")
+    valid = valid & (g >= 0) & (g < n_groups)
+    pos, p, g = pos[valid], p[valid], g[valid]
+    return _calibration_rows(g, n_groups, pos, calibration_q_host(p)), int(valid.size - valid.sum())
+
+
+def _calibration_rows_as_ints(table):
+    t = np.asarray(table).reshape(-1, 3)
+    return [int(v) for v in t[:, 0]], [int(v) for v in t[:, 1]], [int(v) for v in t[:, 2]]
+
+
+def _exact_sum(a):
+    """The sum of non-negative int64 values as a Python integer, whatever its size: the 32-bit halves are summed apart."""
+    a = np.asarray(a, np.int64)
+    return (int((a >> 32).sum(dtype=np.int64)) << 32) + int((a & 0xFFFFFFFF).sum(dtype=np.int64))
+
+
+def calibration_from_table(table, invalid, loss=None):
+    """THE place that divides, and it divides Python integers (each quotient correctly rounded).  table: [N, 3] = (count,
+    positives, q_sum) per bin.  With n = sum(count), P = sum(positives), S = sum(q_sum), d_b = |q_sum_b - positives_b 2^32|:
+    ECE = sum_b d_b / (n 2^32); MCE = max over non-empty bins of d_b / (count_b 2^32); PCOC = S / (P 2^32) (nan when P == 0);
+    CTR = P / n; mean_prob = S / (n 2^32); NE = loss / H(CTR), H(c) = -(c ln c + (1 - c) ln(1 - c)) in Python floats (nan when
+    loss is None or CTR is 0 or 1).  Everything is nan when n == 0.
+    -> {"ECE", "MCE", "PCOC", "NE", "CTR", "mean_prob", "examples", "invalid"}"""
+    import math
+    cnt, pos, qs = _calibration_rows_as_ints(table)
+    n, P, S, one = sum(cnt), sum(pos), sum(qs), CALIBRATION_Q_ONE
+    res = {"ECE": _NAN, "MCE": _NAN, "PCOC": _NAN, "NE": _NAN, "CTR": _NAN, "mean_prob": _NAN, "examples": n,
+           "invalid": int(invalid)}
+    if n == 0:
+        return res
+    d = [abs(q - p * one) for p, q in zip(pos, qs)]
+    res["ECE"] = sum(d) / (n * one)
+    res["MCE"] = max(db / (c * one) for db, c in zip(d, cnt) if c)
+    res["PCOC"] = S / (P * one) if P else _NAN
+    res["CTR"] = ctr = P / n
+    res["mean_prob"] = S / (n * one)
+    if loss is not None and 0 < P < n:
+        res["NE"] = float(loss) / -(ctr * math.log(ctr) + (1.0 - ctr) * math.log(1.0 - ctr))
+    return res
+
+
+def group_calibration_from_table(table, invalid):
+    """The group table's figures, from Python integers: GCE = sum_g |q_sum_g - positives_g 2^32| / (n 2^32), the example-weighted
+    absolute calibration error of the groups (nan when n == 0); GCE_groups = the non-empty groups.
+    -> {"GCE", "GCE_groups", "examples", "invalid"}"""
+    t = np.asarray(table).reshape(-1, 3).astype(np.int64)
+    n, one = _exact_sum(t[:, 0]), CALIBRATION_Q_ONE
+    if t.size and int(t[:, 1].max()) >= 1 << 31:                     # positives_g 2^32 would leave int64: Python integers
+        d = sum(abs(int(q) - int(p) * one) for p, q in zip(t[:, 1], t[:, 2]))
+    else:                                 # per group in int64, the sum over the groups exactly (it may pass 2^63)
+        d = _exact_sum(np.abs(t[:, 2] - (t[:, 1] << 32)))
+    return {"GCE": d / (n * one) if n else _NAN, "GCE_groups": int(np.count_nonzero(t[:, 0])), "examples": n,
+            "invalid": int(invalid)}
+
+
+CALIBRATION_FIGURES = ("ECE", "MCE", "PCOC", "NE", "CTR", "mean_prob")
+
+
+def calibration_reported(res):
+    """What evaluate() reports: the figures of a stream without invalid examples, nan for every figure otherwise (as
+    exact_auc_reported).  -> {"ECE", "MCE", "PCOC", "NE", "CTR", "mean_prob"}"""
+    return {k: (_NAN if res["invalid"] else res[k]) for k in CALIBRATION_FIGURES}
+
+
+def group_calibration_reported(res):
+    """-> {"GCE"}: nan when any example was invalid."""
+    return {"GCE": _NAN if res["invalid"] else res["GCE"]}
+
+
+def check_calibration_world(world):
+    """The calibration settings are a single-replica evaluation, like exact_auc."""
+    if int(world) > 1:
+        raise RsxError("calibration: data-parallel evaluation is not supported (the ranks' tables would have to be summed "
+                       "together); evaluate on one replica")
+
+
+class Calibration:
+    """The calibration tables of one evaluate() call: one launch per batch (rsx_calibration_update, csrc/calibration.hip) adds
+    the batch to a bin table (n_bins in 2..rsx_calibration_max_bins()) and / or a group table (n_groups in
+    1..rsx_calibration_max_groups()); `result()` does ONE device->host copy.  Device state: 8 + 24 n_bins + 24 n_groups bytes,
+    zeroed once here; no workspace.  An example is invalid, for both tables, when its probability is outside [0, 1] or, with a
+    group table, its id outside [0, n_groups)."""
+
+    def __init__(self, device, n_bins=None, n_groups=None):
+        self.device = torch.device(device)
+        self.n_bins = 0 if n_bins is None else int(n_bins)
+        self.n_groups = 0 if n_groups is None else int(n_groups)
+        if n_bins is None and n_groups is None:
+            raise RsxError("calibration: give n_bins, n_groups or both")
+        if n_bins is not None and not CALIBRATION_MIN_BINS <= self.n_bins <= int(lib().rsx_calibration_max_bins()):
+            raise RsxError("calibration: n_bins %d is outside %d..%d"
+                           % (self.n_bins, CALIBRATION_MIN_BINS, int(lib().rsx_calibration_max_bins())))
+        if n_groups is not None and not 1 <= self.n_groups <= int(lib().rsx_calibration_max_groups()):
+            raise RsxError("calibration: n_groups %d is outside 1..%d (the group table is 24 bytes per group)"
+                           % (self.n_groups, int(lib().rsx_calibration_max_groups())))
+        # [0] invalid examples; [1 .. 1 + 3 n_bins) the bin table; then the group table
+        self.state = torch.zeros(1 + 3 * self.n_bins + 3 * self.n_groups, dtype=torch.int64, device=self.device)
+
+    _groups = GroupAUC._groups
+
+    def _floats(self, x):
+        if isinstance(x, torch.Tensor) and x.is_cuda and x.dtype == torch.float32 and x.is_contiguous():
+            return x                      # evaluate()'s tensors as they are: at batch 256 the host's work per batch is the cost
+        return GroupAUC._floats(self, x)
+
+    def update(self, labels, prob, groups=None):
+        """labels / prob / groups: device tensors or numpy arrays of B elements (any shape); groups (needed with a group table,
+        not read without one) may be a strided column view (ids[:, slot]), which is passed through in place.  No host
+        synchronisation."""
+        y, p = self._floats(labels), self._floats(prob)
+        n = int(p.numel())
+        if y.numel() != n:
+            raise ValueError("labels and predictions differ in size")
+        g, stride = None, 1
+        if self.n_groups:
+            if groups is None:
+                raise ValueError("calibration: this object has a group table; update() needs the group ids")
+            g, stride = self._groups(groups)
+            if g.numel() != n:
+                raise ValueError("groups, labels and predictions differ in size")
+        if n == 0:
+            return
+        base = self.state.data_ptr()
+        check(lib().rsx_calibration_update(C.c_void_p(p.data_ptr()), C.c_void_p(y.data_ptr()),
+                                           C.c_void_p(g.data_ptr() if g is not None else None), stride, n, self.n_bins,
+                                           self.n_groups, C.c_void_p(base + 8 if self.n_bins else None),
+                                           C.c_void_p(base + 8 + 24 * self.n_bins if self.n_groups else None), C.c_void_p(base),
+                                           C.c_void_p(torch.cuda.current_stream().cuda_stream)), "rsx_calibration_update")
+
+    def result(self, loss=None, per_group=False):
+        """ONE device->host copy of the state.  With a bin table: calibration_from_table's dict (NE from `loss`) and "table", the
+        int64 [n_bins, 3] array; with a group table: group_calibration_from_table's keys and, when per_group, "records": int64
+        [G', 4] rows (g, count, positives, q_sum) of the non-empty groups in ascending g.  Updates may continue afterwards."""
+        s = self.state.cpu().numpy()
+        invalid, res = int(s[0]), {}
+        if self.n_groups:
+            gt = s[1 + 3 * self.n_bins:].reshape(self.n_groups, 3)
+            live = np.flatnonzero(gt[:, 0])
+            rec = np.concatenate([live.astype(np.int64).reshape(-1, 1), gt[live]], axis=1)
+            res.update(group_calibration_from_table(rec[:, 1:], invalid))
+            if per_group:
+                res["records"] = rec
+        if self.n_bins:
+            table = s[1:1 + 3 * self.n_bins].reshape(self.n_bins, 3).copy()
+            bins = calibration_from_table(table, invalid, loss)
+            if self.n_groups and bins["examples"] != res["examples"]:
+                raise RsxError("calibration: the bin table holds %d examples, the group table %d"
+                               % (bins["examples"], res["examples"]))
+            res.update(bins)
+            res["table"] = table
         return res
