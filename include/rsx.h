@@ -612,7 +612,9 @@ int rsx_tower_reduce_dw_jobs(const rsx_dw_reduce_job* jobs_h, int njobs, rsx_str
  * weights in LDS, weight gradients as per-workgroup partials summed in workgroup order by a second launch (deterministic).
  * Replaces the 2L + 2 launches of rsx_tower_fwd_layer / rsx_tower_head / rsx_tower_bwd_layer for such a tower; the dropout
  * masks are the same counter-based hash (layer index l, element b * widths[l] + c), sums are associated differently.
- * Envelope (rsx_mlp_nobn_supported): 1 <= L <= 3, K0 and widths multiples of 4 and <= 112, 16-byte aligned arrays.
+ * Envelope (rsx_mlp_nobn_supported): 1 <= L <= 3, K0 and widths multiples of 4 and <= 112, and the kernel's LDS layout
+ * (every layer's padded weights + the activation tiles) within the CU's 160 KB -- (96; 100, 52, 20) and (112; 112, 64, 32)
+ * fit, (96; 100, 100, 20) and (112; 112, 112) do not: such a tower takes the launch-per-layer kernels.  16-byte aligned arrays.
  * dW[l] [K_l, widths[l]], db[l] [widths[l]], dwout [widths[L-1]], dbout [1], loss [1] = sum(ce) / B, prob [B],
  * dX [B, K0] = d loss / d X, gs0 (nullable) [B] = d loss / d s0; loss_scale = 1 / (B * replicas) scales every gradient.
  * workspace: rsx_mlp_nobn_workspace_floats(B, K0, widths, L) floats.

@@ -374,11 +374,50 @@ extern "C" size_t rsx_mlp_nobn_workspace_floats(int B, int K0, const int32_t* wi
   return nwg * per;
 }
 
+// The kernel's LDS layout (MlpArgs: o*, ld*, lds_floats) for a shape inside the width envelope -> its size in bytes.  The ONE
+// place that knows it: rsx_mlp_nobn_supported asks it whether the layout fits, mlp_build launches with it.
+static size_t mlp_lds_layout(int K0, const int32_t* widths, int L, MlpArgs& p) {
+  int off = 0, K = K0, wmax = K0;
+  for (int l = 0; l < MLP_MAX_L; ++l) {
+    p.oW[l] = 0; p.ldw[l] = 0; p.oB[l] = 0;
+    if (l >= L) continue;
+    const int N = widths[l];
+    p.ldw[l] = up16(N) + 4;
+    p.oW[l] = off; off += up16(K) * p.ldw[l];
+    wmax = N > wmax ? N : wmax;
+    K = N;
+  }
+  const int NL = widths[L - 1];
+  for (int l = 0; l < L; ++l) { p.oB[l] = off; off += (widths[l] + 3) & ~3; }
+  p.oWout = off; off += (NL + 3) & ~3;
+  // activation tiles: stride = (width + 1 rounded to 16) + 8 floats (covers the ones-row feature of the dW operand; == 8 mod 16)
+  for (int l = 0; l <= MLP_MAX_L; ++l) {
+    p.oIn[l] = 0; p.ldin[l] = 0;
+    if (l < MLP_MAX_L) p.oG[l] = 0;
+  }
+  for (int l = 0; l <= L; ++l) {
+    const int wdt = l == 0 ? K0 : widths[l - 1];
+    p.ldin[l] = up16(wdt + 1) + 8;
+    p.oIn[l] = off; off += 16 * p.ldin[l];
+    if (l > 0) { p.oG[l - 1] = off; off += 16 * p.ldin[l]; }
+  }
+  p.ldda = up16(wmax) + 8;
+  p.oDa[0] = off; off += 16 * p.ldda;
+  p.oDa[1] = off; off += 16 * p.ldda;
+  p.oRow = off; off += 32;
+  p.NL = NL; p.oInL = p.oIn[L]; p.ldinL = p.ldin[L]; p.oGL = p.oG[L - 1];
+  p.lds_floats = (off + 3) & ~3;
+  return (size_t)p.lds_floats * sizeof(float);
+}
+
+constexpr size_t MLP_MAX_LDS = 160 * 1024;     // the CU's LDS on gfx950
+
 extern "C" int rsx_mlp_nobn_supported(int K0, const int32_t* widths, int L) {
   if (!widths || L <= 0 || L > MLP_MAX_L || K0 <= 0 || K0 > MLP_MAX_W || (K0 & 3)) return 0;
   for (int l = 0; l < L; ++l)
     if (widths[l] <= 0 || widths[l] > MLP_MAX_W || (widths[l] & 3)) return 0;
-  return 1;
+  MlpArgs p;
+  return mlp_lds_layout(K0, widths, L, p) <= MLP_MAX_LDS ? 1 : 0;
 }
 
 static int mlp_build(const rsx_mlp_step* s, MlpArgs& p, MlpRed& r, size_t& lds_bytes, unsigned& e4_total) {
@@ -396,27 +435,24 @@ static int mlp_build(const rsx_mlp_step* s, MlpArgs& p, MlpRed& r, size_t& lds_b
   p.seed = s->seed; p.rate = s->dropout_rate; p.loss_scale = s->loss_scale;
   p.B = B; p.K0 = K0; p.L = L;
   const int nwg = (B + 15) / 16;
-  int off = 0, K = K0;
+  const size_t lds = mlp_lds_layout(K0, s->widths, L, p);      // (within MLP_MAX_LDS: rsx_mlp_nobn_supported said so)
+  int K = K0;
   long long po = 0;
   unsigned e4 = 0;
-  int wmax = K0;
   for (int l = 0; l < MLP_MAX_L; ++l) {
     const bool on = l < L;
     const int N = on ? s->widths[l] : 4;
     p.W[l] = on ? s->W[l] : nullptr; p.b[l] = on ? s->b[l] : nullptr; p.mask[l] = on ? s->masks[l] : nullptr;
     p.N[l] = N;
     r.dW[l] = on ? s->dW[l] : nullptr; r.db[l] = on ? s->db[l] : nullptr; r.K[l] = K; r.N[l] = N;
-    p.oW[l] = 0; p.ldw[l] = 0; p.oB[l] = 0; p.poff[l] = 0; r.poff[l] = 0;
+    p.poff[l] = 0; r.poff[l] = 0;
     if (!on) { r.e4_end[l] = 0xFFFFFFFFu; continue; }
     if (!p.W[l] || !p.b[l] || !r.dW[l] || !r.db[l]) return RSX_EINVAL;
     if (!al16(p.W[l])) return RSX_EUNSUPPORTED;
-    p.ldw[l] = up16(N) + 4;
-    p.oW[l] = off; off += up16(K) * p.ldw[l];
     p.poff[l] = po; r.poff[l] = po;
     po += (long long)nwg * up16(K + 1) * up16(N);
     e4 += (unsigned)(up16(K + 1) * up16(N) / 4);
     r.e4_end[l] = e4;
-    wmax = N > wmax ? N : wmax;
     K = N;
   }
   const int NL = s->widths[L - 1];
@@ -425,31 +461,9 @@ static int mlp_build(const rsx_mlp_step* s, MlpArgs& p, MlpRed& r, size_t& lds_b
   p.poffL = po;
   e4 += (unsigned)(p.NPo / 4);
   r.e4_last = e4;
-  for (int l = 0; l < L; ++l) { p.oB[l] = off; off += (s->widths[l] + 3) & ~3; }
-  p.oWout = off; off += (NL + 3) & ~3;
-  // activation tiles: stride = (width + 1 rounded to 16) + 8 floats (covers the ones-row feature of the dW operand; == 8 mod 16)
-  K = K0;
-  for (int l = 0; l <= MLP_MAX_L; ++l) {
-    p.oIn[l] = 0; p.ldin[l] = 0;
-    if (l < MLP_MAX_L) p.oG[l] = 0;
-  }
-  for (int l = 0; l <= L; ++l) {
-    const int wdt = l == 0 ? K0 : s->widths[l - 1];
-    p.ldin[l] = up16(wdt + 1) + 8;
-    p.oIn[l] = off; off += 16 * p.ldin[l];
-    if (l > 0) { p.oG[l - 1] = off; off += 16 * p.ldin[l]; }
-  }
-  p.ldda = up16(wmax) + 8;
-  p.oDa[0] = off; off += 16 * p.ldda;
-  p.oDa[1] = off; off += 16 * p.ldda;
-  p.oRow = off; off += 32;
-  p.NL = NL; p.oInL = p.oIn[L]; p.ldinL = p.ldin[L]; p.oGL = p.oG[L - 1];
-  p.lds_floats = (off + 3) & ~3;
-  const size_t lds = (size_t)p.lds_floats * sizeof(float);
-  if (lds > 160 * 1024) return RSX_EUNSUPPORTED;
   if (lds > 64 * 1024) {
     static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(mlp_nobn_step_k),
-                                                       hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+                                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)MLP_MAX_LDS);
     if (attr != hipSuccess) return RSX_EUNSUPPORTED;
   }
   r.part = s->workspace; r.dwout = s->dwout; r.dbout = s->dbout; r.loss = s->loss;

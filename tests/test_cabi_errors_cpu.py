@@ -176,6 +176,14 @@ def test_round4_entry_points_reject_bad_arguments(L):
     assert L.rsx_mlp_nobn_supported(98, w, 3) == 0                                   # input width not a multiple of 4
     assert L.rsx_mlp_nobn_supported(96, (C.c_int32 * 3)(128, 52, 20), 3) == 0        # a layer wider than 112
     assert L.rsx_mlp_nobn_workspace_floats(1024, 96, w, 3) == 64 * (112 * 112 + 112 * 64 + 64 * 32 + 24)
+    # ... and a layout inside the width envelope whose LDS image (every layer's padded weights + the activation tiles) exceeds the
+    # CU's 160 KB is NOT supported: FusedTower then takes the launch-per-layer kernels instead of failing at its first step
+    for k0, ws, fits in ((96, (100, 100, 20), 0),        # 172 608 B
+                         (112, (112, 112), 0),           # 164 288 B
+                         (112, (112, 112, 112), 0),      # 234 112 B
+                         (96, (100, 52, 20), 1),         # 137 856 B
+                         (112, (112, 64, 32), 1)):       # 152 640 B
+        assert L.rsx_mlp_nobn_supported(k0, (C.c_int32 * len(ws))(*ws), len(ws)) == fits, (k0, ws)
     assert L.rsx_mlp_nobn_train_step(None, None) == EINVAL
     ms = _lib.MlpStep()
     ms.B, ms.K0, ms.L = 16, 96, 3

@@ -13,6 +13,7 @@ import numpy as np
 import pytest
 import torch
 
+from tests import tower_check as tc
 from tests import tower_ref as tr
 
 pytestmark = pytest.mark.gpu
@@ -50,13 +51,6 @@ def _train(case, P, tw, dev, masks, **extra):
                 grads={k: P[k].grad.clone() for k in P.params}, a=[a[:case.B].clone() for a in tw.a])
 
 
-def _figure(got, ref):
-    """max|got - ref| / max|ref| (the absolute error where the reference is exactly zero)"""
-    m = float(ref.abs().max()) if ref.numel() else 0.0
-    e = float((got.double() - ref.double()).abs().max()) if ref.numel() else 0.0
-    return e / m if m > 0.0 else e
-
-
 # Bounds wider than the defaults, per (case, tensor), as a multiple of max|reference|: 4 x the figure of the plain fp32 torch
 # restatement for that tensor and case (profiles/tower_bn_fp64_errors.txt, rounded down) -- never taken from the kernels' own error.
 # Each is a tensor of a B >= 1030 case with one to three elements, of thousands, that are small themselves (so rtol gives them
@@ -76,49 +70,13 @@ LOOSER = {
 
 
 def _close(cid, name, got, ref, rtol, atol_rel=None, atol=None):
-    """None, or the reason `got` misses `ref` (so that one run reports every tensor of a case)."""
-    ref = ref.reshape(got.shape)
-    m = float(ref.abs().max())
-    if (cid, name) in LOOSER:
-        atol = LOOSER[(cid, name)] * m
-    elif atol is None:
-        atol = atol_rel * m if m > 0.0 else 1e-7       # (reference exactly zero -- B = 1: 1e-7 absolute)
-    try:
-        np.testing.assert_allclose(got.cpu().numpy(), ref.cpu().numpy(), rtol=rtol, atol=atol, err_msg=f"{cid} {name}")
-    except AssertionError as e:
-        return str(e)
-    return None
+    return tc.close(LOOSER, cid, name, got, ref, rtol, atol_rel=atol_rel, atol=atol)
 
 
 def _check_train(case, d, out, masks, tag):
-    """out (a train_step's outputs) against the fp64 restatement with the same masks; prints the error table first."""
-    use_s0, use_s1, _, _ = tr.head_flags(case)
-    r = tr.run_ref(case, d, masks=masks, device="cuda")
-    assert r.head_near == 0                                             # (the seed rule, tests/test_tower_ref_cpu.py)
-    if sum(r.near):                                                     # pre-activations inside TAU: the kernel's gates there
-        r = tr.run_ref(case, d, masks=masks, kernel_a=out["a"], device="cuda")
-    for l, n in enumerate(case.widths):
-        assert r.near[l] <= tr.GATE_CAP * case.B * n, (case.id, l, r.near[l])
-    f32 = tr.run_ref(case, d, masks=masks, gates=r.gates, dtype=torch.float32, device="cuda")
-    pairs = [("loss", out["loss"][0], r.loss, f32.loss), ("prob", out["prob"], r.prob, f32.prob), ("dX", out["dX"], r.dX, f32.dX)]
-    if use_s0:
-        pairs.append(("gs0", out["gs0"], r.gs0, f32.gs0))
-    if use_s1:
-        pairs.append(("gs1", out["gs1"], r.gs1, f32.gs1))
-    pairs += [(f"a{l}", out["a"][l], r.a[l], f32.a[l]) for l in range(len(case.widths))]
-    pairs += [(k, out["grads"][k], r.grads[k], f32.grads[k]) for k in out["grads"]]
-    for name, got, ref, ref32 in pairs:
-        print("TOWER_BN_ERR %-14s %-12s kernel %.3e  fp32-torch %.3e" % (tag, name, _figure(got.reshape(ref.shape), ref),
-                                                                        _figure(ref32, ref)))
-    cid = tag.split("/")[0]                                             # (the variants of a case run the same step: one bound)
-    bad = [_close(cid, "loss", out["loss"][0], r.loss, rtol=1e-5, atol=0.0), _close(cid, "prob", out["prob"], r.prob, rtol=1e-5, atol=1e-6)]
-    bad += [_close(cid, name, got, ref, rtol=1e-4, atol_rel=2e-7) for name, got, ref, _ in pairs[2:]]
-    bad = [b for b in bad if b is not None]
-    for b in bad:
-        print("TOWER_BN_FAIL %s: %s" % (tag, " ".join(b.split()[:40])))
-    assert not bad, "\n".join(bad)
-    assert set(out["grads"]) == set(r.grads)
-    return r
+    """out (a train_step's outputs) against the fp64 restatement with the same masks (tests/tower_check.py: the scheme shared
+    with the batch-norm-free tower's tests); prints the error table first."""
+    return tc.check_train(case, d, out, masks, tag, label="TOWER_BN", looser=LOOSER)
 
 
 def _case_inputs(cid):
@@ -194,7 +152,7 @@ def test_infer_matches_fp64_and_leaves_training_alone(cid):
         r = tr.run_ref(case, d, train=False, device="cuda")
         r32 = tr.run_ref(case, d, train=False, dtype=torch.float32, device="cuda")
     for name, got, ref, ref32 in (("loss", loss[0], r.loss, r32.loss), ("prob", prob, r.prob, r32.prob)):
-        print("TOWER_BN_ERR %-14s %-12s kernel %.3e  fp32-torch %.3e" % (cid + "/infer", name, _figure(got, ref), _figure(ref32, ref)))
+        print("TOWER_BN_ERR %-14s %-12s kernel %.3e  fp32-torch %.3e" % (cid + "/infer", name, tc.figure(got, ref), tc.figure(ref32, ref)))
     bad = [b for b in (_close(cid + "/infer", "loss", loss[0], r.loss, rtol=1e-5, atol=0.0),
                        _close(cid + "/infer", "prob", prob, r.prob, rtol=1e-5, atol=1e-6)) if b is not None]
     assert not bad, "\n".join(bad)

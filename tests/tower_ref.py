@@ -1,6 +1,8 @@
 """Reference of the batch-norm tower for tests/test_gpu_tower_bn.py and tests/test_tower_ref_cpu.py: the case table, the
 inputs of a case, a plain torch autograd restatement of one FusedTower.train_step / infer (any dtype, any device) and the
 documented dropout hash on the host.  Nothing here touches the HIP library, so the CPU suite can import it.
+The batch-norm-free tower (Case.bn = False: tests/test_gpu_tower_nobn.py, tests/test_tower_nobn_ref_cpu.py) is the same
+restatement without the moments; its tables (NOBN_CASES, FUSED_CASES) are at the end of this file.
 
 The step restated (csrc/tower.hip; deepfm/deepfm.py:100-112 with fm/fm.py:146-149):
     per layer  a = relu(h @ W + b);  h = BN_train(a) * mask / (1 - rate)      (batch moments, biased variance, eps 1e-3)
@@ -31,8 +33,14 @@ HASH_SEED = 0xD1AD    # the `seed` argument of train_step in every test
 #   nos0    out.W [3] / out.b with s1 and relu2 but WITHOUT s0 (and so without c0)
 #   (tail: the dcn form's out.W has this many entries behind the tower's n_last -- dcn.py: the cross output's weights.  The cases
 #   here carry DCN_TAIL = 5 untouched ones; tests/test_gpu_cross_forms.py's rider cases carry the cross layers' dim.)
+#   din     (bn = False only) z = s0 + h @ mlp.Wout + mlp.bout, no relus, no out.W; s0 absent when the case's s0 is False  (din.py)
 DCN_TAIL = 5
-Case = namedtuple("Case", "id B k0 widths rate head replicas base_seed tail", defaults=(DCN_TAIL,))
+# bn = False: L x [dense(relu) -> dropout] (FusedTower(batch_norm=False)), variables mlp.W{i} / mlp.b{i} / mlp.Wout / mlp.bout.
+# fused: the case is run by the one-launch form (csrc/mlp_fused.hip) and follows ITS seed rule (case_seed).
+# pad = (l, n): layer l stores widths[l] units of which only the first n exist (din.py stores 50 as 52): the columns n.. of W_l
+# and b_l and the rows n.. of the next weight matrix are zero.
+Case = namedtuple("Case", "id B k0 widths rate head replicas base_seed tail bn s0 fused pad",
+                  defaults=(DCN_TAIL, True, True, False, None))
 
 # The kernel every layer takes, derived from the conditions in rsx_tower_fwd_layer / rsx_tower_head /
 # rsx_tower_bwd_layer_defer (csrc/tower.hip), default knobs.  Abbreviations:
@@ -97,6 +105,12 @@ INFER_CASES = ("default", "fix", "splitA", "b4k")
 def param_shapes(case):
     """{name: shape} of the case's DenseArena (the names of deepfm.py / dcn.py)."""
     shapes, d = {}, case.k0
+    if not case.bn:
+        for i, n in enumerate(case.widths):
+            shapes[f"mlp.W{i}"], shapes[f"mlp.b{i}"] = (d, n), (n,)
+            d = n
+        shapes["mlp.Wout"], shapes["mlp.bout"] = (d, 1), (1,)
+        return shapes
     for i, n in enumerate(case.widths):
         shapes[f"dnn.W{i}"], shapes[f"dnn.b{i}"] = (d, n), (n,)
         shapes[f"dnn.gamma{i}"], shapes[f"dnn.beta{i}"] = (n,), (n,)
@@ -113,6 +127,8 @@ def param_shapes(case):
 
 def head_flags(case):
     """(uses s0, uses s1, relu0, relu2)"""
+    if case.head == "din":
+        return (bool(case.s0), False, False, False)
     return {"deepfm": (True, True, True, True), "dcn": (True, False, False, False), "nos0": (False, True, False, True)}[case.head]
 
 
@@ -134,6 +150,11 @@ def draw(case, seed):
         else:
             v = 0.3 * torch.randn(shp, generator=g)
         vals[k] = v
+    if case.pad is not None:        # (after the draw: the values of every other entry are those of the unpadded case)
+        l, n = case.pad
+        vals[f"mlp.W{l}"][:, n:] = 0.0
+        vals[f"mlp.b{l}"][n:] = 0.0
+        vals[f"mlp.W{l + 1}" if l + 1 < len(case.widths) else "mlp.Wout"][n:] = 0.0
     B = case.B
     d = dict(vals=vals, X=torch.randn(B, case.k0, generator=g), s0=0.2 * torch.randn(B, generator=g),
              s1=0.2 * torch.randn(B, generator=g), y=(torch.rand(B, generator=g) < 0.4).float())
@@ -159,8 +180,9 @@ def run_ref(case, d, *, train=True, masks=None, kernel_a=None, gates=None, dtype
     r = Ref()
     r.pre, r.a, r.gates, r.near = [], [], [], []
     h = X
+    pfx = "dnn" if case.bn else "mlp"
     for l, n in enumerate(case.widths):
-        pre = h @ W[f"dnn.W{l}"] + W[f"dnn.b{l}"]
+        pre = h @ W[f"{pfx}.W{l}"] + W[f"{pfx}.b{l}"]
         if not train:
             a = torch.relu(pre)           # (the forward is continuous at the kink: no gate to choose)
             gate = None
@@ -170,6 +192,8 @@ def run_ref(case, d, *, train=True, masks=None, kernel_a=None, gates=None, dtype
                     gate = gates[l].to(device=device, dtype=dtype)
                 else:
                     near = pre.abs() <= TAU
+                    if not case.bn:       # (a pad unit's pre-activation is exactly 0: gate 0 on both sides, not a kink)
+                        near &= pre != 0
                     own = pre > 0
                     gate = (torch.where(near, kernel_a[l].to(device) > 0, own) if kernel_a is not None else own).to(dtype)
                     r.near.append(int(near.sum()))
@@ -177,7 +201,11 @@ def run_ref(case, d, *, train=True, masks=None, kernel_a=None, gates=None, dtype
         r.pre.append(pre.detach())
         r.a.append(a.detach())
         r.gates.append(gate)
-        if train:
+        if not case.bn:           # no moments, train or eval
+            h = a
+            if train and case.rate > 0.0:
+                h = h * to(masks[l]) / (1.0 - case.rate)
+        elif train:
             mean = a.mean(0, keepdim=True)
             var = ((a - mean) ** 2).mean(0, keepdim=True)
             h = (a - mean) * torch.rsqrt(var + BN_EPS) * W[f"dnn.gamma{l}"] + W[f"dnn.beta{l}"]
@@ -186,7 +214,11 @@ def run_ref(case, d, *, train=True, masks=None, kernel_a=None, gates=None, dtype
         else:
             h = a * W[f"dnn.gamma{l}"] / np.sqrt(1.0 + BN_EPS) + W[f"dnn.beta{l}"]
     n_last = case.widths[-1]
-    if case.head == "dcn":
+    if case.head == "din":
+        u = h @ W["mlp.Wout"].reshape(-1) + W["mlp.bout"]
+        z = (s0 + u) if use_s0 else u
+        v0 = None
+    elif case.head == "dcn":
         u = h @ W["out.W"].reshape(-1)[:n_last] + W["out.b"]
         z = s0 + u
         v0 = None
@@ -215,14 +247,26 @@ def run_ref(case, d, *, train=True, masks=None, kernel_a=None, gates=None, dtype
 
 @functools.lru_cache(maxsize=None)
 def case_seed(case, device="cpu"):
-    """The first of the case's SEED_TRIES consecutive seeds whose fp64 reference alone has no head row on a relu kink."""
-    for seed in range(case.base_seed, case.base_seed + SEED_TRIES):
+    """The first of the case's SEED_TRIES consecutive seeds whose fp64 reference alone has no head row on a relu kink.
+    A fused case (the one-launch form keeps its activations in LDS: no kernel gate to borrow): the first of FUSED_SEED_TRIES
+    consecutive seeds with, in addition, no pre-activation with 0 < |pre| <= TAU at all, under the masks the test runs with."""
+    tries = FUSED_SEED_TRIES if case.fused else SEED_TRIES
+    for seed in range(case.base_seed, case.base_seed + tries):
         d = draw(case, seed)
         with torch.no_grad():
-            r = run_ref(case, d, masks=d["masks"], device=device, backward=False)
-        if r.head_near == 0:
+            r = run_ref(case, d, masks=case_masks(case, d), device=device, backward=False)
+        if r.head_near == 0 and (not case.fused or sum(r.near) == 0):
             return seed
-    raise AssertionError(f"{case.id}: every seed {case.base_seed}..+{SEED_TRIES - 1} puts a head row within {TAU} of a relu kink")
+    raise AssertionError(f"{case.id}: every seed {case.base_seed}..+{tries - 1} puts a head row within {TAU} of a relu kink"
+                         + (" or a pre-activation inside it" if case.fused else ""))
+
+
+def case_masks(case, d):
+    """The keep masks of the case's main comparison: the drawn ones, or the documented hash's for a case that runs with
+    masks=None (FUSED_HASH: its seed rule has to hold under THOSE masks)."""
+    if case.rate > 0.0 and case.id in FUSED_HASH:
+        return hash_masks(case.B, case.widths, case.rate)
+    return d["masks"]
 
 
 # ------------------------------------------------------------------------------------------ the dropout hash on the host
@@ -248,3 +292,80 @@ def hash_masks(B, widths, rate, step=RNG_STEP, seed=HASH_SEED, layer0=0):
         h = hash32((np.arange(B * n, dtype=np.uint64) & np.uint64(M)) ^ key)
         out.append(torch.from_numpy((h >= thresh).astype(np.float32).reshape(B, n)))
     return out
+
+
+# ------------------------------------------------------------------------------------------ the batch-norm-free tower
+FUSED_SEED_TRIES = 32
+
+
+def _nobn(cid, B, k0, widths, rate, replicas, base_seed, s0=True, fused=False, pad=None):
+    return Case(cid, B, k0, widths, rate, "din", replicas, base_seed, DCN_TAIL, False, s0, fused, pad)
+
+
+# The launch-per-layer form of a batch-norm-free tower (gamma == nullptr in csrc/tower.hip).  Dispatch does not depend on BN
+# (rsx_tower_fwd_layer / rsx_tower_bwd_layer_defer: only B, K and N enter), so the derivations are those of CASES above; what is
+# new is the branch every kernel takes inside: h = a * mask / (1 - rate) instead of the normalisation, no statistics rows.
+NOBN_CASES = [
+    # L0 K=20 N=12, L1 K=12 N=7: fwd small; bwd small<false> one-tile, L1 with N % 4 != 0; head<4>, last width no multiple of 4
+    _nobn("tiny", 3, 20, (12, 7), 0.0, 1, 3100),
+    # the same kernels with two row tiles (17 = 16 + 1), dropout
+    _nobn("tiny17", 17, 20, (12, 7), 0.5, 1, 3200, s0=False),
+    # B = 1: without BN nothing cancels -- the gradients are NOT zero; kernels as tiny
+    _nobn("b1", 1, 20, (12, 8), 0.0, 1, 3300),
+    # L0 K=260 N=36: fwd small; bwd small<false> GROUPED (17 * 16 = 272 >= 256 d(input) tiles, N % 4 == 0, N <= 128); head<4>
+    _nobn("grouped", 250, 260, (36,), 0.3, 1, 3400),
+    # din.py's own tower (stored widths) launch per layer.  B = 1024: L0 K=96, L1 K=100, L2 K=52 all < 256 -> fwd small x3;
+    # bwd small<true> (sb = 2) grouped (N % 4 == 0, N <= 128) x3; head<4>; 3 layers: the reduce jobs are deferred
+    _nobn("din1024", 1024, 96, (100, 52, 20), 0.5, 2, 3500, pad=(1, 50)),
+    # B = 1000 < 1024: fwd small x3; bwd small<false> (sb = 1, direct dW): L0 (6 * 63 = 378 >= 256 d(input) tiles) and L1
+    # (7 * 63 = 441) grouped, L2 (4 * 63 = 252 < 256) one-tile; ragged last row tile (1000 = 62 * 16 + 8); head<4>
+    _nobn("din1000", 1000, 96, (100, 52, 20), 0.5, 1, 3600, pad=(1, 50)),
+    # L0 K=260 N=100: fwd big<2>; bwd big<5,8>, K % 16 != 0
+    # L1 K=100 N=64:  fwd small; bwd small<true> grouped (sb = 3)
+    # L2 K=64  N=200: fwd small; bwd small<true> one-tile (N > 128)
+    # L3 K=200 N=7:   fwd small; bwd small<true> one-tile (N % 4 != 0); head<4>
+    # 4 layers: the reduces are deferred, jobs of both kinds in ONE rsx_tower_reduce_dw_jobs launch
+    _nobn("splitA", 1030, 260, (100, 64, 200, 7), 0.5, 1, 3700),
+    # L0 K=256 N=48: fwd big<1>; bwd big<5,4>.  L1 K=48 N=256: fwd small; bwd small<true> one-tile.  L2 K=256 N=60: fwd big<1>;
+    # bwd big<5,4>; head<4>.  replicas 2
+    _nobn("splitB", 1030, 256, (48, 256, 60), 0.5, 2, 3800, s0=False),
+    # B >= 4096: L0 K=64 N=128 fwd big<2>, bwd big<2,8>; L1 K=128 N=192 fwd big<3>, bwd small<true> one-tile (sb = 9); L2 K=192
+    # N=256 fwd big<4>, bwd small<true> one-tile; L3 K=256 N=68 fwd big<2>, bwd big<5,8>; L4 K=68 N=36 fwd big<1>, bwd big<2,4>;
+    # head<4>.  5 layers: nothing deferred, both reduce kernels launched directly
+    _nobn("b4k", 4100, 64, (128, 192, 256, 68, 36), 0.5, 1, 3900),
+    # inside the one-launch form's width envelope but 172 608 B of LDS: default forms, no override -- rsx_mlp_nobn_supported says
+    # no and the tower takes the launch-per-layer kernels: fwd small x3, bwd small<false> one-tile (6 * 4, 7 * 4, 7 * 4 < 256), head<4>
+    _nobn("fallback", 64, 96, (100, 100, 20), 0.5, 1, 4000),
+]
+NOBN_CASE = {c.id: c for c in NOBN_CASES}
+NOBN_HASH_CASES = ("tiny17", "din1024", "splitA", "splitB", "b4k")     # the big kernels and one small case
+NOBN_INFER_CASES = ("grouped", "splitA", "b4k")
+
+# The one-launch form (csrc/mlp_fused.hip): one 16-row tile per workgroup, nwg = ceil(B / 16).  nks = ceil(K / 16) k-steps of
+# tile_fwd (K = the layer's input width) and of tile_bwd (K = the layer's OWN width N: d(input) = da . W^T); an odd nks takes the
+# tail MFMA group behind the two-accumulator loop, nks = 1 the tail alone.  LDS = mlp_lds_layout's bytes (> 64 KB: the opt-in
+# dynamic size).  mlp_reduce_body<32> keeps 32 partials in flight: nwg = 33 is the first batch with a second trip.
+FUSED_CASES = [
+    # L = 1; fwd nks 1 (tail only), bwd nks 1; N = 4 < 16 (one partly filled column tile); nwg = 1 with ONE live row; 5 KB
+    _nobn("f_b1", 1, 16, (4,), 0.0, 1, 5000, fused=True),
+    # L = 1; fwd nks 2 (even, no tail), bwd nks 4; N = 64 a multiple of 16; nwg = 1 full; 24 KB
+    _nobn("f_l1", 16, 32, (64,), 0.3, 2, 5100, fused=True, s0=False),
+    # L = 2; fwd nks 3 (odd) and 3, bwd nks 3 and 3; nwg = 2 with a one-row last tile; 50 880 B: under 64 KB
+    _nobn("f_48", 17, 48, (48, 48), 0.5, 1, 5200, fused=True),
+    # L = 2; fwd nks 7 (odd) and 7, bwd nks 7 (N = 112) and 1 (N = 4); 250 = 15 * 16 + 10; hash dropout; 101 KB
+    _nobn("f_112", 250, 112, (112, 4), 0.5, 1, 5300, fused=True, s0=False),
+    # L = 3; N = 4 everywhere, K0 = 16; nwg = 33: the reduce's second trip holds ONE partial
+    _nobn("f_33", 520, 16, (4, 4, 4), 0.0, 2, 5400, fused=True),
+    # din.py's storage: L = 3; fwd nks 6, 7, 4 and bwd nks 7, 4, 2; N = 100, 52, 20 (none a multiple of 16); 137 856 B; the pad
+    # units 50, 51 of layer 1.  B = 1030: nwg = 65 (three trips of the reduce, the last with one partial), explicit masks
+    _nobn("f_din", 1030, 96, (100, 52, 20), 0.5, 2, 5500, fused=True, pad=(1, 50)),
+    # the same at nwg = 33 with hash dropout and without s0
+    _nobn("f_din520", 520, 96, (100, 52, 20), 0.5, 1, 5600, fused=True, s0=False, pad=(1, 50)),
+    # the largest admitted layout worth running: 152 640 B; fwd nks 7, 7, 4 and bwd nks 7, 4, 2; N = 112 and 64 multiples of 16
+    _nobn("f_max", 1030, 112, (112, 64, 32), 0.0, 1, 5700, fused=True),
+]
+FUSED_CASE = {c.id: c for c in FUSED_CASES}
+FUSED_HASH = ("f_112", "f_din520")             # run with masks=None: the reference takes hash_masks(..., layer0=0)
+# the seeds case_seed picks for them (tests/test_tower_nobn_ref_cpu.py pins them: a change of the draw or of the rule shows)
+FUSED_SEEDS = {"f_b1": 5000, "f_l1": 5100, "f_48": 5200, "f_112": 5303, "f_33": 5400, "f_din": 5500, "f_din520": 5601,
+               "f_max": 5702}
