@@ -1750,6 +1750,42 @@ int rsx_calibration_update(const float* prob, const float* labels, const int32_t
                            int n_bins, int64_t n_groups, uint64_t* bins, uint64_t* group_table, uint64_t* invalid,
                            rsx_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Isotonic calibration (csrc/calibration_map.hip): the equal-mass table a monotone correction is fitted from, and the correction
+ * applied to probabilities.  Opt-in, beside everything above (which it never changes).
+ * The table, in integers.  ks[0 .. V) are the SORTED valid keys of rsx_auc_exact_append, (bits(p) << 1) | positive -- what
+ * rsx_auc_exact_finalize leaves at the front of its key buffer, V = P + N of its output; the padding keys behind them are not
+ * read.  h(i) = the position of the first key with i's score (key >> 1); the bin of position i is b(i) = (h(i) * M) / V in 64-bit
+ * integers, 2 <= M <= rsx_calibration_max_bins(): all examples of one score share a bin, bins ascend with the score, bins may be
+ * empty (heavy ties, M > V).  Row b of table[M, 3] is uint64 {count, positives, sum of q}, q = uint64(double(p) * 2^32) with p the
+ * fp32 whose bits are key >> 1: rsx_calibration_update's row and q, so metrics.calibration_from_table reduces this table too.  The
+ * host fits (metrics.isotonic_from_table, the one place that divides): pool-adjacent-violators over the non-empty rows as blocks
+ * (C, S, Q), pooling the last two while S_prev C_last > S_last C_prev (equal means stay apart); knots x = fp32(Q / (C 2^32)),
+ * y = fp32(S / C); neighbours whose x collide in fp32 are pooled too.  1 <= K <= M knots, x strictly increasing, y non-decreasing.
+ * The map, in fp32 (no FMA contraction, IEEE division).  p outside [0, 1] by rsx_auc_exact_append's bit test: returned unchanged,
+ * bit for bit (-0.0 counts as +0.0).  p <= x[0]: y[0].  p >= x[K-1]: y[K-1].  Otherwise, j the largest index with x[j] <= p:
+ *   t = (p - x[j]) / (x[j+1] - x[j]);  o = y[j] + t * (y[j+1] - y[j]);  out = min(o, y[j+1])
+ * The minimum keeps the map monotone across a knot whatever the last rounding does.  metrics.isotonic_apply_host is the same
+ * arithmetic in numpy, bit for bit.
+ *   rsx_calibration_quantile_table  ONE launch, one workgroup per bin: both ends of the bin's position range by binary search
+ *                                   over the sorted keys, a strided read of the range (16-byte loads), a fixed-order reduction,
+ *                                   one lane stores the row.  It writes every word of table[n_bins, 3]; no workspace, no atomics,
+ *                                   no allocation, no synchronisation, nothing zeroed by the caller; n_valid == 0 writes zeros.
+ *                                   PRECONDITION: sorted_keys[0 .. n_valid) ascend (it is not checked).  With all scores equal one
+ *                                   workgroup reads every key: slow, correct (DESIGN.md section 11c has the measured price).
+ *   rsx_calibrate_apply             ONE launch over prob_in[0 .. n) -> prob_out[0 .. n) (prob_out may EQUAL prob_in; no other
+ *                                   overlap): the knots staged in LDS once per workgroup (8 KiB at 1024), a binary search and the
+ *                                   five operations per element, a bounded grid; 16-byte loads and stores where prob_in and
+ *                                   prob_out share their offset within 16 bytes, a scalar head and tail for the rest (any element
+ *                                   offset works).  x is NOT checked for order (metrics.IsotonicMap does that).  Capturable:
+ *                                   nothing is allocated, nothing synchronises.  n == 0 is a no-op.
+ * RSX_EINVAL (before any HIP call).  quantile_table: a NULL pointer, n_valid < 0 or above rsx_auc_exact_max_keys(), n_bins outside
+ * [2, rsx_calibration_max_bins()], sorted_keys not 16-byte or table not 8-byte aligned.  apply: a NULL pointer, n < 0, n_knots
+ * outside [1, 1024], a pointer that is not 4-byte aligned. */
+int rsx_calibration_quantile_table(const uint32_t* sorted_keys, int64_t n_valid, int n_bins, uint64_t* table, rsx_stream_t stream);
+int rsx_calibrate_apply(const float* x, const float* y, int n_knots, const float* prob_in, float* prob_out, int64_t n,
+                        rsx_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

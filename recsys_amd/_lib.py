@@ -437,6 +437,8 @@ _SIGS = {
     "rsx_calibration_max_bins": (_I, []),
     "rsx_calibration_max_groups": (_I, []),
     "rsx_calibration_update": (_I, [_P, _P, _P, C.c_int64, C.c_int64, _I, C.c_int64, _P, _P, _P, _P]),
+    "rsx_calibration_quantile_table": (_I, [_P, C.c_int64, _I, _P, _P]),
+    "rsx_calibrate_apply": (_I, [_P, _P, _I, _P, _P, C.c_int64, _P]),
 }
 
 _lib = None

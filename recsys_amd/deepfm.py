@@ -233,6 +233,17 @@ def define_flags(p=None):
     p.add_argument("--calibration_key", default=None,
                    help="evaluate() also reports GCE, the example-weighted |mean prediction - observed CTR| of every id of this "
                         "column (--group_auc_key's names, e.g. _c16).  Single replica only")
+    p.add_argument("--calibration_fit", type=int, default=0,
+                   help="evaluate() also fits an isotonic calibration map from an equal-mass table of this many bins (2..1024) over "
+                        "the evaluation's sorted scores, reduced on the GPU, and writes <model_dir>/calibration-<global_step>.json; "
+                        "0: off.  Single replica only")
+    p.add_argument("--calibration_apply", type=lambda s: s.lower() in ("1", "true", "yes"), default=False,
+                   help="evaluate() also reports ECE_cal, MCE_cal and PCOC_cal: the figures of the probabilities mapped through the "
+                        "calibration map of the current global step (needs --calibration_bins; never together with "
+                        "--calibration_fit).  Single replica only")
+    p.add_argument("--export_calibration", default="auto", choices=("auto", "off", "require"),
+                   help="--task_type export: auto puts the calibration map of the exported global step into the bundle "
+                        "(calibration.json) when there is one, off never does, require fails when there is none")
     p.add_argument("--feature_set", default="criteo", choices=["criteo", "uid_iid"],
                    help="criteo: the 39-field pipeline of fm.py (BASELINE configs); uid_iid: deepfm.py as committed "
                         "(int64 u_id / i_id hashed into 500000 / 100000 buckets, int64 label)")
@@ -323,7 +334,9 @@ def run_main(model_fn, FLAGS, make_params_fn):
                        optimizer_hparams=optimizer_hparams, exact_auc=bool(getattr(FLAGS, "exact_auc", False)),
                        group_auc_key=getattr(FLAGS, "group_auc_key", None) or None,
                        calibration_bins=int(getattr(FLAGS, "calibration_bins", 0) or 0),
-                       calibration_key=getattr(FLAGS, "calibration_key", None) or None)
+                       calibration_key=getattr(FLAGS, "calibration_key", None) or None,
+                       calibration_fit=int(getattr(FLAGS, "calibration_fit", 0) or 0),
+                       calibration_apply=bool(getattr(FLAGS, "calibration_apply", False)))
     est = Estimator(model_fn, FLAGS.model_dir, params, config)
     shard = None
     if FLAGS.mirror:
@@ -355,7 +368,8 @@ def run_main(model_fn, FLAGS, make_params_fn):
                 break
         return out
     if FLAGS.task_type == "export":
-        return est.export_savedmodel(FLAGS.export_path, table_dtype=FLAGS.export_table_dtype)
+        return est.export_savedmodel(FLAGS.export_path, table_dtype=FLAGS.export_table_dtype,
+                                     calibration=getattr(FLAGS, "export_calibration", "auto"))
     raise SystemExit("unknown --task_type %r" % FLAGS.task_type)
 
 

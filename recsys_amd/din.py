@@ -602,6 +602,17 @@ def define_flags():
     p.add_argument("--calibration_key", default=None, choices=("i_id", "i_cate"),
                    help="evaluate() also reports GCE, the example-weighted |mean prediction - observed CTR| per target item or "
                         "per target category.  Single replica only")
+    p.add_argument("--calibration_fit", type=int, default=0,
+                   help="evaluate() also fits an isotonic calibration map from an equal-mass table of this many bins (2..1024) over "
+                        "the evaluation's sorted scores, reduced on the GPU, and writes <model_dir>/calibration-<global_step>.json; "
+                        "0: off.  Single replica only")
+    p.add_argument("--calibration_apply", type=lambda s: s.lower() in ("1", "true", "yes"), default=False,
+                   help="evaluate() also reports ECE_cal, MCE_cal and PCOC_cal: the figures of the probabilities mapped through the "
+                        "calibration map of the current global step (needs --calibration_bins; never together with "
+                        "--calibration_fit).  Single replica only")
+    p.add_argument("--export_calibration", default="auto", choices=("auto", "off", "require"),
+                   help="--task_type export: auto puts the calibration map of the exported global step into the bundle "
+                        "(calibration.json) when there is one, off never does, require fails when there is none")
     return p
 
 
@@ -626,7 +637,8 @@ def main(argv=None):
     cfg = RunConfig(save_checkpoints_steps=FLAGS.save_checkpoints_steps, keep_checkpoint_max=5,
                     log_step_count_steps=FLAGS.log_steps, exact_auc=FLAGS.exact_auc,
                     group_auc_key=FLAGS.group_auc_key, calibration_bins=FLAGS.calibration_bins,
-                    calibration_key=FLAGS.calibration_key)
+                    calibration_key=FLAGS.calibration_key, calibration_fit=FLAGS.calibration_fit,
+                    calibration_apply=FLAGS.calibration_apply)
     est = Estimator(model_fn, FLAGS.model_dir, params, cfg)
     shard = None
     if FLAGS.mirror:
@@ -641,7 +653,8 @@ def main(argv=None):
     if FLAGS.task_type == "eval":
         return est.evaluate(lambda: input_fn(eval_files, FLAGS.batch_size, 1, False, FLAGS.hist_len, shard, True), steps=FLAGS.eval_steps)
     if FLAGS.task_type == "export":     # (only when asked: the reference's deepfm.py exports after every task, its main falls through)
-        return est.export_savedmodel(FLAGS.export_path, table_dtype=FLAGS.export_table_dtype)
+        return est.export_savedmodel(FLAGS.export_path, table_dtype=FLAGS.export_table_dtype,
+                                     calibration=FLAGS.export_calibration)
     return list(zip(range(10), est.predict(lambda: input_fn(eval_files, FLAGS.batch_size, 1, False, FLAGS.hist_len))))
 
 

@@ -75,6 +75,14 @@ class RunConfig:
     # Single replica
     calibration_bins: int = 0
     calibration_key: Optional[str] = None
+    # calibration_fit = M (2..1024; 0: off): evaluate() fits an isotonic map (metrics.IsotonicMap) from an equal-mass table of M
+    # bins over this call's sorted (score, label) keys, keeps it in Estimator.last_calibration_map, writes
+    # <model_dir>/calibration-<global_step>.json and reports "calibration_knots".  calibration_apply (needs calibration_bins, and a
+    # map of the current global_step): evaluate() also reports "ECE_cal", "MCE_cal" and "PCOC_cal", the figures of the mapped
+    # probabilities (one more launch of rsx_calibrate_apply and of the bin table per batch).  Never both in one call: the figures
+    # would be in-sample.  Both off: everything as before.  Single replica
+    calibration_fit: int = 0
+    calibration_apply: bool = False
 
 
 @dataclass
@@ -515,6 +523,7 @@ class Estimator:
     def __init__(self, model_fn, model_dir=None, params=None, config: Optional[RunConfig] = None):
         self._n_infer_graphs = 0
         self.last_calibration = None      # the latest evaluate()'s full metrics.Calibration result (table, records), if asked for
+        self.last_calibration_map = None  # the metrics.IsotonicMap the latest evaluate() with calibration_fit fitted (table, ece)
         self.model_fn = model_fn
         self.model_dir = model_dir
         self.params = dict(params or {})
@@ -1004,7 +1013,16 @@ class Estimator:
         batch; at the end one sort, the header's copy, one records launch and the records' copy); single replica only.
         RunConfig.calibration_bins adds "ECE", "MCE", "PCOC" and "NE" (NE from this call's loss), RunConfig.calibration_key "GCE"
         and "GCE_groups" (metrics.Calibration: one more launch per batch for both, one more device->host copy at the end; nan,
-        with a WARNING line, when an example was invalid); the full result stays in `last_calibration`; single replica only."""
+        with a WARNING line, when an example was invalid); the full result stays in `last_calibration`; single replica only.
+        RunConfig.calibration_fit = M fits an isotonic map from this call's examples (an ExactAUC is kept whether or not exact_auc
+        is set; after the last batch ONE launch of rsx_calibration_quantile_table and a copy of 24 M bytes, then
+        metrics.isotonic_from_table on the host): `last_calibration_map`, <model_dir>/calibration-<global_step>.json (the chief
+        writes it, temporary name and rename), "calibration_knots" in the result (0 when the fit is refused: an invalid example,
+        or no positive or no negative -- one WARNING line, no file).  RunConfig.calibration_apply maps every batch's prob through
+        the map of the current global_step into a second buffer (rsx_calibrate_apply, same stream) and adds "ECE_cal", "MCE_cal"
+        and "PCOC_cal" from a second bin table; every other key keeps its raw value.  Refused before the first batch is read:
+        calibration_apply without calibration_bins or without a map of this step, both settings together, M outside 2..1024, a
+        second rank.  A logloss / NE of the mapped probabilities is out of scope."""
         self._check_consistent("evaluate")
         exact = bool(getattr(self.config, "exact_auc", False))
         if exact:                         # refused before the first batch is read
@@ -1019,6 +1037,26 @@ class Estimator:
             _metrics.check_calibration_world(1 if self.store.dp is None else self.store.dp.world)
             cal_group_of, cal_groups = self._group_column(ckey, "calibration_key") if ckey else (None, None)
             cal = _metrics.Calibration(self.store.device, cbins or None, cal_groups)
+        cfit, capply = int(getattr(self.config, "calibration_fit", 0) or 0), bool(getattr(self.config, "calibration_apply", False))
+        cmap = cal2 = cbuf = None         # calibration_apply: the Calibrator, the mapped probabilities' bin table and buffer
+        if cfit or capply:                # refused here, before the first batch is read
+            _metrics.check_calibration_map_world(1 if self.store.dp is None else self.store.dp.world)
+            if cfit and capply:
+                raise _metrics.RsxError("calibration_fit and calibration_apply in one evaluate() would report in-sample figures: "
+                                        "fit on one evaluation, apply in another")
+            if cfit and not _metrics.CALIBRATION_MIN_BINS <= cfit <= 1024:
+                raise _metrics.RsxError("calibration_fit %d is outside %d..1024" % (cfit, _metrics.CALIBRATION_MIN_BINS))
+            if capply:
+                if not cbins:
+                    raise _metrics.RsxError("calibration_apply needs calibration_bins: ECE_cal is a figure of that table")
+                step = self._calibration_step()
+                m = self.calibration_map_for_step(step)
+                if m is None:
+                    raise _metrics.RsxError("calibration_apply: no calibration map for global step %d (neither last_calibration_map "
+                                            "nor %s); run evaluate() with calibration_fit first"
+                                            % (step, self._calibration_path(step) or "a model_dir"))
+                cmap = _metrics.Calibrator(self.store.device, m)
+                cal2 = _metrics.Calibration(self.store.device, cbins)
         met = _metrics.EvalMetrics(self.store.device)
         ex = None                         # metrics.ExactAUC, sized by the first batch: the append launches follow met.update's
         ga = None                         # metrics.GroupAUC, likewise
@@ -1031,7 +1069,7 @@ class Estimator:
                         break
                     prob, loss, lab = self._infer_step(features, labels, ModeKeys.EVAL)
                     met.update(lab, prob, loss)
-                    if exact:
+                    if exact or cfit:
                         if ex is None:
                             ex = _metrics.ExactAUC(self.store.device,
                                                    None if steps is None else max(1, int(steps) * int(prob.numel())))
@@ -1045,6 +1083,11 @@ class Estimator:
                         ga.update(group_of(getattr(self, "_infer_features", None) or features), lab, prob)
                     if cal is not None:   # the same device copy of the batch, the same stream
                         cal.update(lab, prob, cal_group_of(getattr(self, "_infer_features", None) or features) if ckey else None)
+                    if cmap is not None:  # into a buffer of its own (prob may be the graph's static output), the same stream
+                        p1 = prob if prob.dtype == torch.float32 and prob.is_contiguous() else prob.to(torch.float32).contiguous()
+                        if cbuf is None or cbuf.numel() != p1.numel():      # (the last batch of a stream may be a partial one)
+                            cbuf = torch.empty(p1.numel(), dtype=torch.float32, device=p1.device)
+                        cal2.update(lab, cmap.apply(p1, out=cbuf))
                     n += 1
         finally:
             _close_iter(it)
@@ -1054,8 +1097,10 @@ class Estimator:
         res = {"AUC": res["AUC"], "Accuracy": res["Accuracy"], "loss": res["loss"], "global_step": self.global_step}
         line = ("INFO:Saving dict for global step %d: AUC = %.7g, Accuracy = %.7g, global_step = %d, loss = %.7g"
                 % (res["global_step"], res["AUC"], res["Accuracy"], res["global_step"], res["loss"]))
+        if exact or cfit:
+            ex = ex or _metrics.ExactAUC(self.store.device, 1)
+            xr = ex.result()
         if exact:
-            xr = (ex or _metrics.ExactAUC(self.store.device, 1)).result()
             res["AUC_exact"] = _metrics.exact_auc_reported(xr)
             if xr["invalid"] and self._is_chief():
                 print("WARNING:exact_auc: %d of %d probabilities are outside [0, 1] or not finite; AUC_exact is nan"
@@ -1083,9 +1128,70 @@ class Estimator:
                 print("WARNING:calibration: %d of %d examples have a probability outside [0, 1] or not finite%s; the calibration "
                       "figures are nan" % (cr["invalid"], cr["invalid"] + cr["examples"],
                                            ", or a %s id outside [0, %d)" % (ckey, cal_groups) if ckey else ""), flush=True)
+        if cal2 is not None:
+            c2 = cal2.result()
+            rep = _metrics.calibration_reported(c2)
+            res.update({"ECE_cal": rep["ECE"], "MCE_cal": rep["MCE"], "PCOC_cal": rep["PCOC"]})
+            line += ", ECE_cal = %.7g, PCOC_cal = %.7g" % (res["ECE_cal"], res["PCOC_cal"])
         if self._is_chief():
             print(line, flush=True)
+        if cfit:
+            res["calibration_knots"] = self._fit_calibration_map(ex, xr, cfit)
         return res
+
+    def _script_name(self):
+        return self.model_fn.__module__.rsplit(".", 1)[-1]
+
+    def _calibration_path(self, step):
+        return os.path.join(self.model_dir, "calibration-%d.json" % int(step)) if self.model_dir else None
+
+    def _calibration_step(self):
+        """The global_step the next evaluate() / export runs at, known without reading a batch: the restored variables', or the
+        latest checkpoint's while the variables are not built yet."""
+        if self.store.built:
+            self._maybe_restore()
+            return int(self.global_step)
+        from . import checkpoint
+        import re
+        p = checkpoint.latest(self.model_dir) if self.model_dir else None
+        return int(re.search(r"model\.ckpt-(\d+)\.pt$", p).group(1)) if p else 0
+
+    def calibration_map_for_step(self, step=None):
+        """The metrics.IsotonicMap of `step` (default: the current one): last_calibration_map when it is of that step, else
+        <model_dir>/calibration-<step>.json, else None.  A map of another step or another script is never taken."""
+        step = self._calibration_step() if step is None else int(step)
+        m = self.last_calibration_map
+        if m is not None and m.global_step == step and m.script == self._script_name():
+            return m
+        path = self._calibration_path(step)
+        if path and os.path.isfile(path):
+            m = _metrics.IsotonicMap.load(path)
+            if m.global_step == step and m.script == self._script_name():
+                return m
+        return None
+
+    def _fit_calibration_map(self, ex, xr, bins):
+        """calibration_fit's tail: the equal-mass table of ex's sorted keys -> the map, last_calibration_map, the file.
+        -> the number of knots (0: refused)."""
+        V, P = xr["positives"] + xr["negatives"], xr["positives"]
+        if xr["invalid"] or P == 0 or xr["negatives"] == 0:
+            if self._is_chief():
+                why = ("%d of %d probabilities are outside [0, 1] or not finite" % (xr["invalid"], xr["invalid"] + V)
+                       if xr["invalid"] else "the %d examples hold %d positives and %d negatives" % (V, P, xr["negatives"]))
+                print("WARNING:calibration_fit: no map is fitted: %s" % why, flush=True)
+            return 0
+        table = ex.quantile_table(bins)
+        x, y = _metrics.isotonic_from_table(table)
+        m = _metrics.IsotonicMap(x, y, bins=bins, examples=V, positives=P, global_step=self.global_step,
+                                 script=self._script_name(), table=table, ece=_metrics.calibration_from_table(table, 0)["ECE"])
+        self.last_calibration_map = m
+        path = self._calibration_path(m.global_step)
+        if path and self._is_chief():
+            os.makedirs(self.model_dir, exist_ok=True)
+            m.save(path)
+        if self._is_chief():
+            print("INFO:calibration map: K = %d, V = %d, P = %d, path = %s" % (m.knots, V, P, path), flush=True)
+        return m.knots
 
     def _group_auc_source(self, key):
         """RunConfig.group_auc_key -> (features -> the batch's group ids, group_bits)."""
@@ -1167,15 +1273,18 @@ class Estimator:
         return {"prob": np.concatenate(out) if out else np.zeros(0, np.float32)}
 
 
-    def export_savedmodel(self, export_dir_base, table_dtype="float32"):
+    def export_savedmodel(self, export_dir_base, table_dtype="float32", calibration="auto"):
         """Estimator.export_savedmodel (deepfm/deepfm.py:220-234): the latest checkpoint of model_dir as a serving bundle
         `<export_dir_base>/<unix seconds>/` = model.json + variables.npz (recsys_amd.serving: the variables in fp32, no
         optimizer slots or state), written under a temporary name and renamed when complete.  -> the directory (the chief's
         under data parallelism; None on the other ranks).  serving.Predictor.load() serves it.
         table_dtype "bfloat16" / "float16" (--export_table_dtype): the embedding tables are rounded to that dtype and stored
-        in it (a format_version 2 bundle); opt-in, it changes the probabilities."""
+        in it (a format_version 2 bundle); opt-in, it changes the probabilities.
+        calibration (--export_calibration): "auto" puts calibration.json (the metrics.IsotonicMap of the exported global_step:
+        last_calibration_map, else <model_dir>/calibration-<step>.json) beside the two files when there is one; "off" never;
+        "require" raises when there is none.  A map of another step is never taken."""
         from . import serving
-        return serving.export_estimator(self, export_dir_base, table_dtype=table_dtype)
+        return serving.export_estimator(self, export_dir_base, table_dtype=table_dtype, calibration=calibration)
 
 
 class _LaunchThread:

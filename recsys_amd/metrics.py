@@ -13,7 +13,11 @@ group's examples -- the DIN paper's GAUC (csrc/auc_group.hip); `group_auc_record
 `group_auc_from_records` the one place that divides.  Those three are rank statistics; whether a probability of 0.03 means 3 % is
 what `Calibration` answers (RunConfig.calibration_bins / calibration_key): a reliability table and a per-group table of (count,
 positives, fixed-point sum of p), one launch per batch (csrc/calibration.hip); `calibration_bins_host` / `calibration_groups_host`
-are their definitions in numpy and `calibration_from_table` (ECE, MCE, PCOC, NE) / `group_calibration_from_table` (GCE) divide."""
+are their definitions in numpy and `calibration_from_table` (ECE, MCE, PCOC, NE) / `group_calibration_from_table` (GCE) divide.
+What to do about a miscalibrated model is isotonic regression (RunConfig.calibration_fit / calibration_apply,
+csrc/calibration_map.hip): `ExactAUC.quantile_table` reduces the sorted keys to an equal-mass table, `isotonic_from_table` fits the
+knots from it in Python integers, `IsotonicMap` carries them (JSON, fp32 bit patterns) and `Calibrator` applies them on the device;
+`quantile_table_host` / `isotonic_apply_host` are the definitions in numpy."""
 import ctypes as C
 
 import numpy as np
@@ -164,6 +168,7 @@ class ExactAUC:
         # [0..3] finalize's {U2, P, N, invalid}; [4] the invalid examples the append launches counted
         self.out = torch.zeros(5, dtype=torch.int64, device=self.device)
         self.workspace = None
+        self.sorted_valid = None          # V = P + N of the latest result() while the buffer still holds its sorted keys
 
     def _as_device(self, x):
         if not isinstance(x, torch.Tensor):
@@ -191,6 +196,7 @@ class ExactAUC:
                                          C.c_void_p(self.out.data_ptr() + 8 * 4),
                                          C.c_void_p(torch.cuda.current_stream().cuda_stream)), "rsx_auc_exact_append")
         self.count = need
+        self.sorted_valid = None
 
     def result(self):
         """-> {"AUC_exact", "u2", "positives", "negatives", "invalid"}; one finalize, ONE device->host copy.  The key buffer keeps
@@ -205,7 +211,25 @@ class ExactAUC:
         if s[3] != s[4] or s[1] + s[2] + s[3] != self.count:
             raise RsxError("exact_auc: the sorted keys hold %d positives, %d negatives and %d invalid examples of %d; the append "
                            "launches counted %d invalid" % (s[1], s[2], s[3], self.count, s[4]))
+        self.sorted_valid = s[1] + s[2]
         return exact_auc_from_counts(s[0], s[1], s[2], s[3])
+
+    def quantile_table(self, n_bins):
+        """The equal-mass, tie-aware table of the examples result() has sorted (quantile_table_host's, integer for integer):
+        int64 [n_bins, 3] = (count, positives, q_sum).  Call it after result() and before the next update(); ONE launch
+        (rsx_calibration_quantile_table, no workspace) and ONE device->host copy of 24 n_bins bytes."""
+        n_bins = int(n_bins)
+        if not CALIBRATION_MIN_BINS <= n_bins <= int(lib().rsx_calibration_max_bins()):
+            raise RsxError("quantile_table: n_bins %d is outside %d..%d"
+                           % (n_bins, CALIBRATION_MIN_BINS, int(lib().rsx_calibration_max_bins())))
+        if self.sorted_valid is None:
+            raise RsxError("quantile_table: call result() first (it sorts the keys), and again after any further update()")
+        table = torch.empty(3 * n_bins, dtype=torch.int64, device=self.device)
+        check(lib().rsx_calibration_quantile_table(C.c_void_p(self.keys.data_ptr()), self.sorted_valid, n_bins,
+                                                   C.c_void_p(table.data_ptr()),
+                                                   C.c_void_p(torch.cuda.current_stream().cuda_stream)),
+              "rsx_calibration_quantile_table")
+        return table.cpu().numpy().reshape(n_bins, 3)
 
 
 # ---- GAUC: the exact AUC per group, weighted by the group's examples (include/rsx.h rsx_auc_group_*) ---------------------------
@@ -625,3 +649,221 @@ class Calibration:
             res.update(bins)
             res["table"] = table
         return res
+
+
+# ---- isotonic calibration: equal-mass table, the fit and the map (include/rsx.h rsx_calibration_quantile_table, --------------
+# ---- rsx_calibrate_apply) ---------------------------------------------------------------------------------------------------
+ISOTONIC_MAX_KNOTS = 1024
+ISOTONIC_FORMAT = "recsys_amd.isotonic_map.v1"
+
+
+def _check_quantile_bins(n_bins):
+    n_bins = int(n_bins)
+    if not CALIBRATION_MIN_BINS <= n_bins <= 1024:
+        raise ValueError("n_bins must be in 2..1024")
+    return n_bins
+
+
+def quantile_table_host(labels, prob, n_bins):
+    """The documented definition of the equal-mass, tie-aware table, in numpy.  ks = the sorted valid keys of
+    exact_auc_keys_host, V of them; h(i) = the position of the first key with i's score; bin b(i) = (h(i) * M) // V in 64-bit
+    integers.  All examples of one score share a bin, bins ascend with the score and may be empty.
+    -> table int64 [n_bins, 3] = (count, positives, q_sum), calibration_bins_host's row and q."""
+    M = _check_quantile_bins(n_bins)
+    keys = exact_auc_keys_host(labels, prob)
+    ks = np.sort(keys[keys != EXACT_AUC_PAD])
+    V = int(ks.size)
+    if V == 0:
+        return np.zeros((M, 3), np.int64)
+    score = ks >> np.uint32(1)
+    head = np.ones(V, bool)
+    head[1:] = score[1:] != score[:-1]
+    h = np.maximum.accumulate(np.where(head, np.arange(V, dtype=np.int64), 0))
+    b = (h * M) // V
+    p = np.ascontiguousarray(score.astype(np.uint32)).view(np.float32)
+    return _calibration_rows(b, M, (ks & np.uint32(1)) != 0, calibration_q_host(p))
+
+
+def _isotonic_knot(block):
+    c, s, q = block
+    return float(np.float32(q / (c << 32))), float(np.float32(s / c))
+
+
+def isotonic_from_table(table):
+    """THE place that divides: the isotonic fit of a (count, positives, q_sum) table, over Python integers.  The non-empty rows,
+    in order, are pushed as blocks (C, S, Q); while the last two violate STRICTLY -- S_prev C_last > S_last C_prev -- they are
+    replaced by their sum (pool-adjacent-violators on a stack; equal means stay apart).  Knots x = float32(Q / (C << 32)),
+    y = float32(S / C), true division of integers and then the rounding to fp32.  Two neighbours whose x are equal in fp32 are
+    pooled and the knots taken again, until x ascends strictly.
+    -> (x, y) float32 [K], 1 <= K <= rows, x strictly increasing, y non-decreasing.  An empty table raises ValueError."""
+    cnt, pos, qs = _calibration_rows_as_ints(table)
+    blocks = []
+    for c, s, q in zip(cnt, pos, qs):
+        if c == 0:
+            continue
+        blocks.append((c, s, q))
+        while len(blocks) > 1 and blocks[-2][1] * blocks[-1][0] > blocks[-1][1] * blocks[-2][0]:
+            (c1, s1, q1), (c0, s0, q0) = blocks.pop(), blocks.pop()
+            blocks.append((c0 + c1, s0 + s1, q0 + q1))
+    if not blocks:
+        raise ValueError("isotonic_from_table: the table holds no example")
+    while True:
+        knots = [_isotonic_knot(b) for b in blocks]
+        clash = next((j for j in range(len(knots) - 1) if knots[j][0] >= knots[j + 1][0]), None)
+        if clash is None:
+            break
+        (c0, s0, q0), (c1, s1, q1) = blocks[clash], blocks[clash + 1]
+        blocks[clash:clash + 2] = [(c0 + c1, s0 + s1, q0 + q1)]
+    return np.array([k[0] for k in knots], np.float32), np.array([k[1] for k in knots], np.float32)
+
+
+def _check_knots(x, y):
+    """x, y as float32 [K] after IsotonicMap's checks (ValueError otherwise)."""
+    x = np.ascontiguousarray(np.asarray(x, np.float32).reshape(-1))
+    y = np.ascontiguousarray(np.asarray(y, np.float32).reshape(-1))
+    if x.size != y.size:
+        raise ValueError("isotonic map: x has %d knots, y has %d" % (x.size, y.size))
+    if not 1 <= x.size <= ISOTONIC_MAX_KNOTS:
+        raise ValueError("isotonic map: %d knots are outside 1..%d" % (x.size, ISOTONIC_MAX_KNOTS))
+    for name, v in (("x", x), ("y", y)):
+        if not bool(np.all((v >= 0) & (v <= 1))):          # a NaN fails both comparisons
+            raise ValueError("isotonic map: %s has a value outside [0, 1]" % name)
+    if not bool(np.all(x[1:] > x[:-1])):
+        raise ValueError("isotonic map: x is not strictly increasing")
+    if not bool(np.all(y[1:] >= y[:-1])):
+        raise ValueError("isotonic map: y decreases")
+    return x, y
+
+
+def isotonic_apply_host(p, x, y):
+    """The documented definition of the map, in numpy fp32 -- bit for bit what rsx_calibrate_apply computes.  A p outside
+    [0, 1] by exact_auc_keys_host's bit test is returned unchanged, bit for bit (-0.0 counts as +0.0); p <= x[0] -> y[0];
+    p >= x[K-1] -> y[K-1]; otherwise with j the largest index with x[j] <= p:
+    t = (p - x[j]) / (x[j+1] - x[j]); o = y[j] + t * (y[j+1] - y[j]); out = o if o < y[j+1] else y[j+1] -- every operation one
+    fp32 operation rounded to nearest.  x must ascend strictly (not checked here).  -> float32, p's shape."""
+    p = np.ascontiguousarray(np.asarray(p, np.float32))
+    x = np.ascontiguousarray(np.asarray(x, np.float32).reshape(-1))
+    y = np.ascontiguousarray(np.asarray(y, np.float32).reshape(-1))
+    K = int(x.size)
+    if K < 1 or y.size != K:
+        raise ValueError("isotonic map: x and y need the same number of knots, at least one")
+    bits = p.reshape(-1).view(np.uint32)
+    u = np.where(bits == 0x80000000, np.uint32(0), bits).astype(np.uint32)
+    valid = u <= 0x3F800000
+    v = u[valid].view(np.float32)
+    r = np.full(v.shape, y[0], np.float32)
+    if K > 1:
+        j = np.clip(np.searchsorted(x, v, side="right") - 1, 0, K - 2)
+        x0, y0, y1 = x[j], y[j], y[j + 1]
+        t = (v - x0) / (x[j + 1] - x0)
+        o = y0 + t * (y1 - y0)
+        r = np.where(o < y1, o, y1).astype(np.float32)
+        r = np.where(v <= x[0], y[0], np.where(v >= x[K - 1], y[K - 1], r)).astype(np.float32)
+    out = bits.copy()
+    out[valid] = r.view(np.uint32)
+    return out.view(np.float32).reshape(p.shape)
+
+
+def check_calibration_map_world(world):
+    """calibration_fit / calibration_apply are a single-replica evaluation, like exact_auc."""
+    if int(world) > 1:
+        raise RsxError("calibration map: data-parallel evaluation is not supported (the ranks' keys would have to be sorted "
+                       "together); evaluate on one replica")
+
+
+def _f32_bits(a):
+    return [int(v) for v in np.ascontiguousarray(np.asarray(a, np.float32)).view(np.uint32)]
+
+
+class IsotonicMap:
+    """A fitted isotonic map: knots x (strictly increasing) and y (non-decreasing), float32 [K], 1 <= K <= 1024, all in [0, 1];
+    bins = the M it was fitted with, examples = V, positives = P, global_step / script = the model it belongs to.  In memory only:
+    table (the equal-mass table, int64 [M, 3]) and ece (its ECE by calibration_from_table) when evaluate() fitted it."""
+
+    def __init__(self, x, y, bins=0, examples=0, positives=0, global_step=0, script="", table=None, ece=None):
+        self.x, self.y = _check_knots(x, y)
+        self.bins, self.examples, self.positives = int(bins), int(examples), int(positives)
+        self.global_step, self.script = int(global_step), str(script)
+        self.table, self.ece = table, ece
+
+    @property
+    def knots(self):
+        return int(self.x.size)
+
+    def to_json(self):
+        """-> a dict for json.dump: the knots as fp32 bit patterns (x_bits / y_bits, what from_json reads) beside readable
+        floats (x / y, never read back)."""
+        return {"format": ISOTONIC_FORMAT, "script": self.script, "global_step": self.global_step, "bins": self.bins,
+                "examples": self.examples, "positives": self.positives, "knots": self.knots,
+                "x_bits": _f32_bits(self.x), "y_bits": _f32_bits(self.y),
+                "x": [float(v) for v in self.x], "y": [float(v) for v in self.y]}
+
+    @classmethod
+    def from_json(cls, doc):
+        """The map of to_json()'s dict (or its JSON text).  ValueError for: an unknown format, x and y of unequal length, K
+        outside 1..1024, an x that does not increase strictly, a y that decreases, a value outside [0, 1]."""
+        import json
+        if isinstance(doc, (str, bytes)):
+            doc = json.loads(doc)
+        if not isinstance(doc, dict) or doc.get("format") != ISOTONIC_FORMAT:
+            raise ValueError("isotonic map: unknown format %r" % (doc.get("format") if isinstance(doc, dict) else type(doc),))
+        try:
+            xb, yb = [int(v) for v in doc["x_bits"]], [int(v) for v in doc["y_bits"]]
+        except (KeyError, TypeError) as e:
+            raise ValueError("isotonic map: x_bits / y_bits are missing or not integers (%s)" % e)
+        if len(xb) != len(yb):
+            raise ValueError("isotonic map: x has %d knots, y has %d" % (len(xb), len(yb)))
+        if any(not 0 <= v <= 0xFFFFFFFF for v in xb + yb):
+            raise ValueError("isotonic map: a bit pattern is outside 32 bits")
+        x, y = np.array(xb, np.uint32).view(np.float32), np.array(yb, np.uint32).view(np.float32)
+        return cls(x, y, doc.get("bins", 0), doc.get("examples", 0), doc.get("positives", 0), doc.get("global_step", 0),
+                   doc.get("script", ""))
+
+    def save(self, path):
+        """to_json() to `path`, written under a temporary name and renamed."""
+        import json
+        import os
+        tmp = "%s.tmp.%d" % (path, os.getpid())
+        with open(tmp, "w") as f:
+            json.dump(self.to_json(), f)
+            f.write("\n")
+        os.replace(tmp, path)
+
+    @classmethod
+    def load(cls, path):
+        with open(path) as f:
+            return cls.from_json(f.read())
+
+    def apply_host(self, p):
+        return isotonic_apply_host(p, self.x, self.y)
+
+
+class Calibrator:
+    """An IsotonicMap held on the device (8 bytes per knot).  `apply` is ONE launch of rsx_calibrate_apply on the current stream;
+    nothing is allocated when `out` is given, so the call can be captured into a graph."""
+
+    def __init__(self, device, map):
+        self.device = torch.device(device)
+        self.map = map
+        self.x = torch.from_numpy(map.x.copy()).to(self.device)
+        self.y = torch.from_numpy(map.y.copy()).to(self.device)
+
+    def apply(self, prob, out=None):
+        """prob: a float32 device tensor (contiguous, any shape) or a numpy array.  -> the mapped probabilities: `out` (a device
+        tensor of the same size; it may be `prob` itself) or a new tensor for a tensor, a numpy array for a numpy array."""
+        host = not isinstance(prob, torch.Tensor)
+        if host:
+            shape = np.asarray(prob).shape
+            prob = torch.from_numpy(np.ascontiguousarray(np.asarray(prob, np.float32)).reshape(-1).copy()).to(self.device)
+        if not (prob.is_cuda and prob.dtype == torch.float32 and prob.is_contiguous()):
+            raise ValueError("calibrate: prob must be a contiguous float32 device tensor (or a numpy array)")
+        if out is None:
+            out = torch.empty_like(prob)
+        elif not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype == torch.float32 and out.is_contiguous()
+                  and out.numel() == prob.numel()):
+            raise ValueError("calibrate: out must be a contiguous float32 device tensor of prob's size")
+        if prob.numel():                  # (an empty tensor has no address to pass)
+            check(lib().rsx_calibrate_apply(C.c_void_p(self.x.data_ptr()), C.c_void_p(self.y.data_ptr()), int(self.x.numel()),
+                                            C.c_void_p(prob.data_ptr()), C.c_void_p(out.data_ptr()), int(prob.numel()),
+                                            C.c_void_p(torch.cuda.current_stream().cuda_stream)), "rsx_calibrate_apply")
+        return out.cpu().numpy().reshape(shape) if host else out

@@ -30,6 +30,17 @@ The reference exports a SavedModel whose serving signature parses serialized `tf
                                 form), bit-identical to the Estimator the bundle came from.  A 16-bit bundle's tables are
                                 widened to fp32 on the host first: it answers like an fp32 bundle holding the rounded values,
                                 and saves no device memory here.
+  calibration a bundle may carry one more file, `calibration.json`: the isotonic map (metrics.IsotonicMap: fp32 knots as bit
+              patterns) fitted by `evaluate()` with RunConfig.calibration_fit at the exported global_step
+              (`export_savedmodel(..., calibration="auto" | "off" | "require")`, `--export_calibration`).  The manifest and
+              format_version do not change and read_bundle reads only its two files: old readers and old bundles are untouched.
+              `Predictor.load(..., calibrated=None)` applies the map iff the bundle carries one (False: raw; True: it must):
+              `predict` / `predict_examples` then return the mapped probabilities on every path -- one more launch of
+              rsx_calibrate_apply (csrc/calibration_map.hip) behind the predict launch, inside the request size's graph on the
+              fused and device-parse paths, an eager launch into a buffer of the Predictor's own on the layers path.
+              `Predictor.calibrate(prob)` maps any array.  Out of scope: the din.py request kinds (`rank_candidates`,
+              `recommend*`, `evaluate_*`) select on and return RAW scores -- the map is monotone, so the order stands, and the
+              caller may pass the returned prob through `Predictor.calibrate`.
 """
 import ctypes as C
 import importlib
@@ -58,6 +69,8 @@ FORMAT_VERSION_16BIT = 2
 TABLE_DTYPES = ("float32", "bfloat16", "float16")
 SCRIPTS = ("fm", "deepfm", "xdeepfm", "dcn", "din")
 MANIFEST, VARIABLES = "model.json", "variables.npz"
+CALIBRATION = "calibration.json"      # optional: the isotonic map of the exported global_step (metrics.IsotonicMap.to_json)
+CALIBRATION_MODES = ("auto", "off", "require")
 # model_fn parameters that shape the network (what a Predictor needs to rebuild it without the training flags)
 _NETWORK_PARAMS = ("embedding_size", "deep_layers", "cross_layers", "cin_bf16", "cin_split", "hist_len", "n_item", "n_cate",
                    "tower", "force_generic")
@@ -198,10 +211,14 @@ def params_from_manifest(manifest, max_batch_size):
 
 
 # ---- bundle writer / reader ----------------------------------------------------------------------------------------------
-def write_bundle(export_dir_base, manifest, tensors):
+def write_bundle(export_dir_base, manifest, tensors, extra_files=None):
     """-> `<export_dir_base>/<unix seconds>`, holding model.json and variables.npz.  The bundle is assembled in a temporary
     directory of the same parent and renamed when complete: a reader never sees half a bundle.  (A second export within the
-    same second takes the next free second, as tf.estimator's export does.)"""
+    same second takes the next free second, as tf.estimator's export does.)
+    extra_files: {file name: text} written beside the two (calibration.json); the manifest does not list them."""
+    for name in (extra_files or {}):
+        if name in (MANIFEST, VARIABLES) or os.path.basename(name) != name or not name:
+            raise _lib.RsxError("export: %r is no name for an extra bundle file" % name)
     base = os.path.abspath(export_dir_base)
     os.makedirs(base, exist_ok=True)
     for k, v in tensors.items():
@@ -215,6 +232,9 @@ def write_bundle(export_dir_base, manifest, tensors):
         with open(os.path.join(tmp, MANIFEST), "w") as f:
             json.dump(manifest, f, indent=1, sort_keys=True)
             f.write("\n")
+        for name, text in (extra_files or {}).items():
+            with open(os.path.join(tmp, name), "w") as f:
+                f.write(text)
         ts = int(time.time())
         while True:
             final = os.path.join(base, "%d" % ts)
@@ -343,12 +363,16 @@ def store_variables_names(store):
     return [k for k, _ in _store_tensors(store)]
 
 
-def export_estimator(est, export_dir_base, table_dtype="float32"):
+def export_estimator(est, export_dir_base, table_dtype="float32", calibration="auto"):
     """Estimator.export_savedmodel's body: the latest checkpoint of est.model_dir as a bundle -> its directory.  table_dtype
-    "bfloat16" / "float16": every embedding-row tensor is rounded to it (`quantize_rows`) and stored in it."""
+    "bfloat16" / "float16": every embedding-row tensor is rounded to it (`quantize_rows`) and stored in it.
+    calibration: "auto" adds calibration.json when est has a map of the exported global_step (last_calibration_map, else
+    <model_dir>/calibration-<step>.json), "off" never, "require" raises when there is none; a map of another step is never taken."""
     from . import checkpoint
     script = est.model_fn.__module__.rsplit(".", 1)[-1]
     _check_export(script, table_dtype, module=est.model_fn.__module__)
+    if calibration not in CALIBRATION_MODES:
+        raise _lib.RsxError("export: calibration %r is none of %s" % (calibration, ", ".join(CALIBRATION_MODES)))
     # With a model_dir the bundle is its latest checkpoint (restored now unless this Estimator already runs from it); an
     # Estimator without one (model_dir=None: tests, notebooks) exports the variables it holds.
     if est.model_dir:
@@ -366,7 +390,17 @@ def export_estimator(est, export_dir_base, table_dtype="float32"):
         tensors = store_variables(est.store)
         if table_dtype != "float32":
             tensors = quantize_tensors(tensors, est.params["embedding_size"], table_dtype)
-        out = write_bundle(export_dir_base, make_manifest(script, est.params, est.global_step, tensors, table_dtype), tensors)
+        extra = None
+        if calibration != "off":
+            cmap = est.calibration_map_for_step(est.global_step)
+            if cmap is None and calibration == "require":
+                raise _lib.RsxError("export: calibration=\"require\" and there is no calibration map for global step %d (neither "
+                                    "last_calibration_map nor %s)"
+                                    % (est.global_step, est._calibration_path(est.global_step) or "a model_dir"))
+            if cmap is not None:
+                extra = {CALIBRATION: json.dumps(cmap.to_json()) + "\n"}
+        out = write_bundle(export_dir_base, make_manifest(script, est.params, est.global_step, tensors, table_dtype), tensors,
+                           extra)
         print("INFO:Model exported.", flush=True)
     if est.store.dp is not None:
         est.store.dp.barrier()
@@ -408,7 +442,7 @@ class Predictor(DinRanking):
 
     @classmethod
     def load(cls, export_dir, device="cuda", max_batch_size=4096, use_hip_graph=True, max_candidates=None, one_launch=False,
-             device_parse=False, parse_row_bytes=2048):
+             device_parse=False, parse_row_bytes=2048, calibrated=None):
         """export_dir: a bundle, or the --export_path that holds bundles (the newest is taken).  max_candidates (din.py bundles;
         default max_batch_size): the candidates per user one `rank_candidates` launch takes, longer requests are cut along C.
         one_launch (dcn.py bundles; the other scripts ignore it): answer through rsx_predict_dcn, path == "fused", instead of
@@ -420,13 +454,21 @@ class Predictor(DinRanking):
         example the device declines (malformed, a missing numeric, a record above 8 KB) or with more bytes than the staging
         buffer holds is parsed on the host exactly as without the flag.  Off by default.
         parse_row_bytes: the staging buffers (one pinned, one on the device) hold max_batch_size * parse_row_bytes request
-        bytes; a Criteo request row is about 0.9 KB (39 entries, 8-byte categorical values), 2048 leaves room for two."""
+        bytes; a Criteo request row is about 0.9 KB (39 entries, 8-byte categorical values), 2048 leaves room for two.
+        calibrated: None applies the bundle's calibration.json iff it carries one, False serves raw probabilities, True raises
+        when there is none.  A map whose global_step or script disagrees with the manifest is refused (whatever `calibrated`
+        says).  `calibration` holds the metrics.IsotonicMap or None, `calibrated` says whether predict / predict_examples map."""
         import torch
         self = object.__new__(cls)
         self.bundle_dir = latest_bundle(export_dir)
         self.manifest, arrays = read_bundle(self.bundle_dir)
         m = self.manifest
         self.script, self.global_step = m["script"], int(m["global_step"])
+        self.calibration = self._read_calibration()
+        if calibrated and self.calibration is None:
+            raise _lib.RsxError("Predictor: calibrated=True and bundle %r carries no %s" % (self.bundle_dir, CALIBRATION))
+        self.calibrated = self.calibration is not None and (calibrated is None or bool(calibrated))
+        self._cal = self._cal_buf = None    # metrics.Calibrator; the layers path's output buffer
         self.table_dtype = m.get("table_dtype", "float32")
         self.signature = SIGNATURE
         self.device = torch.device(device)
@@ -447,6 +489,11 @@ class Predictor(DinRanking):
         else:
             self.path = "layers"
             self._layers_setup(arrays)
+        if self.calibration is not None:
+            from .metrics import Calibrator
+            self._cal = Calibrator(self.device, self.calibration)
+            if self.calibrated and self.path == "layers":
+                self._cal_buf = torch.empty(self.max_batch_size, dtype=torch.float32, device=self.device)
         self.max_candidates = self.max_batch_size if max_candidates is None else int(max_candidates)
         if self.max_candidates < 1:
             raise _lib.RsxError("Predictor: max_candidates must be at least 1")
@@ -469,6 +516,28 @@ class Predictor(DinRanking):
             self.rank_path = "fused" if self._rank_supported() else "layers"
             self.topk_path = "device" if self.rank_path == "fused" else "host"
         return self
+
+    def _read_calibration(self):
+        """The bundle's calibration.json as a metrics.IsotonicMap, None when the bundle has none."""
+        from .metrics import IsotonicMap
+        path = os.path.join(self.bundle_dir, CALIBRATION)
+        if not os.path.isfile(path):
+            return None
+        try:
+            cmap = IsotonicMap.load(path)
+        except (OSError, ValueError) as e:
+            raise _lib.RsxError("bundle %r: cannot read %s (%s)" % (self.bundle_dir, CALIBRATION, e)) from e
+        if cmap.global_step != self.global_step or cmap.script != self.script:
+            raise _lib.RsxError("bundle %r: %s belongs to %s.py at global step %d, the model is %s.py at global step %d"
+                                % (self.bundle_dir, CALIBRATION, cmap.script, cmap.global_step, self.script, self.global_step))
+        return cmap
+
+    def calibrate(self, prob):
+        """The bundle's map applied to any array of probabilities (numpy -> numpy, device tensor -> device tensor); what the
+        din.py request kinds, which return raw scores, leave to the caller."""
+        if self._cal is None:
+            raise _lib.RsxError("Predictor: bundle %r carries no %s" % (self.bundle_dir, CALIBRATION))
+        return self._cal.apply(prob)
 
     # -- the one-launch path ----------------------------------------------------------------------------------------------
     def _fused_variables(self, arrays, need):
@@ -565,6 +634,8 @@ class Predictor(DinRanking):
         fn = getattr(_lib.lib(), self._kernel)          # rsx_predict_fm_tower / rsx_predict_dcn: the same call shape
         _lib.check(fn(C.byref(self._model), self._ids.data_ptr(), self._prob.data_ptr(), int(n),
                       torch.cuda.current_stream().cuda_stream), self._kernel)
+        if self.calibrated:               # behind the predict launch, in place in the Predictor's own buffer (and in its graph)
+            self._cal.apply(self._prob[:n], out=self._prob[:n])
 
     def _run(self, key, launch):
         """`launch()` eagerly, or as the captured graph of `key`: warm-up on the first request, capture on the second."""
@@ -691,11 +762,15 @@ class Predictor(DinRanking):
             return {"ids": parse_uid_iid_examples(serialized, self.layout)}
         return ip.parse_criteo_examples(serialized, self.layout)[0]
 
-    def predict(self, features):
+    def predict(self, features, raw=False):
         """One parsed batch ({'ids': int32 [B, F]}, + 'cont_log' for xdeepfm.py; din.py: its four id arrays), host or device
-        -> {'prob': float32 numpy [B]}."""
+        -> {'prob': float32 numpy [B]}: the mapped probabilities when `calibrated`.  raw=True (layers path; what rank_candidates
+        asks for): the model's own probabilities whatever `calibrated` says."""
         import torch
         from .estimator import ModeKeys
+        if raw and self.calibrated and self.path == "fused":
+            raise _lib.RsxError("Predictor: raw=True on the fused path of a calibrated Predictor (the map is part of the request's "
+                                "graph); load with calibrated=False")
         B = int(next(iter(features.values())).shape[0])
         out = np.empty(B, np.float32)
         with torch.no_grad():
@@ -709,6 +784,8 @@ class Predictor(DinRanking):
                 else:
                     part = {k: v[s:e] for k, v in features.items()}
                     prob, _, _ = self._est._infer_step(part, None, ModeKeys.PREDICT)
+                    if self.calibrated and not raw:     # never into the Estimator's static graph buffer
+                        prob = self._cal.apply(prob.reshape(-1).float().contiguous(), out=self._cal_buf[:e - s])
                 out[s:e] = prob.reshape(-1).float().cpu().numpy()
         return {"prob": out}
 

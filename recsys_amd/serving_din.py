@@ -939,7 +939,7 @@ class DinRanking:
         if self.rank_path != "fused":
             host = [x.detach().cpu().numpy() if isinstance(x, torch.Tensor) else np.asarray(x)
                     for x in (u_iid_seq, u_icat_seq, i_id, i_cate)]
-            return {"prob": self.predict(expand_rank_request(*host, hist_len=P))["prob"].reshape(shape)}
+            return {"prob": self.predict(expand_rank_request(*host, hist_len=P), raw=True)["prob"].reshape(shape)}
 
         out = np.empty((U, Cn), np.float32)
         with torch.no_grad():
