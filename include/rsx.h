@@ -294,7 +294,9 @@ typedef struct {
    * applied at any time inside the window.
    *   window_block_u      float4 per lane of a TABLE_TF1_COLD block: 0 (= 8, the stand-alone sweep's) or 2 / 4 -- smaller
    *                       blocks spread a slice over the CUs a latency-bound launch leaves idle; blk_lo / blk_hi then count
-   *                       blocks of rsx_adam_num_blocks_u(segs, nseg, window_block_u).
+   *                       blocks of rsx_adam_num_blocks_u(segs, nseg, window_block_u).  (A VEC_COLD segment with window maps
+   *                       takes 2 float4 per lane at window_block_u 0 / 8 -- the stand-alone sweep spreads the vector's
+   *                       1 + w updates per element over 4x the workgroups -- and 8 in a 2 / 4 slice; 8 without maps.)
    *   alphas_from_state   0: the step sizes come from the beta powers (state words 0, 1) -- the slice of the window's FIRST
    *                       step, whose block 0 also leaves them in state words 8.. --; 1: they are read from there (later steps:
    *                       the powers have been advanced since).                                                              */

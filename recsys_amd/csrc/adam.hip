@@ -67,6 +67,7 @@ __global__ __launch_bounds__(ADAM_T) void adam_slice_k(const AdamSlice s) { adam
 template <int NW, bool COMPACT>
 __global__ __launch_bounds__(ADAM_T, RSX_ADAM_WIN_OCC) void adam_window_k(const AdamSlice s) {
   // (the window's step sizes for the lazy window pass: state words 8.., adam_device.h)
+  RSX_STAMP(0, blockIdx.x == 0);
   if (blockIdx.x == 0 && threadIdx.x == 0 && s.blk_lo == 0 && !s.args.alpha_src) adam_publish_step_sizes<NW>(s.args);
   if constexpr (COMPACT) {
     __shared__ uint32_t lds[WIN_LIST_WORDS];
@@ -74,7 +75,27 @@ __global__ __launch_bounds__(ADAM_T, RSX_ADAM_WIN_OCC) void adam_window_k(const 
   } else {
     adam_window_block<NW>(s.args, s.blk_lo + blockIdx.x);
   }
+#ifdef RSX_STAMPS
+  // the last exit of a first-order-vector block (slot 1) and of a table block (slot 2): scripts/stamp_probe_window.py
+  int si = 0;
+  for (int k = 1; k < s.args.nseg; ++k)
+    if (s.blk_lo + blockIdx.x >= s.args.seg[k].blk_begin) si = k;
+  const bool vec_blk = s.args.seg[si].kind == RSX_ADAM_VEC_COLD;
+  __syncthreads();
+  RSX_STAMP_MAX(1, vec_blk);
+  RSX_STAMP_MAX(2, !vec_blk);
+#endif
 }
+#ifdef RSX_STAMPS
+// profiling build only: copy this unit's phase stamps (100 MHz wall clock ticks) to the host
+extern "C" int rsx_dbg_stamps_adam_zero() {
+  static const unsigned long long z[64] = {0};
+  return hipMemcpyToSymbol(HIP_SYMBOL(rsx_stamps_d), z, sizeof(z)) == hipSuccess ? RSX_OK : RSX_ELAUNCH;
+}
+extern "C" int rsx_dbg_stamps_adam(unsigned long long* out_h) {
+  return hipMemcpyFromSymbol(out_h, HIP_SYMBOL(rsx_stamps_d), sizeof(unsigned long long) * 64) == hipSuccess ? RSX_OK : RSX_ELAUNCH;
+}
+#endif
 template <int NW>
 static void launch_window(const AdamSlice& s, const bool compact, hipStream_t st) {
   if (compact) RSX_LAUNCH((adam_window_k<NW, true>), dim3(s.n_blk), dim3(ADAM_T), 0, st, s);

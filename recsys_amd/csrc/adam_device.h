@@ -79,6 +79,16 @@ constexpr long long ADAM_Q = (long long)ADAM_T * ADAM_U;  // float4 per workgrou
 // LAST ones to finish (stamps: 8.6 us after the launch's first workgroup, against 4.8 for the window pass).
 constexpr int ADAM_U_DENSE = 2;
 constexpr long long ADAM_Q_DENSE = (long long)ADAM_T * ADAM_U_DENSE;
+// VEC_COLD segments of a WINDOW sweep in full-size blocks (nw > 0, win_u == 0: the stand-alone launch, adam_window_k) take 2
+// float4 per lane as well: the first-order vector is 1 / 16 of the tables' elements, but each of its elements takes the
+// 1 + nw updates one by one (adam_window_vec_block), and in 2 048-float4 blocks DeepFM's vector was 103 workgroups of the
+// launch's 1 861 that ran as long as the whole launch.  411 workgroups spread the same work over every CU.
+constexpr int ADAM_U_WVEC = 2;
+constexpr long long ADAM_Q_WVEC = (long long)ADAM_T * ADAM_U_WVEC;
+// float4 positions per lane of a VEC_SLOT / VEC_COLD block (host and device: adam_build_args lays the blocks out with it)
+__host__ __device__ __forceinline__ int adam_vec_u(const int kind, const int nw, const int win_u) {
+  return kind == RSX_ADAM_VEC_COLD && nw > 0 && win_u == 0 ? ADAM_U_WVEC : ADAM_U;
+}
 
 // "Am I the last workgroup of this launch?" for thread 0 of every workgroup, after its block's work (and a __syncthreads):
 // arrival counters by workgroup index modulo 32 (one 128-byte line each: state words 4 + 32 r), then the shared ticket
@@ -165,7 +175,8 @@ __device__ __forceinline__ void adam_block(const AdamArgs& a, const uint32_t blk
   // the window's extra slot maps are equally spaced (one allocation): base + stride instead of 7 pointers in scalar registers
   const int32_t* __restrict__ swb = a.slot_w0;
   const long long sws = a.slot_w_stride;
-  const long long base = (long long)(blk - s.blk_begin) * (s.kind == RSX_ADAM_DENSE ? ADAM_Q_DENSE : ADAM_Q);
+  const int vec_u = adam_vec_u(s.kind, a.nw, a.win_u);        // (ADAM_U for every kind but a window's VEC_COLD)
+  const long long base = (long long)(blk - s.blk_begin) * (s.kind == RSX_ADAM_DENSE ? ADAM_Q_DENSE : (long long)ADAM_T * vec_u);
   float4* __restrict__ var4 = reinterpret_cast<float4*>(s.var);
   float4* __restrict__ m4 = reinterpret_cast<float4*>(s.m);
   float4* __restrict__ v4 = reinterpret_cast<float4*>(s.v);
@@ -255,7 +266,7 @@ __device__ __forceinline__ void adam_block(const AdamArgs& a, const uint32_t blk
     const long long n4 = s.n >> 2;
 #pragma unroll
     for (int u = 0; u < ADAM_U; ++u) {
-      const long long e = base + (long long)u * ADAM_T + tid;
+      const long long e = u < vec_u ? base + (long long)u * ADAM_T + tid : n4 + 1;      // (positions past a short block: no-ops)
       if (e < n4) {
         int4 sl = reinterpret_cast<const int4*>(s.slot)[e];
         for (int l = 0; l < nw; ++l) {
@@ -438,7 +449,8 @@ __device__ __forceinline__ bool adam_win_guard4(const float4& var, const float4&
 //     workgroups walking batches with a stride of the grid 85.2 / 64.7 at 4 per CU, 81.0 / 59.9 at 8 per CU; one batch per
 //     workgroup without a pipeline 97.5 / 65.6.  With the state L2-resident the updates alone cost ~9 us per step of the
 //     window: from ~4 steps per window on the kernel is VALU-bound, not HBM-bound.)
-//   - blocks of the other kinds (the first-order vector, ...): adam_block.
+//   - VEC_COLD blocks of the stand-alone sweep (U == ADAM_U): adam_window_vec_block, below.
+//   - blocks of the other kinds, and the riders' VEC_COLD blocks: adam_block.
 // U = float4 per lane of a block (== a.win_u, or ADAM_U when that is 0: the host picks the instantiation)
 //
 // COMPACT (rsx_adam_slice.window_compact; the stand-alone sweep only, rows of 4 .. 256 floats, a power of two): a row whose m
@@ -471,6 +483,231 @@ __device__ __forceinline__ bool win_shortcut_gate(const AdamArgs& a, const float
   for (int j = 0; j < NW; ++j) ok = ok && plus_finite(aw.get(j));
   return ok;
 }
+// Packed fast form of the zero-gradient updates (adam_fast.h), for the tables' and the vector's chain alike: usable (fast_ok)
+// when the hyper-parameters keep every operand of a guarded element inside the fast forms' domains for all 1 + NW updates
+// (b1^8 >= 1/4, b2^8 >= 2^-8, alphas within 4x).  Returns adam_win_guard1's lower bound on |m|, 2^-90 / min alpha, as bits.
+template <int NW>
+__device__ __forceinline__ uint32_t win_fast_form(const AdamArgs& a, const float alpha0, const AlphaW& aw, bool& fast_ok) {
+  float amin = alpha0, amax = alpha0;
+#pragma unroll
+  for (int j = 0; j < NW; ++j) {
+    amin = fminf(amin, aw.get(j));
+    amax = fmaxf(amax, aw.get(j));
+  }
+  fast_ok = RSX_ADAM_WIN_FAST && a.b1 >= 0.85f && a.b1 < 1.f && a.b2 >= 0.5f && a.b2 < 1.f && a.eps >= 0x1p-30f &&
+            a.eps <= 1.f && amin >= 0x1p-24f && amax <= 16.f && amax <= 4.f * amin;
+  return __float_as_uint(fast_ok ? 0x1p-90f / amin : 1.f);
+}
+
+// ---- window sweep: the first-order vector (VEC_COLD blocks of the stand-alone launch, ADAM_U_WVEC float4 per lane) ------------
+// adam_block's VEC_COLD branch gives every element -- void ones included -- 1 + NW IEEE adam_dense1 updates after ~10 dependent
+// round trips per float4 (segment fields, slot map, one trip per window map, state), 8 float4 one after another, and stores all
+// of them back: 103 workgroups that left 16 us after the last of the launch's 1 642 table blocks.  Here:
+//   - the segment's fields are read once; every load of the block's 2 float4 per lane (slot map, the NW window maps, m, v,
+//     var; unconditional, clamped index) is issued before the first use: one round trip;
+//   - elements some step of the window touches (AND of the maps >= 0) are neither computed nor stored;
+//   - under the launch-uniform gate (win_shortcut_gate, and 1 - b1, 1 - b2 in [+0, FLT_MAX]; with b2 > 0 that is 1 - b2 in
+//     [0, 1)) an element with m = 0x00000000 and v in [+0, +inf) is STILL:  m1 = +0 + (0 - 0) omb1 = +0,
+//     n = (+0) alpha = +0, v1 = v + (0 - v) omb2 = v - fl(v omb2) in [+0, v] (x - x = +0 in round-to-nearest), sqrt(v1) + eps
+//     in (0, FLT_MAX], (+0) / that = +0, var - (+0) = var with all its bits.  void (v = +0 too): nothing moves, nothing is
+//     stored.  idle: v alone takes its 1 + NW steps v + (0 - v) omb2 and is stored alone.  (v = +inf is NOT idle in this
+//     formula, unlike the tables' v * b2: inf + (0 - inf) omb2 = NaN, which the next update carries into var.  m = -0 is live:
+//     -0 + (0 - -0) omb1 = +0.)  The one non-arithmetic difference is the tables': a signalling NaN weight under a still element
+//     keeps its payload;
+//   - every other untouched element is live.  A wave whose live elements all pass adam_win_guard1 (once per window, on the
+//     loaded state) takes the packed chain, adam_zero_grad2_dense, two elements per instruction; any other wave takes
+//     adam_zero_grad1<true> 1 + NW times: adam_dense1(g = 0) operation by operation with the fast square root / division
+//     behind a guard on each update's own operands, IEEE for a wave with an element outside;
+//   - the math is skipped where no lane of the wave needs it; a float4 is stored when one of its elements moved (the others
+//     return the bits that were loaded -- as adam_block does for touched elements).
+// No compaction: with 2 float4 per lane the packed chain is well under 1 k instructions per wave, spread over 1 644 waves.
+struct WinVecEl {
+  float var, m, v;
+  bool live, idle;
+};
+__device__ __forceinline__ void win_vec_classify(WinVecEl& x, const bool untouched, const bool gate) {
+  const uint32_t mb = __float_as_uint(x.m), vb = __float_as_uint(x.v);
+  const bool still = gate && mb == 0u && vb < 0x7f800000u;
+  x.live = untouched && !still;
+  x.idle = untouched && still && vb != 0u;
+}
+// One zero-gradient ApplyAdam update of two elements -- adam_dense1(g = 0) operation by operation -- with the packed square
+// root / division.  The moments' updates are the IEEE operations themselves (v_pk_mul_f32 / v_pk_add_f32); what the guard
+// has to cover is the operands of the square root and the division, and adam_win_guard1's bounds cover them for THIS formula
+// too: with fast_ok (b1 in [0.85, 1), b2 in [0.5, 1)) 1 - b is exact, m1 = m - fl(m omb1) and v1 = v - fl(v omb2) are m b1 and
+// v b2 to within 2 ulp and never larger in magnitude than m, v -- against a factor 4 of room between the guard's bounds
+// (|n_j| >= 2^-92, v_j >= 2^-94) and the fast forms' domains (2^-94, 2^-96), and a factor 0.272 / 0.25 in b1^8 >= 1 / 4.  (The
+// guard's v == +0 case needs m == +0: such an element is void here and never live.)
+__device__ __forceinline__ void adam_zero_grad2_dense(rsx_f2& var, rsx_f2& m, rsx_f2& v, const float alpha, const float omb1,
+                                                      const float omb2, const float eps) {
+  m = m + (0.f - m) * omb1;
+  v = v + (0.f - v) * omb2;
+  const rsx_f2 n = m * alpha;
+  const rsx_f2 d = rsx_sqrt2_fast(v) + eps;
+  var = var - rsx_div2_fast(n, d);
+}
+// idle elements: v alone; live ones: update by update, each behind its own guard (adam_zero_grad1)
+template <int NW, int N>
+__device__ __forceinline__ void win_vec_update(WinVecEl (&x)[N], const Hp& h, const AlphaW& aw, const bool with_live = true) {
+  bool any_idle = false, any_live = false;
+#pragma unroll
+  for (int i = 0; i < N; ++i) {
+    any_idle |= x[i].idle;
+    any_live |= x[i].live;
+  }
+  if (__builtin_amdgcn_ballot_w64(any_idle) != 0ull) {          // (wave-uniform)
+#pragma unroll
+    for (int i = 0; i < N; ++i) {
+      float v = x[i].v;
+#pragma unroll
+      for (int j = 0; j < 1 + NW; ++j) v = v + (0.f - v) * h.omb2;      // adam_dense1's v1 with g * g = +0
+      if (x[i].idle) x[i].v = v;
+    }
+  }
+  if (with_live && __builtin_amdgcn_ballot_w64(any_live) != 0ull) {
+    // a wave with a live element outside the packed form's guard (or hyper-parameters outside): update by update, each behind its own guard
+#pragma unroll 1
+    for (int j = 0; j < 1 + NW; ++j) {
+      Hp hj = h;
+      if (j > 0) hj.alpha = aw.get(j - 1);
+#pragma unroll
+      for (int i = 0; i < N; ++i) adam_zero_grad1<true>(x[i].var, x[i].m, x[i].v, x[i].live, hj);
+    }
+  }
+}
+template <int NW>
+__device__ __forceinline__ void adam_window_vec_block(const AdamArgs& a, const SegDev& s, const uint32_t blk, const int tid) {
+  static_assert(ADAM_U_WVEC == 2, "two float4 per lane, both in flight at once");
+  // the segment's fields, once (DESIGN 4c rule 6: `s` is a dynamically indexed kernel argument, every use is a load)
+  float* const __restrict__ var1 = s.var;
+  float* const __restrict__ m1 = s.m;
+  float* const __restrict__ v1 = s.v;
+  const int32_t* const __restrict__ slot = s.slot;
+  const long long n = s.n;
+  const long long base = (long long)(blk - s.blk_begin) * ADAM_Q_WVEC;
+  const int32_t* const __restrict__ swb = a.slot_w0;
+  const long long sws = a.slot_w_stride;
+  Hp h;
+  h.b1 = a.b1;
+  h.b2 = a.b2;
+  h.omb1 = 1.0f - a.b1;
+  h.omb2 = 1.0f - a.b2;
+  h.eps = a.eps;
+  AlphaW aw;
+  adam_step_sizes(a, NW, h.alpha, aw);
+  const bool gate = win_shortcut_gate<NW>(a, h.alpha, aw) && __float_as_uint(h.omb1) < 0x7f800000u &&
+                    __float_as_uint(h.omb2) < 0x7f800000u;
+  bool fast_ok;
+  const uint32_t m_lo_bits = win_fast_form<NW>(a, h.alpha, aw, fast_ok);
+  const long long n4 = n >> 2;
+  if (n4 > 0) {
+    float4* const __restrict__ var4 = reinterpret_cast<float4*>(var1);
+    float4* const __restrict__ m4 = reinterpret_cast<float4*>(m1);
+    float4* const __restrict__ v4 = reinterpret_cast<float4*>(v1);
+    const long long e0 = base + tid, e1 = e0 + ADAM_T;
+    const bool in0 = e0 < n4, in1 = e1 < n4;
+    const long long c0 = in0 ? e0 : n4 - 1, c1 = in1 ? e1 : n4 - 1;
+    int4 t0 = reinterpret_cast<const int4*>(slot)[c0], t1 = reinterpret_cast<const int4*>(slot)[c1];
+    // (untouched = -1 = all ones: one value >= 0 clears the sign of the AND.)  All of them in flight at once.
+#pragma unroll
+    for (int l = 0; l < NW; ++l) {
+      const int4* const w = reinterpret_cast<const int4*>(swb + (long long)l * sws);
+      const int4 w0 = w[c0], w1 = w[c1];
+      t0.x &= w0.x; t0.y &= w0.y; t0.z &= w0.z; t0.w &= w0.w;
+      t1.x &= w1.x; t1.y &= w1.y; t1.z &= w1.z; t1.w &= w1.w;
+    }
+    const float4 mm0 = m4[c0], vv0 = v4[c0], va0 = var4[c0], mm1 = m4[c1], vv1 = v4[c1], va1 = var4[c1];
+    WinVecEl x[8] = {{va0.x, mm0.x, vv0.x, false, false}, {va0.y, mm0.y, vv0.y, false, false},
+                     {va0.z, mm0.z, vv0.z, false, false}, {va0.w, mm0.w, vv0.w, false, false},
+                     {va1.x, mm1.x, vv1.x, false, false}, {va1.y, mm1.y, vv1.y, false, false},
+                     {va1.z, mm1.z, vv1.z, false, false}, {va1.w, mm1.w, vv1.w, false, false}};
+    win_vec_classify(x[0], in0 && t0.x < 0, gate);
+    win_vec_classify(x[1], in0 && t0.y < 0, gate);
+    win_vec_classify(x[2], in0 && t0.z < 0, gate);
+    win_vec_classify(x[3], in0 && t0.w < 0, gate);
+    win_vec_classify(x[4], in1 && t1.x < 0, gate);
+    win_vec_classify(x[5], in1 && t1.y < 0, gate);
+    win_vec_classify(x[6], in1 && t1.z < 0, gate);
+    win_vec_classify(x[7], in1 && t1.w < 0, gate);
+    // every live element of the wave inside adam_win_guard1 (evaluated once, on the loaded state; fast_ok / m_lo_bits:
+    // win_fast_form): the packed chain, two elements per instruction -- what it computes in the other elements is dropped.
+    // (Named pairs: an array of them indexed inside the step loop is demoted to LDS by this toolchain.)
+#define RSX_WV_BAD(i) (x[i].live && adam_win_guard1(x[i].var, x[i].m, x[i].v, m_lo_bits))
+    const bool bad = !fast_ok | RSX_WV_BAD(0) | RSX_WV_BAD(1) | RSX_WV_BAD(2) | RSX_WV_BAD(3) | RSX_WV_BAD(4) | RSX_WV_BAD(5) |
+                     RSX_WV_BAD(6) | RSX_WV_BAD(7);
+#undef RSX_WV_BAD
+    const bool packed = __builtin_amdgcn_ballot_w64(bad) == 0ull;      // (wave-uniform)
+    const bool any_live = x[0].live | x[1].live | x[2].live | x[3].live | x[4].live | x[5].live | x[6].live | x[7].live;
+    win_vec_update<NW>(x, h, aw, !packed);
+    if (packed && __builtin_amdgcn_ballot_w64(any_live) != 0ull) {
+      rsx_f2 va01 = {x[0].var, x[1].var}, va23 = {x[2].var, x[3].var}, va45 = {x[4].var, x[5].var}, va67 = {x[6].var, x[7].var};
+      rsx_f2 mm01 = {x[0].m, x[1].m}, mm23 = {x[2].m, x[3].m}, mm45 = {x[4].m, x[5].m}, mm67 = {x[6].m, x[7].m};
+      rsx_f2 vv01 = {x[0].v, x[1].v}, vv23 = {x[2].v, x[3].v}, vv45 = {x[4].v, x[5].v}, vv67 = {x[6].v, x[7].v};
+      const float omb1 = h.omb1, omb2 = h.omb2, eps = h.eps;      // (scalars: `h` by reference here sent it to LDS)
+      auto step = [&](const float alpha) {
+        adam_zero_grad2_dense(va01, mm01, vv01, alpha, omb1, omb2, eps);
+        adam_zero_grad2_dense(va23, mm23, vv23, alpha, omb1, omb2, eps);
+        adam_zero_grad2_dense(va45, mm45, vv45, alpha, omb1, omb2, eps);
+        adam_zero_grad2_dense(va67, mm67, vv67, alpha, omb1, omb2, eps);
+      };
+      step(h.alpha);
+#pragma unroll 1
+      for (int j = 0; j < NW; ++j) step(aw.get(j));
+#define RSX_WV_TAKE(i, VA, MM, VV, c) if (x[i].live) { x[i].var = VA.c; x[i].m = MM.c; x[i].v = VV.c; }
+      RSX_WV_TAKE(0, va01, mm01, vv01, x) RSX_WV_TAKE(1, va01, mm01, vv01, y)
+      RSX_WV_TAKE(2, va23, mm23, vv23, x) RSX_WV_TAKE(3, va23, mm23, vv23, y)
+      RSX_WV_TAKE(4, va45, mm45, vv45, x) RSX_WV_TAKE(5, va45, mm45, vv45, y)
+      RSX_WV_TAKE(6, va67, mm67, vv67, x) RSX_WV_TAKE(7, va67, mm67, vv67, y)
+#undef RSX_WV_TAKE
+    }
+    const bool live0 = x[0].live | x[1].live | x[2].live | x[3].live, live1 = x[4].live | x[5].live | x[6].live | x[7].live;
+    const bool idle0 = x[0].idle | x[1].idle | x[2].idle | x[3].idle, idle1 = x[4].idle | x[5].idle | x[6].idle | x[7].idle;
+    if (live0) {
+      var4[c0] = make_float4(x[0].var, x[1].var, x[2].var, x[3].var);
+      m4[c0] = make_float4(x[0].m, x[1].m, x[2].m, x[3].m);
+    }
+    if (live0 || idle0) v4[c0] = make_float4(x[0].v, x[1].v, x[2].v, x[3].v);
+    if (live1) {
+      var4[c1] = make_float4(x[4].var, x[5].var, x[6].var, x[7].var);
+      m4[c1] = make_float4(x[4].m, x[5].m, x[6].m, x[7].m);
+    }
+    if (live1 || idle1) v4[c1] = make_float4(x[4].v, x[5].v, x[6].v, x[7].v);
+  }
+  // scalar tail (n not a multiple of 4): the wave that holds float4 position n4's lane -- the block the layout adds for it
+  // (work = n / 4 + 1) -- takes the 1 .. 3 last elements in lanes 0 .. 2, maps hoisted the same way
+  const int nt = (int)(n & 3);
+  const long long tp = n4 - base;                                 // position n4 within this block
+  if (nt != 0 && tp >= 0 && tp < ADAM_Q_WVEC && (tid >> 6) == (int)((tp & (ADAM_T - 1)) >> 6)) {      // (wave-uniform)
+    const int q = tid & 63;
+    const bool mine = q < nt;
+    const long long i = n4 * 4 + (mine ? q : 0);
+    int t = slot[i];
+#pragma unroll
+    for (int l = 0; l < NW; ++l) t &= swb[(long long)l * sws + i];
+    WinVecEl x = {var1[i], m1[i], v1[i], false, false};
+    win_vec_classify(x, mine && t < 0, gate);
+    if (__builtin_amdgcn_ballot_w64(x.idle) != 0ull) {
+      float v = x.v;
+#pragma unroll
+      for (int j = 0; j < 1 + NW; ++j) v = v + (0.f - v) * h.omb2;
+      if (x.idle) x.v = v;
+    }
+    if (__builtin_amdgcn_ballot_w64(x.live) != 0ull) {
+#pragma unroll 1
+      for (int j = 0; j < 1 + NW; ++j) {
+        Hp hj = h;
+        if (j > 0) hj.alpha = aw.get(j - 1);
+        adam_zero_grad1<true>(x.var, x.m, x.v, x.live, hj);
+      }
+    }
+    if (x.live) {
+      var1[i] = x.var;
+      m1[i] = x.m;
+    }
+    if (x.live || x.idle) v1[i] = x.v;
+  }
+}
+
 template <int NW, int U = ADAM_U, bool COMPACT = false>
 __device__ __forceinline__ void adam_window_block(const AdamArgs& a, const uint32_t blk, const int tid = threadIdx.x,
                                                   uint32_t* const lds = nullptr /* COMPACT: WIN_LIST_WORDS words of LDS */) {
@@ -485,6 +722,12 @@ __device__ __forceinline__ void adam_window_block(const AdamArgs& a, const uint3
     if (blk >= a.seg[k].blk_begin) si = k;
   const SegDev& s = a.seg[si];
   if (s.kind != RSX_ADAM_TABLE_TF1_COLD) {
+    if constexpr (U == ADAM_U) {         // the stand-alone launch (a.win_u == 0): the vector's blocks are ADAM_U_WVEC wide
+      if (s.kind == RSX_ADAM_VEC_COLD) {
+        adam_window_vec_block<NW>(a, s, blk, tid);
+        return;
+      }
+    }
     adam_block(a, blk, tid);
     return;
   }
@@ -496,17 +739,8 @@ __device__ __forceinline__ void adam_window_block(const AdamArgs& a, const uint3
   h.eps = a.eps;
   AlphaW aw;
   adam_step_sizes(a, nw, h.alpha, aw);
-  // Packed fast form of the zero-gradient updates (adam_fast.h): usable when the hyper-parameters keep every operand of a
-  // guarded element inside the fast forms' domains for all 1 + NW updates (b1^8 >= 1/4, b2^8 >= 2^-8, alphas within 4x).
-  float amin = h.alpha, amax = h.alpha;
-#pragma unroll
-  for (int j = 0; j < NW; ++j) {
-    amin = fminf(amin, aw.get(j));
-    amax = fmaxf(amax, aw.get(j));
-  }
-  const bool fast_ok = RSX_ADAM_WIN_FAST && a.b1 >= 0.85f && a.b1 < 1.f && a.b2 >= 0.5f && a.b2 < 1.f && a.eps >= 0x1p-30f &&
-                       a.eps <= 1.f && amin >= 0x1p-24f && amax <= 16.f && amax <= 4.f * amin;
-  const uint32_t m_lo_bits = __float_as_uint(fast_ok ? 0x1p-90f / amin : 1.f);
+  bool fast_ok;
+  const uint32_t m_lo_bits = win_fast_form<NW>(a, h.alpha, aw, fast_ok);
   const int32_t* __restrict__ swb = a.slot_w0;
   const int sws = (int)a.slot_w_stride;           // (< 2^28: adam_build_args) 32-bit element offsets: scalar base + vector offset
   float4* __restrict__ var4 = reinterpret_cast<float4*>(s.var);
@@ -848,7 +1082,8 @@ static inline int adam_build_args(const rsx_adam_seg* segs_h, int nseg, float* s
     }
     d.blk_begin = blocks;
     const long long quantum = s.kind == RSX_ADAM_DENSE ? ADAM_Q_DENSE
-                              : (s.kind == RSX_ADAM_TABLE_TF1_COLD && a.win_u > 0 ? (long long)ADAM_T * a.win_u : ADAM_Q);
+                              : (s.kind == RSX_ADAM_TABLE_TF1_COLD && a.win_u > 0 ? (long long)ADAM_T * a.win_u
+                                 : (long long)ADAM_T * adam_vec_u(s.kind, a.nw, a.win_u));
     blocks += (uint32_t)((work + quantum - 1) / quantum);
   }
   a.nseg = k;
