@@ -3,8 +3,8 @@
 // the 200-threshold tf.metrics.auc of csrc/metrics.hip and beside AUC_exact; it changes neither.
 //
 // THE CONTRACT, in integers.  An example is (group g, fp32 p, label y).  k32 is csrc/auc_exact.hip's 32-bit key exactly:
-// (bits(p) << 1) | (y > 0.5f) for 0 <= p <= 1 (-0.0 counts as +0.0), the padding key otherwise.  The example is valid when k32 is
-// not the padding key and 0 <= g < 2^group_bits (group_bits in 1..31).  A valid example is ONE 64-bit key
+// (bits(p) << 1) | positive for a valid p, by the example rule of csrc/eval_device.h, the padding key otherwise.  The example is
+// valid when k32 is not the padding key and 0 <= g < 2^group_bits (group_bits in 1..31).  A valid example is ONE 64-bit key
 //     (uint64(g) << 32) | k32            unsigned key order = (group, score, label) order
 // and an invalid one the padding key 0xFFFFFFFFFFFFFFFF, which sorts to the end, takes no part and is counted.  Over the sorted
 // valid keys let
@@ -45,40 +45,13 @@
 // a launch workgroups meet in integer atomics only.  Grids are bounded (AX_MAX_GRID workgroups stride over the tiles).
 #include "rsx_common.h"
 #include "auc_sort_device.h"
+#include "eval_device.h"      // the example rule and the append kernel, the workgroup scans, the key predicates, the tile load
 
 namespace {
-typedef unsigned long long ull;
-constexpr uint64_t AG_PAD = ~0ull;
-constexpr int AG_T = 256;               // append
 constexpr int AG_MAX_PASSES = 8;        // 4 + ceil(31 / 8)
 constexpr int AG_HDR = 8;               // header words (the last one is zero)
 
-static_assert(AX_IPL == 4, "a lane's keys are loaded as two 16-byte vectors");
-
-// ---- append ------------------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(AG_T) void ag_append_k(const float* __restrict__ prob, const float* __restrict__ labels,
-                                                    const int32_t* __restrict__ groups, int64_t gstride, int64_t n, uint32_t glimit,
-                                                    uint64_t* __restrict__ keys, ull* invalid_word) {
-  __shared__ unsigned int bad;
-  if (threadIdx.x == 0) bad = 0u;
-  __syncthreads();
-  unsigned int mine = 0u;
-  for (int64_t i = (int64_t)blockIdx.x * AG_T + threadIdx.x; i < n; i += (int64_t)gridDim.x * AG_T) {
-    uint32_t u = __float_as_uint(prob[i]);
-    if (u == 0x80000000u) u = 0u;                         // -0.0 is +0.0
-    const uint32_t g = (uint32_t)groups[i * gstride];     // a negative id compares above every limit (<= 2^31)
-    const bool valid = u <= 0x3F800000u && g < glimit;
-    const uint32_t pos = labels[i] > 0.5f ? 1u : 0u;
-    keys[i] = valid ? (((uint64_t)g << 32) | (uint64_t)((u << 1) | pos)) : AG_PAD;
-    mine += valid ? 0u : 1u;
-  }
-#pragma unroll
-  for (int d = 32; d > 0; d >>= 1) mine += (unsigned int)__shfl_xor((int)mine, d);
-  if ((threadIdx.x & 63) == 0 && mine) atomicAdd(&bad, mine);
-  __syncthreads();
-  if (threadIdx.x == 0 && bad) atomicAdd(invalid_word, (ull)bad);
-}
-
+// ---- append: ev_append_k<uint64_t, true> of csrc/eval_device.h ----------------------------------------------------------------
 __global__ __launch_bounds__(AX_T) void ag_zero_k(uint32_t* dtot, ull* hdr) {
   for (int i = threadIdx.x; i < AG_MAX_PASSES * AX_BINS; i += AX_T) dtot[i] = 0u;
   if (threadIdx.x < AG_HDR) hdr[threadIdx.x] = 0ull;
@@ -100,70 +73,15 @@ struct AgRed {
   int n, nT;
 };
 
-struct AgTile {
-  uint64_t k[AX_IPL];
-  uint64_t prev;       // the key in front of k[0] (padding in front of position 0: position 0 is a head)
+struct AgTile : EvTile<uint64_t> {
   uint64_t next;       // the key behind k[3] (padding behind position n - 1: position n - 1 is a tail)
-  uint32_t excl;       // negatives of the tile in front of k[0]
-  uint32_t total;      // negatives of the tile
 };
-
-__device__ __forceinline__ bool ag_valid(uint64_t k) { return k != AG_PAD; }
-__device__ __forceinline__ bool ag_neg(uint64_t k) { return ag_valid(k) && (k & 1ull) == 0ull; }
-__device__ __forceinline__ bool ag_pos(uint64_t k) { return ag_valid(k) && (k & 1ull) != 0ull; }
-__device__ __forceinline__ bool ag_shead(uint64_t k, uint64_t pk) { return ag_valid(k) && (k >> 1) != (pk >> 1); }
-__device__ __forceinline__ bool ag_ghead(uint64_t k, uint64_t pk) { return ag_valid(k) && (k >> 32) != (pk >> 32); }
-__device__ __forceinline__ bool ag_tail(uint64_t k, uint64_t nk) { return ag_valid(k) && (k >> 32) != (nk >> 32); }
-
-template <bool MAX, typename T>
-__device__ __forceinline__ T ag_op(T a, T b) {
-  return MAX ? (a > b ? a : b) : a + b;
-}
-
-// Exclusive sum or running maximum of v over the workgroup's AX_T threads (unsigned values: the identity of both is 0); total:
-// over all threads.  lds: AX_W words.  Ends with every thread past the barrier that makes lds reusable.
-template <bool MAX, typename T>
-__device__ __forceinline__ T ag_block_excl(T v, T* lds, T& total) {
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  T incl = v;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const T o = __shfl_up(incl, d);
-    if (lane >= d) incl = ag_op<MAX>(incl, o);
-  }
-  if (lane == 63) lds[w] = incl;
-  T ex = __shfl_up(incl, 1);
-  if (lane == 0) ex = (T)0;
-  __syncthreads();
-  T pre = (T)0, tot = (T)0;
-#pragma unroll
-  for (int ww = 0; ww < AX_W; ++ww) {
-    const T x = lds[ww];
-    if (ww < w) pre = ag_op<MAX>(pre, x);
-    tot = ag_op<MAX>(tot, x);
-  }
-  __syncthreads();
-  total = tot;
-  return ag_op<MAX>(pre, ex);
-}
 
 // thread tid holds the tile's keys 4 tid .. 4 tid + 3
 __device__ __forceinline__ void ag_load_tile(const AgRed& a, int t, uint32_t* lds, AgTile& s) {
-  const int i0 = t * AX_TILE + (int)threadIdx.x * AX_IPL;
-  if (i0 + AX_IPL <= a.n) {
-    const ulonglong2* q = reinterpret_cast<const ulonglong2*>(a.keys + i0);
-    const ulonglong2 q0 = q[0], q1 = q[1];
-    s.k[0] = q0.x; s.k[1] = q0.y; s.k[2] = q1.x; s.k[3] = q1.y;
-  } else {
-#pragma unroll
-    for (int k = 0; k < AX_IPL; ++k) s.k[k] = i0 + k < a.n ? a.keys[i0 + k] : AG_PAD;
-  }
-  s.prev = (i0 > 0 && i0 <= a.n) ? a.keys[i0 - 1] : AG_PAD;
-  s.next = i0 + AX_IPL < a.n ? a.keys[i0 + AX_IPL] : AG_PAD;
-  uint32_t c = 0u;
-#pragma unroll
-  for (int k = 0; k < AX_IPL; ++k) c += ag_neg(s.k[k]) ? 1u : 0u;
-  s.excl = ag_block_excl<false>(c, lds, s.total);
+  const int i1 = t * AX_TILE + ((int)threadIdx.x + 1) * AX_IPL;
+  s.next = i1 < a.n ? a.keys[i1] : ~0ull;
+  ev_load_tile(a.keys, a.n, t, lds, s);
 }
 
 __global__ __launch_bounds__(AX_T) void ag_counts_k(const AgRed a) {
@@ -177,19 +95,19 @@ __global__ __launch_bounds__(AX_T) void ag_counts_k(const AgRed a) {
 #pragma unroll
     for (int k = 0; k < AX_IPL; ++k) {
       const uint64_t pk = k == 0 ? s.prev : s.k[k - 1];
-      if (ag_shead(s.k[k], pk)) lh = run + 1u;
-      if (ag_ghead(s.k[k], pk)) {
+      if (ev_shead(s.k[k], pk)) lh = run + 1u;
+      if (ev_ghead(s.k[k], pk)) {
         lg = run + 1u;
         lq = (uint32_t)(tid * AX_IPL + k) + 1u;
       }
-      run += ag_neg(s.k[k]) ? 1u : 0u;
-      pc += ag_pos(s.k[k]) ? 1u : 0u;
+      run += ev_neg(s.k[k]) ? 1u : 0u;
+      pc += ev_pos(s.k[k]) ? 1u : 0u;
     }
     uint32_t mh, mg, mq, ptot;
-    ag_block_excl<true>(lh, l32, mh);
-    ag_block_excl<true>(lg, l32, mg);
-    ag_block_excl<true>(lq, l32, mq);
-    ag_block_excl<false>(pc, l32, ptot);
+    ev_block_excl<true, AX_W>(lh, l32, mh);
+    ev_block_excl<true, AX_W>(lg, l32, mg);
+    ev_block_excl<true, AX_W>(lq, l32, mq);
+    ev_block_excl<false, AX_W>(pc, l32, ptot);
     if (tid == 0) {
       a.tneg[t] = s.total;
       a.thead[t] = mh;
@@ -201,22 +119,6 @@ __global__ __launch_bounds__(AX_T) void ag_counts_k(const AgRed a) {
   if (tid == 0 && positives) atomicAdd(&a.hdr[5], positives);
 }
 
-// ONE workgroup: exclusive scan of arr[0 .. nT) in place, of the values pre(t, arr[t]); returns the total.  Thread tid handles
-// the tiles t0 + tid, so pre may read what the same thread wrote to another array in an earlier scan of this launch.
-template <bool MAX, typename T, typename F>
-__device__ __forceinline__ T ag_tiles_scan(T* arr, int nT, T* lds, F pre) {
-  T carry = (T)0;
-  for (int t0 = 0; t0 < nT; t0 += AX_T) {
-    const int t = t0 + (int)threadIdx.x;
-    const T v = t < nT ? pre(t, arr[t]) : (T)0;
-    T tot;
-    const T ex = ag_block_excl<MAX>(v, lds, tot);
-    if (t < nT) arr[t] = ag_op<MAX>(carry, ex);
-    carry = ag_op<MAX>(carry, tot);
-  }
-  return carry;
-}
-
 // phase 0 (after counts): negatives in front of every tile; h, b and q in front of it (the running maxima of the tiles' last-head
 // values made global: c and the position never decrease, so "the last" is "the largest"; 0 when there is none, which only the
 // first tile sees, whose first key is a head itself); the header's totals.
@@ -225,11 +127,11 @@ __global__ __launch_bounds__(AX_T) void ag_scan_k(const AgRed a, int phase) {
   __shared__ uint32_t l32[AX_W];
   __shared__ ull l64[AX_W];
   if (phase == 0) {
-    const uint32_t N = ag_tiles_scan<false>(a.tneg, a.nT, l32, [](int, uint32_t v) { return v; });
+    const uint32_t N = ev_tiles_scan<false, AX_W>(a.tneg, a.nT, l32, [](int, uint32_t v) { return v; });
     const auto to_c = [&](int t, uint32_t l) { return l ? a.tneg[t] + l - 1u : 0u; };
-    ag_tiles_scan<true>(a.thead, a.nT, l32, to_c);
-    ag_tiles_scan<true>(a.tgrp, a.nT, l32, to_c);
-    ag_tiles_scan<true>(a.tq, a.nT, l32, [](int t, uint32_t l) { return l ? (uint32_t)t * AX_TILE + l - 1u : 0u; });
+    ev_tiles_scan<true, AX_W>(a.thead, a.nT, l32, to_c);
+    ev_tiles_scan<true, AX_W>(a.tgrp, a.nT, l32, to_c);
+    ev_tiles_scan<true, AX_W>(a.tq, a.nT, l32, [](int t, uint32_t l) { return l ? (uint32_t)t * AX_TILE + l - 1u : 0u; });
     if (threadIdx.x == 0) {
       const ull P = a.hdr[5];
       a.hdr[6] = N;
@@ -237,10 +139,10 @@ __global__ __launch_bounds__(AX_T) void ag_scan_k(const AgRed a, int phase) {
       a.hdr[1] = (ull)a.n - P - N;
     }
   } else if (phase == 1) {
-    ag_tiles_scan<false>(a.tU, a.nT, l64, [](int, ull v) { return v; });
-    ag_tiles_scan<true>(a.tsb, a.nT, l64, [&](int t, ull l) { return l ? a.tU[t] + l - 1ull : 0ull; });
+    ev_tiles_scan<false, AX_W>(a.tU, a.nT, l64, [](int, ull v) { return v; });
+    ev_tiles_scan<true, AX_W>(a.tsb, a.nT, l64, [&](int t, ull l) { return l ? a.tU[t] + l - 1ull : 0ull; });
   } else {
-    const uint32_t M = ag_tiles_scan<false>(a.tmix, a.nT, l32, [](int, uint32_t v) { return v; });
+    const uint32_t M = ev_tiles_scan<false, AX_W>(a.tmix, a.nT, l32, [](int, uint32_t v) { return v; });
     if (threadIdx.x == 0) a.hdr[3] = M;
   }
 }
@@ -265,22 +167,22 @@ __global__ __launch_bounds__(AX_T) void ag_pass_k(const AgRed a) {
     for (int k = 0; k < AX_IPL; ++k) {
       const uint64_t pk = k == 0 ? s.prev : s.k[k - 1];
       c[k] = run;
-      sh[k] = ag_shead(s.k[k], pk);
-      gh[k] = ag_ghead(s.k[k], pk);
+      sh[k] = ev_shead(s.k[k], pk);
+      gh[k] = ev_ghead(s.k[k], pk);
       if (sh[k]) hv = run;
       if (gh[k]) {
         bv = run;
         qv = p0 + (uint32_t)k;
       }
-      run += ag_neg(s.k[k]) ? 1u : 0u;
+      run += ev_neg(s.k[k]) ? 1u : 0u;
     }
     uint32_t m32;
-    uint32_t ch = ag_block_excl<true>(hv, l32, m32);
-    uint32_t cb = ag_block_excl<true>(bv, l32, m32);
-    uint32_t cq = ag_block_excl<true>(qv, l32, m32);
-    ch = ag_op<true>(ch, a.thead[t]);
-    cb = ag_op<true>(cb, a.tgrp[t]);
-    cq = ag_op<true>(cq, a.tq[t]);
+    uint32_t ch = ev_block_excl<true, AX_W>(hv, l32, m32);
+    uint32_t cb = ev_block_excl<true, AX_W>(bv, l32, m32);
+    uint32_t cq = ev_block_excl<true, AX_W>(qv, l32, m32);
+    ch = ev_op<true>(ch, a.thead[t]);
+    cb = ev_op<true>(cb, a.tgrp[t]);
+    cq = ev_op<true>(cq, a.tq[t]);
     ull con[AX_IPL], mine = 0ull;
     uint32_t bb[AX_IPL], qq[AX_IPL];
 #pragma unroll
@@ -292,11 +194,11 @@ __global__ __launch_bounds__(AX_T) void ag_pass_k(const AgRed a) {
       }
       bb[k] = cb;
       qq[k] = cq;
-      con[k] = ag_pos(s.k[k]) ? (ull)(c[k] - cb) + (ull)(ch - cb) : 0ull;
+      con[k] = ev_pos(s.k[k]) ? (ull)(c[k] - cb) + (ull)(ch - cb) : 0ull;
       mine += con[k];
     }
     ull tot64;
-    ull S = ag_block_excl<false>(mine, l64, tot64);       // S of k[0]: local in MODE 1, global otherwise
+    ull S = ev_block_excl<false, AX_W>(mine, l64, tot64);       // S of k[0]: local in MODE 1, global otherwise
     if (MODE != 1) S += a.tU[t];
     ull sv = 0ull;                                        // S at my last group head (MODE 1: + 1, 0 = none)
     {
@@ -308,14 +210,14 @@ __global__ __launch_bounds__(AX_T) void ag_pass_k(const AgRed a) {
       }
     }
     ull m64;
-    ull csb = ag_block_excl<true>(sv, l64, m64);
+    ull csb = ev_block_excl<true, AX_W>(sv, l64, m64);
     if (MODE == 1) {
       if (tid == 0) {
         a.tU[t] = tot64;
         a.tsb[t] = m64;
       }
     } else {
-      csb = ag_op<true>(csb, a.tsb[t]);
+      csb = ev_op<true>(csb, a.tsb[t]);
       ull gP[AX_IPL], gN[AX_IPL], gU[AX_IPL];
       bool mixed[AX_IPL];
       uint32_t nmix = 0u;
@@ -324,8 +226,8 @@ __global__ __launch_bounds__(AX_T) void ag_pass_k(const AgRed a) {
       for (int k = 0; k < AX_IPL; ++k) {
         if (gh[k]) csb = r;
         mixed[k] = false;
-        if (ag_tail(s.k[k], k == AX_IPL - 1 ? s.next : s.k[k + 1])) {
-          const uint32_t Ng = c[k] + (ag_neg(s.k[k]) ? 1u : 0u) - bb[k];
+        if (ev_gtail(s.k[k], k == AX_IPL - 1 ? s.next : s.k[k + 1])) {
+          const uint32_t Ng = c[k] + (ev_neg(s.k[k]) ? 1u : 0u) - bb[k];
           const uint32_t ng = p0 + (uint32_t)k + 1u - qq[k];
           gN[k] = Ng;
           gP[k] = ng - Ng;
@@ -340,7 +242,7 @@ __global__ __launch_bounds__(AX_T) void ag_pass_k(const AgRed a) {
         r += con[k];
       }
       uint32_t tmixed;
-      uint32_t slot = ag_block_excl<false>(nmix, l32, tmixed);
+      uint32_t slot = ev_block_excl<false, AX_W>(nmix, l32, tmixed);
       if (MODE == 2) {
         if (tid == 0) a.tmix[t] = tmixed;
       } else {
@@ -361,8 +263,8 @@ __global__ __launch_bounds__(AX_T) void ag_pass_k(const AgRed a) {
   }
   if (MODE == 2) {
     ull tg, ts;
-    ag_block_excl<false>(groups, l64, tg);
-    ag_block_excl<false>(skipped, l64, ts);
+    ev_block_excl<false, AX_W>(groups, l64, tg);
+    ev_block_excl<false, AX_W>(skipped, l64, ts);
     if (tid == 0) {
       if (tg) atomicAdd(&a.hdr[2], tg);
       if (ts) atomicAdd(&a.hdr[4], ts);
@@ -424,10 +326,8 @@ extern "C" int rsx_auc_group_append(const float* prob, const float* labels, cons
   if (group_bits < 1 || group_bits > 31 || group_stride < 1) return RSX_EINVAL;
   if (reinterpret_cast<uintptr_t>(keys_at_offset) & 7u) return RSX_EINVAL;
   if (n == 0) return RSX_OK;
-  int64_t blocks = (n + AG_T - 1) / AG_T;
-  if (blocks > 256) blocks = 256;
-  RSX_LAUNCH(ag_append_k, dim3((unsigned)blocks), dim3(AG_T), 0, rsx_s(stream), prob, labels, groups, group_stride, n,
-             1u << group_bits, keys_at_offset, reinterpret_cast<ull*>(invalid_word));
+  ev_append<uint64_t, true>(prob, labels, groups, group_stride, n, 1u << group_bits, keys_at_offset, invalid_word,
+                            rsx_s(stream));
   RSX_CHECK_LAUNCH();
   return RSX_OK;
 }

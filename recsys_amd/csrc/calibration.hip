@@ -2,9 +2,9 @@
 // and their per-slice forms are made of, accumulated on the device beside the rank statistics of csrc/metrics.hip,
 // csrc/auc_exact.hip and csrc/auc_group.hip.  Opt-in; it changes none of them.
 //
-// THE CONTRACT, in integers.  An example is (fp32 p, label y[, group g]).  It is positive when y > 0.5f (metrics.hip's rule) and
-// valid when 0 <= p <= 1 by auc_exact.hip's bit test (-0.0 counts as +0.0; NaN, infinities, everything else: invalid) and, when a
-// group column is given, 0 <= g < n_groups.  An invalid example enters no table and is counted.  Of a valid example
+// THE CONTRACT, in integers.  An example is (fp32 p, label y[, group g]).  Whether it is positive and whether p is valid
+// (0 <= p <= 1) is the example rule of csrc/eval_device.h, as is q below; with a group column the example is valid only when
+// 0 <= g < n_groups too.  An invalid example enters no table and is counted.  Of a valid example
 //     bin  b = min(n_bins - 1, int(p * float(n_bins)))     ONE fp32 multiply, rounded to nearest, then truncated: the arithmetic is
 //                                                          the definition (a p one ulp below k / n_bins may land in bin k)
 //     q    = uint64(double(p) * 2^32)                      the product is exact in fp64; the conversion truncates; q <= 2^32
@@ -21,9 +21,9 @@
 // positives and a zero q nothing to q_sum.  The invalid count: one atomic per workgroup.  No allocation, no workspace, no
 // synchronisation, nothing zeroed: the caller zeroes the state once.
 #include "rsx_common.h"
+#include "eval_device.h"      // the example rule, q, the group-id test, the invalid-count flush
 
 namespace {
-typedef unsigned long long ull;
 constexpr int CAL_T = 256;
 constexpr int CAL_MAX_BINS = 1024;
 constexpr int64_t CAL_MAX_GROUPS = 1ll << 22;
@@ -35,28 +35,23 @@ __global__ __launch_bounds__(CAL_T) void cal_update_k(const float* __restrict__ 
                                                       uint32_t n_groups, ull* bins, ull* group_table, ull* invalid_word) {
   __shared__ unsigned int h_count[CAL_MAX_BINS], h_pos[CAL_MAX_BINS];
   __shared__ ull h_q[CAL_MAX_BINS];
-  __shared__ unsigned int bad;
   for (int i = threadIdx.x; i < n_bins; i += CAL_T) {
     h_count[i] = 0u;
     h_pos[i] = 0u;
     h_q[i] = 0ull;
   }
-  if (threadIdx.x == 0) bad = 0u;
   __syncthreads();
   const float fbins = (float)n_bins;
-  unsigned int mine = 0u;
+  unsigned int wave_bad = 0u;
   for (int64_t i = (int64_t)blockIdx.x * CAL_T + threadIdx.x; i < n; i += (int64_t)gridDim.x * CAL_T) {
-    uint32_t u = __float_as_uint(prob[i]);
-    if (u == 0x80000000u) u = 0u;                         // -0.0 is +0.0
-    const bool pos = labels[i] > 0.5f;
-    const uint32_t g = n_groups ? (uint32_t)groups[i * gstride] : 0u;   // a negative id compares above every limit (<= 2^22)
-    const bool valid = u <= 0x3F800000u && (n_groups == 0u || g < n_groups);
-    if (!valid) {
-      mine += 1u;
-      continue;
-    }
-    const float p = __uint_as_float(u);
-    const ull q = (ull)((double)p * 4294967296.0);
+    const EvExample e = ev_example(prob[i], labels[i]);
+    const int32_t g = n_groups ? groups[i * gstride] : 0;
+    const bool bad = !e.valid || (n_groups && !ev_group_ok(g, n_groups));
+    wave_bad += ev_count_invalid(bad);
+    if (bad) continue;
+    const bool pos = e.pos;
+    const float p = __uint_as_float(e.u);
+    const ull q = ev_q(e.u);
     if (n_bins) {
       int b = (int)(p * fbins);
       b = b < n_bins - 1 ? b : n_bins - 1;
@@ -71,16 +66,12 @@ __global__ __launch_bounds__(CAL_T) void cal_update_k(const float* __restrict__ 
       if (q) atomicAdd(row + 2, q);
     }
   }
-#pragma unroll
-  for (int d = 32; d > 0; d >>= 1) mine += (unsigned int)__shfl_xor((int)mine, d);
-  if ((threadIdx.x & 63) == 0 && mine) atomicAdd(&bad, mine);
-  __syncthreads();
+  ev_flush_invalid<CAL_T / 64>(wave_bad, invalid_word);      // its barrier stands between the LDS atomics above and the reads below
   for (int i = threadIdx.x; i < n_bins; i += CAL_T) {
     if (h_count[i]) atomicAdd(&bins[3 * i], (ull)h_count[i]);
     if (h_pos[i]) atomicAdd(&bins[3 * i + 1], (ull)h_pos[i]);
     if (h_q[i]) atomicAdd(&bins[3 * i + 2], h_q[i]);
   }
-  if (threadIdx.x == 0 && bad) atomicAdd(invalid_word, (ull)bad);
 }
 }  // namespace
 

@@ -18,8 +18,8 @@
 // rate) but correct; DESIGN.md section 11c has the measured price.
 //
 // THE MAP, in fp32 (compiled with -ffp-contract=off and IEEE division).  Knots x[0 .. K) strictly increasing, y[0 .. K)
-// non-decreasing, 1 <= K <= 1024.  A p outside [0, 1] by auc_exact.hip's bit test is returned unchanged, bit for bit; -0.0 counts
-// as +0.0.  p <= x[0] -> y[0]; p >= x[K-1] -> y[K-1]; otherwise with j the largest index with x[j] <= p
+// non-decreasing, 1 <= K <= 1024.  A p outside [0, 1] by the example rule of csrc/eval_device.h (-0.0 counts as +0.0) is returned
+// unchanged, bit for bit.  p <= x[0] -> y[0]; p >= x[K-1] -> y[K-1]; otherwise with j the largest index with x[j] <= p
 //     t = (p - x[j]) / (x[j+1] - x[j]);  o = y[j] + t * (y[j+1] - y[j]);  out = o < y[j+1] ? o : y[j+1]
 // one subtraction on each side, one division, one multiply, one add, one minimum, in that order.
 //
@@ -29,9 +29,9 @@
 // scalar.  Every element is read and written by the same thread: prob_out may equal prob_in (it may not overlap it otherwise).
 // Nothing is allocated and nothing synchronises: the launch can be captured into a graph.
 #include "rsx_common.h"
+#include "eval_device.h"      // the example rule, q, the workgroup reduction
 
 namespace {
-typedef unsigned long long ull;
 constexpr int CM_T = 256;
 constexpr int CM_W = CM_T / RSX_WAVE;
 constexpr int CM_MAX_BINS = 1024;         // rsx_calibration_max_bins()
@@ -54,14 +54,14 @@ __device__ int64_t cm_first_head(const uint32_t* __restrict__ ks, int64_t V, int
 
 __device__ __forceinline__ void cm_take(uint32_t k, ull& pos, ull& q) {
   pos += k & 1u;
-  q += (ull)((double)__uint_as_float(k >> 1) * 4294967296.0);
+  q += ev_q(k >> 1);
 }
 
 __global__ __launch_bounds__(CM_T) void cm_quantile_table_k(const uint32_t* __restrict__ ks, int64_t V, int M,
                                                             ull* __restrict__ table) {
   __shared__ int64_t range[2];
-  __shared__ ull wpos[CM_W], wq[CM_W];
-  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, b = blockIdx.x;
+  __shared__ ull lpos[CM_W], lq[CM_W];
+  const int tid = threadIdx.x, b = blockIdx.x;
   if (tid < 2) {
     const int bb = b + tid;
     range[tid] = bb >= M ? V : cm_first_head(ks, V, ((int64_t)bb * V + M - 1) / M);
@@ -81,19 +81,8 @@ __global__ __launch_bounds__(CM_T) void cm_quantile_table_k(const uint32_t* __re
     cm_take(v.w, pos, q);
   }
   if (a1 + tid < hi) cm_take(ks[a1 + tid], pos, q);
-#pragma unroll
-  for (int d = 32; d > 0; d >>= 1) {
-    const ull op = ((ull)(uint32_t)__shfl_xor((int)(uint32_t)(pos >> 32), d) << 32) | (uint32_t)__shfl_xor((int)(uint32_t)pos, d);
-    const ull oq = ((ull)(uint32_t)__shfl_xor((int)(uint32_t)(q >> 32), d) << 32) | (uint32_t)__shfl_xor((int)(uint32_t)q, d);
-    pos += op;
-    q += oq;
-  }
-  if (lane == 0) { wpos[w] = pos; wq[w] = q; }
-  __syncthreads();
+  const ull p = ev_block_reduce<false, CM_W>(pos, lpos), s = ev_block_reduce<false, CM_W>(q, lq);
   if (tid == 0) {
-    ull p = 0ull, s = 0ull;
-#pragma unroll
-    for (int ww = 0; ww < CM_W; ++ww) { p += wpos[ww]; s += wq[ww]; }
     table[3 * b] = (ull)(hi - lo);
     table[3 * b + 1] = p;
     table[3 * b + 2] = s;
@@ -101,10 +90,9 @@ __global__ __launch_bounds__(CM_T) void cm_quantile_table_k(const uint32_t* __re
 }
 
 __device__ __forceinline__ float cm_map(float p, const float* sx, const float* sy, int K) {
-  uint32_t u = __float_as_uint(p);
-  if (u == 0x80000000u) u = 0u;           // -0.0 is +0.0
-  if (u > 0x3F800000u) return p;          // outside [0, 1], NaN, infinities: unchanged, bit for bit
-  const float v = __uint_as_float(u);
+  const EvExample e = ev_example(p, 0.f);
+  if (!e.valid) return p;                 // outside [0, 1], NaN, infinities: unchanged, bit for bit
+  const float v = __uint_as_float(e.u);   // -0.0 is +0.0
   if (v <= sx[0]) return sy[0];
   if (v >= sx[K - 1]) return sy[K - 1];
   int lo = 0, hi = K - 1;                 // x[lo] <= v < x[hi]

@@ -1007,59 +1007,13 @@ class Estimator:
         """Estimator.evaluate (fm/fm.py:216-221): AUC-200 / Accuracy / mean batch loss accumulated ON DEVICE by one
         launch per batch (metrics.EvalMetrics); the host synchronises once, when the counters are read back.
         Data-parallel: every rank evaluates its own shard of the eval stream and the integer counters are summed.
-        RunConfig.exact_auc adds "AUC_exact" (metrics.ExactAUC: one more launch per batch, one sort and one more device->host
-        copy at the end; nan, with a WARNING line, when a probability was outside [0, 1]); single replica only.
-        RunConfig.group_auc_key adds "GAUC", "GAUC_groups" and "GAUC_skipped_examples" (metrics.GroupAUC: one more launch per
-        batch; at the end one sort, the header's copy, one records launch and the records' copy); single replica only.
-        RunConfig.calibration_bins adds "ECE", "MCE", "PCOC" and "NE" (NE from this call's loss), RunConfig.calibration_key "GCE"
-        and "GCE_groups" (metrics.Calibration: one more launch per batch for both, one more device->host copy at the end; nan,
-        with a WARNING line, when an example was invalid); the full result stays in `last_calibration`; single replica only.
-        RunConfig.calibration_fit = M fits an isotonic map from this call's examples (an ExactAUC is kept whether or not exact_auc
-        is set; after the last batch ONE launch of rsx_calibration_quantile_table and a copy of 24 M bytes, then
-        metrics.isotonic_from_table on the host): `last_calibration_map`, <model_dir>/calibration-<global_step>.json (the chief
-        writes it, temporary name and rename), "calibration_knots" in the result (0 when the fit is refused: an invalid example,
-        or no positive or no negative -- one WARNING line, no file).  RunConfig.calibration_apply maps every batch's prob through
-        the map of the current global_step into a second buffer (rsx_calibrate_apply, same stream) and adds "ECE_cal", "MCE_cal"
-        and "PCOC_cal" from a second bin table; every other key keeps its raw value.  Refused before the first batch is read:
-        calibration_apply without calibration_bins or without a map of this step, both settings together, M outside 2..1024, a
-        second rank.  A logloss / NE of the mapped probabilities is out of scope."""
+        The opt-in settings of RunConfig -- exact_auc, group_auc_key, calibration_bins / calibration_key, calibration_fit /
+        calibration_apply -- are one object each (_ExactKeys, _GroupAUCSetting, _CalibrationSetting, _CalibrationMapSetting below;
+        their docstrings say what each adds): built in that order before the first batch is read, which is where a bad setting
+        or a second rank is refused; updated in that order behind EvalMetrics.update on the same stream; reported in that order."""
         self._check_consistent("evaluate")
-        exact = bool(getattr(self.config, "exact_auc", False))
-        if exact:                         # refused before the first batch is read
-            _metrics.check_exact_auc_world(1 if self.store.dp is None else self.store.dp.world)
-        gkey = getattr(self.config, "group_auc_key", None)
-        if gkey:                          # an unknown key and a second rank are refused before the first batch is read, too
-            _metrics.check_group_auc_world(1 if self.store.dp is None else self.store.dp.world)
-            group_of, group_bits = self._group_auc_source(gkey)
-        cbins, ckey = int(getattr(self.config, "calibration_bins", 0) or 0), getattr(self.config, "calibration_key", None)
-        cal = None                        # metrics.Calibration: a bad setting is refused here, before the first batch is read
-        if cbins or ckey:
-            _metrics.check_calibration_world(1 if self.store.dp is None else self.store.dp.world)
-            cal_group_of, cal_groups = self._group_column(ckey, "calibration_key") if ckey else (None, None)
-            cal = _metrics.Calibration(self.store.device, cbins or None, cal_groups)
-        cfit, capply = int(getattr(self.config, "calibration_fit", 0) or 0), bool(getattr(self.config, "calibration_apply", False))
-        cmap = cal2 = cbuf = None         # calibration_apply: the Calibrator, the mapped probabilities' bin table and buffer
-        if cfit or capply:                # refused here, before the first batch is read
-            _metrics.check_calibration_map_world(1 if self.store.dp is None else self.store.dp.world)
-            if cfit and capply:
-                raise _metrics.RsxError("calibration_fit and calibration_apply in one evaluate() would report in-sample figures: "
-                                        "fit on one evaluation, apply in another")
-            if cfit and not _metrics.CALIBRATION_MIN_BINS <= cfit <= 1024:
-                raise _metrics.RsxError("calibration_fit %d is outside %d..1024" % (cfit, _metrics.CALIBRATION_MIN_BINS))
-            if capply:
-                if not cbins:
-                    raise _metrics.RsxError("calibration_apply needs calibration_bins: ECE_cal is a figure of that table")
-                step = self._calibration_step()
-                m = self.calibration_map_for_step(step)
-                if m is None:
-                    raise _metrics.RsxError("calibration_apply: no calibration map for global step %d (neither last_calibration_map "
-                                            "nor %s); run evaluate() with calibration_fit first"
-                                            % (step, self._calibration_path(step) or "a model_dir"))
-                cmap = _metrics.Calibrator(self.store.device, m)
-                cal2 = _metrics.Calibration(self.store.device, cbins)
+        settings = self._eval_settings(steps)
         met = _metrics.EvalMetrics(self.store.device)
-        ex = None                         # metrics.ExactAUC, sized by the first batch: the append launches follow met.update's
-        ga = None                         # metrics.GroupAUC, likewise
         n = 0
         it = input_fn()
         try:
@@ -1069,25 +1023,12 @@ class Estimator:
                         break
                     prob, loss, lab = self._infer_step(features, labels, ModeKeys.EVAL)
                     met.update(lab, prob, loss)
-                    if exact or cfit:
-                        if ex is None:
-                            ex = _metrics.ExactAUC(self.store.device,
-                                                   None if steps is None else max(1, int(steps) * int(prob.numel())))
-                        ex.update(lab, prob)
-                    if gkey:
-                        if ga is None:
-                            ga = _metrics.GroupAUC(self.store.device, group_bits,
-                                                   None if steps is None else max(1, int(steps) * int(prob.numel())))
+                    if settings:
                         # the device copy of the batch that _infer_step just used (the graph's static buffer or the eager
-                        # copy): ids[:, slot] is read in place, behind the forward on the same stream
-                        ga.update(group_of(getattr(self, "_infer_features", None) or features), lab, prob)
-                    if cal is not None:   # the same device copy of the batch, the same stream
-                        cal.update(lab, prob, cal_group_of(getattr(self, "_infer_features", None) or features) if ckey else None)
-                    if cmap is not None:  # into a buffer of its own (prob may be the graph's static output), the same stream
-                        p1 = prob if prob.dtype == torch.float32 and prob.is_contiguous() else prob.to(torch.float32).contiguous()
-                        if cbuf is None or cbuf.numel() != p1.numel():      # (the last batch of a stream may be a partial one)
-                            cbuf = torch.empty(p1.numel(), dtype=torch.float32, device=p1.device)
-                        cal2.update(lab, cmap.apply(p1, out=cbuf))
+                        # copy): a group column is read in place, behind the forward on the same stream
+                        on_device = getattr(self, "_infer_features", None) or features
+                        for s in settings:
+                            s.update(lab, prob, on_device)
                     n += 1
         finally:
             _close_iter(it)
@@ -1097,47 +1038,25 @@ class Estimator:
         res = {"AUC": res["AUC"], "Accuracy": res["Accuracy"], "loss": res["loss"], "global_step": self.global_step}
         line = ("INFO:Saving dict for global step %d: AUC = %.7g, Accuracy = %.7g, global_step = %d, loss = %.7g"
                 % (res["global_step"], res["AUC"], res["Accuracy"], res["global_step"], res["loss"]))
-        if exact or cfit:
-            ex = ex or _metrics.ExactAUC(self.store.device, 1)
-            xr = ex.result()
-        if exact:
-            res["AUC_exact"] = _metrics.exact_auc_reported(xr)
-            if xr["invalid"] and self._is_chief():
-                print("WARNING:exact_auc: %d of %d probabilities are outside [0, 1] or not finite; AUC_exact is nan"
-                      % (xr["invalid"], xr["invalid"] + xr["positives"] + xr["negatives"]), flush=True)
-            line += ", AUC_exact = %.7g" % res["AUC_exact"]
-        if gkey:
-            gr = (ga or _metrics.GroupAUC(self.store.device, group_bits, 1)).result()
-            res["GAUC"] = _metrics.group_auc_reported(gr)
-            res["GAUC_groups"] = gr["mixed_groups"]
-            res["GAUC_skipped_examples"] = gr["skipped_examples"]
-            if gr["invalid"] and self._is_chief():
-                print("WARNING:group_auc_key %s: %d examples have a probability outside [0, 1] or not finite, or an id outside "
-                      "[0, 2^%d); GAUC is nan" % (gkey, gr["invalid"], group_bits), flush=True)
-            line += ", GAUC = %.7g" % res["GAUC"]
-        if cal is not None:
-            cr = self.last_calibration = cal.result(loss=res["loss"], per_group=True)
-            if cbins:
-                res.update({k: v for k, v in _metrics.calibration_reported(cr).items() if k in ("ECE", "MCE", "PCOC", "NE")})
-                line += ", ECE = %.7g, PCOC = %.7g, NE = %.7g" % (res["ECE"], res["PCOC"], res["NE"])
-            if ckey:
-                res["GCE"] = _metrics.group_calibration_reported(cr)["GCE"]
-                res["GCE_groups"] = cr["GCE_groups"]
-                line += ", GCE = %.7g" % res["GCE"]
-            if cr["invalid"] and self._is_chief():
-                print("WARNING:calibration: %d of %d examples have a probability outside [0, 1] or not finite%s; the calibration "
-                      "figures are nan" % (cr["invalid"], cr["invalid"] + cr["examples"],
-                                           ", or a %s id outside [0, %d)" % (ckey, cal_groups) if ckey else ""), flush=True)
-        if cal2 is not None:
-            c2 = cal2.result()
-            rep = _metrics.calibration_reported(c2)
-            res.update({"ECE_cal": rep["ECE"], "MCE_cal": rep["MCE"], "PCOC_cal": rep["PCOC"]})
-            line += ", ECE_cal = %.7g, PCOC_cal = %.7g" % (res["ECE_cal"], res["PCOC_cal"])
+        for s in settings:
+            line += s.report(res)
         if self._is_chief():
             print(line, flush=True)
-        if cfit:
-            res["calibration_knots"] = self._fit_calibration_map(ex, xr, cfit)
+        for s in settings:
+            s.finish(res)
         return res
+
+    def _eval_settings(self, steps):
+        """RunConfig -> evaluate()'s opt-in settings, in update and report order."""
+        cfg = self.config
+        exact, fit = bool(getattr(cfg, "exact_auc", False)), int(getattr(cfg, "calibration_fit", 0) or 0)
+        gkey, ckey = getattr(cfg, "group_auc_key", None), getattr(cfg, "calibration_key", None)
+        bins, apply = int(getattr(cfg, "calibration_bins", 0) or 0), bool(getattr(cfg, "calibration_apply", False))
+        keys = _ExactKeys(self, steps, reported=exact) if exact or fit else None
+        return [s for s in (keys,
+                            _GroupAUCSetting(self, steps, gkey) if gkey else None,
+                            _CalibrationSetting(self, bins, ckey) if bins or ckey else None,
+                            _CalibrationMapSetting(self, keys, fit, apply, bins) if fit or apply else None) if s is not None]
 
     def _script_name(self):
         return self.model_fn.__module__.rsplit(".", 1)[-1]
@@ -1193,13 +1112,9 @@ class Estimator:
             print("INFO:calibration map: K = %d, V = %d, P = %d, path = %s" % (m.knots, V, P, path), flush=True)
         return m.knots
 
-    def _group_auc_source(self, key):
-        """RunConfig.group_auc_key -> (features -> the batch's group ids, group_bits)."""
-        group_of, n_rows = self._group_column(key, "group_auc_key")
-        return group_of, min(31, max(1, (n_rows - 1).bit_length()))
-
     def _group_column(self, key, setting):
-        """The key of RunConfig.group_auc_key / calibration_key -> (features -> the batch's group ids, the column's row count).
+        """The key of RunConfig.group_auc_key / calibration_key -> (features -> the batch's group ids, the column's row count;
+        GAUC's group_bits are the bits of row count - 1).
         Criteo scripts and --feature_set uid_iid: the key of an embedding column of the layout; the group is the column's
         table-local id, ids[:, slot] of the batch as it is (host or device, no copy here).  din.py: i_id / i_cate."""
         cols = self.params.get("embedding_feature_columns")
@@ -1421,6 +1336,170 @@ def _close_iter(it):
     close = getattr(it, "close", None)
     if close is not None:
         close()
+
+
+def _world(est):
+    return 1 if est.store.dp is None else est.store.dp.world
+
+
+class _EvalSetting:
+    """One opt-in setting of Estimator.evaluate().  The constructor refuses what the setting cannot do before the first batch is
+    read.  update(lab, prob, features): the batch's launches, behind EvalMetrics.update on the same stream, no synchronisation
+    (features: the device copy of the batch).  report(res): adds the result keys, prints the setting's WARNING line on the chief
+    and returns its part of the "INFO:Saving dict" line.  finish(res): what comes behind that line."""
+
+    def update(self, lab, prob, features):
+        pass
+
+    def report(self, res):
+        return ""
+
+    def finish(self, res):
+        pass
+
+
+def _first_batch_capacity(steps, prob):
+    """The key buffers are sized by the first batch: steps batches of its size, growable when steps is None."""
+    return None if steps is None else max(1, int(steps) * int(prob.numel()))
+
+
+class _ExactKeys(_EvalSetting):
+    """RunConfig.exact_auc: "AUC_exact" (metrics.ExactAUC: one more launch per batch, one sort and one more device->host copy at
+    the end; nan, with a WARNING line, when a probability was outside [0, 1]); single replica only.  calibration_fit reduces the
+    same sorted keys, so with either setting ONE ExactAUC is kept; without exact_auc nothing is reported."""
+
+    def __init__(self, est, steps, reported):
+        if reported:
+            _metrics.check_single_replica("exact_auc", _world(est))
+        self.est, self.steps, self.reported, self.acc, self.counts = est, steps, reported, None, None
+
+    def update(self, lab, prob, features):
+        if self.acc is None:
+            self.acc = _metrics.ExactAUC(self.est.store.device, _first_batch_capacity(self.steps, prob))
+        self.acc.update(lab, prob)
+
+    def report(self, res):
+        self.acc = self.acc or _metrics.ExactAUC(self.est.store.device, 1)
+        xr = self.counts = self.acc.result()
+        if not self.reported:
+            return ""
+        res["AUC_exact"] = _metrics.exact_auc_reported(xr)
+        if xr["invalid"] and self.est._is_chief():
+            print("WARNING:exact_auc: %d of %d probabilities are outside [0, 1] or not finite; AUC_exact is nan"
+                  % (xr["invalid"], xr["invalid"] + xr["positives"] + xr["negatives"]), flush=True)
+        return ", AUC_exact = %.7g" % res["AUC_exact"]
+
+
+class _GroupAUCSetting(_EvalSetting):
+    """RunConfig.group_auc_key: "GAUC", "GAUC_groups" and "GAUC_skipped_examples" (metrics.GroupAUC: one more launch per batch;
+    at the end one sort, the header's copy, one records launch and the records' copy); single replica only.  An unknown key is
+    refused by Estimator._group_column."""
+
+    def __init__(self, est, steps, key):
+        _metrics.check_single_replica("group_auc_key", _world(est))
+        self.group_of, n_rows = est._group_column(key, "group_auc_key")
+        self.bits = min(31, max(1, (n_rows - 1).bit_length()))
+        self.est, self.steps, self.key, self.acc = est, steps, key, None
+
+    def update(self, lab, prob, features):
+        if self.acc is None:
+            self.acc = _metrics.GroupAUC(self.est.store.device, self.bits, _first_batch_capacity(self.steps, prob))
+        self.acc.update(self.group_of(features), lab, prob)
+
+    def report(self, res):
+        gr = (self.acc or _metrics.GroupAUC(self.est.store.device, self.bits, 1)).result()
+        res["GAUC"] = _metrics.group_auc_reported(gr)
+        res["GAUC_groups"] = gr["mixed_groups"]
+        res["GAUC_skipped_examples"] = gr["skipped_examples"]
+        if gr["invalid"] and self.est._is_chief():
+            print("WARNING:group_auc_key %s: %d examples have a probability outside [0, 1] or not finite, or an id outside "
+                  "[0, 2^%d); GAUC is nan" % (self.key, gr["invalid"], self.bits), flush=True)
+        return ", GAUC = %.7g" % res["GAUC"]
+
+
+class _CalibrationSetting(_EvalSetting):
+    """RunConfig.calibration_bins: "ECE", "MCE", "PCOC" and "NE" (NE from this call's loss); RunConfig.calibration_key: "GCE" and
+    "GCE_groups" (metrics.Calibration: one more launch per batch for both, one more device->host copy at the end; nan, with a
+    WARNING line, when an example was invalid); the full result stays in Estimator.last_calibration; single replica only."""
+
+    def __init__(self, est, bins, key):
+        _metrics.check_single_replica("calibration", _world(est))
+        self.group_of, self.n_groups = est._group_column(key, "calibration_key") if key else (None, None)
+        self.acc = _metrics.Calibration(est.store.device, bins or None, self.n_groups)
+        self.est, self.bins, self.key = est, bins, key
+
+    def update(self, lab, prob, features):
+        self.acc.update(lab, prob, self.group_of(features) if self.key else None)
+
+    def report(self, res):
+        cr = self.est.last_calibration = self.acc.result(loss=res["loss"], per_group=True)
+        line = ""
+        if self.bins:
+            res.update({k: v for k, v in _metrics.calibration_reported(cr).items() if k in ("ECE", "MCE", "PCOC", "NE")})
+            line += ", ECE = %.7g, PCOC = %.7g, NE = %.7g" % (res["ECE"], res["PCOC"], res["NE"])
+        if self.key:
+            res["GCE"] = _metrics.group_calibration_reported(cr)["GCE"]
+            res["GCE_groups"] = cr["GCE_groups"]
+            line += ", GCE = %.7g" % res["GCE"]
+        if cr["invalid"] and self.est._is_chief():
+            print("WARNING:calibration: %d of %d examples have a probability outside [0, 1] or not finite%s; the calibration "
+                  "figures are nan" % (cr["invalid"], cr["invalid"] + cr["examples"],
+                                       ", or a %s id outside [0, %d)" % (self.key, self.n_groups) if self.key else ""), flush=True)
+        return line
+
+
+class _CalibrationMapSetting(_EvalSetting):
+    """RunConfig.calibration_fit = M: behind the INFO line, an isotonic map fitted from the keys _ExactKeys has sorted (ONE launch
+    of rsx_calibration_quantile_table and a copy of 24 M bytes, then metrics.isotonic_from_table on the host):
+    Estimator.last_calibration_map, <model_dir>/calibration-<global_step>.json (the chief writes it, temporary name and rename),
+    "calibration_knots" in the result (0 when the fit is refused: an invalid example, or no positive or no negative -- one
+    WARNING line, no file).  RunConfig.calibration_apply: every batch's prob is mapped through the map of the current
+    global_step into a second buffer (rsx_calibrate_apply, same stream) and a second bin table gives "ECE_cal", "MCE_cal" and
+    "PCOC_cal"; every other key keeps its raw value.  Refused: a second rank, both settings together (in-sample figures), M
+    outside 2..1024, calibration_apply without calibration_bins or without a map of this step.  A logloss / NE of the mapped
+    probabilities is out of scope.
+    The fit depends on `keys` (the _ExactKeys of this evaluate()): keys.report() must have run, reported or not -- it sorts the
+    keys and leaves the counts that finish() reads -- which evaluate() guarantees by reporting every setting before any finish()."""
+
+    def __init__(self, est, keys, fit, apply, bins):
+        _metrics.check_single_replica("calibration map", _world(est))
+        if fit and apply:
+            raise _metrics.RsxError("calibration_fit and calibration_apply in one evaluate() would report in-sample figures: "
+                                    "fit on one evaluation, apply in another")
+        if fit:
+            _metrics.check_bins(fit, "calibration_fit %d is outside %d..%d")
+        self.est, self.keys, self.fit, self.map, self.buf = est, keys, fit, None, None
+        if apply:
+            if not bins:
+                raise _metrics.RsxError("calibration_apply needs calibration_bins: ECE_cal is a figure of that table")
+            step = est._calibration_step()
+            m = est.calibration_map_for_step(step)
+            if m is None:
+                raise _metrics.RsxError("calibration_apply: no calibration map for global step %d (neither last_calibration_map "
+                                        "nor %s); run evaluate() with calibration_fit first"
+                                        % (step, est._calibration_path(step) or "a model_dir"))
+            self.map = _metrics.Calibrator(est.store.device, m)
+            self.acc = _metrics.Calibration(est.store.device, bins)
+
+    def update(self, lab, prob, features):
+        if self.map is None:
+            return
+        # into a buffer of its own (prob may be the graph's static output), the same stream
+        p1 = prob if prob.dtype == torch.float32 and prob.is_contiguous() else prob.to(torch.float32).contiguous()
+        if self.buf is None or self.buf.numel() != p1.numel():              # (the last batch of a stream may be a partial one)
+            self.buf = torch.empty(p1.numel(), dtype=torch.float32, device=p1.device)
+        self.acc.update(lab, self.map.apply(p1, out=self.buf))
+
+    def report(self, res):
+        if self.map is None:
+            return ""
+        rep = _metrics.calibration_reported(self.acc.result())
+        res.update({"ECE_cal": rep["ECE"], "MCE_cal": rep["MCE"], "PCOC_cal": rep["PCOC"]})
+        return ", ECE_cal = %.7g, PCOC_cal = %.7g" % (res["ECE_cal"], res["PCOC_cal"])
+
+    def finish(self, res):
+        if self.fit:
+            res["calibration_knots"] = self.est._fit_calibration_map(self.keys.acc, self.keys.counts, self.fit)
 
 
 def train_and_evaluate(estimator: Estimator, train_spec: TrainSpec, eval_spec: EvalSpec, eval_every_steps=None):

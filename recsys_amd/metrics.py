@@ -92,22 +92,134 @@ def finalize(hist_pos, hist_neg, correct, examples, batches, loss_sum):
     return {"AUC": auc, "Accuracy": correct / max(examples, 1), "loss": loss_sum / max(batches, 1), "examples": examples}
 
 
+# ---- what the opt-in metrics share: the example rule, the settings' checks, the inputs of an update ---------------------------
+CALIBRATION_MIN_BINS, CALIBRATION_MAX_BINS = 2, 1024       # rsx_calibration_max_bins()
+
+
+def example_bits_host(labels, prob):
+    """The example rule of csrc/eval_device.h, in numpy: u = the fp32 pattern of p as an integer (never passed through
+    arithmetic), -0.0 as +0.0; valid when u <= 0x3F800000 (0 <= p <= 1); positive when label > 0.5.
+    -> (positive bool [n] (None when labels is None), u uint32 [n], valid bool [n]), flat."""
+    p = np.ascontiguousarray(np.asarray(prob, np.float32).reshape(-1))
+    pos = None
+    if labels is not None:
+        y = np.ascontiguousarray(np.asarray(labels, np.float32).reshape(-1))
+        if y.size != p.size:
+            raise ValueError("labels and predictions differ in size")
+        pos = y > np.float32(0.5)
+    u = p.view(np.uint32).copy()
+    u[u == 0x80000000] = 0
+    return pos, u, u <= 0x3F800000
+
+
+def check_bins(n_bins, refusal=None):
+    """n_bins as an int in 2..1024.  Outside: ValueError (the host definitions), or RsxError(refusal % (n_bins, 2, 1024)) where
+    a device class or evaluate() names its own text."""
+    n_bins = int(n_bins)
+    if not CALIBRATION_MIN_BINS <= n_bins <= CALIBRATION_MAX_BINS:
+        if refusal is None:
+            raise ValueError("n_bins must be in 2..1024")
+        raise RsxError(refusal % (n_bins, CALIBRATION_MIN_BINS, CALIBRATION_MAX_BINS))
+    return n_bins
+
+
+def check_single_replica(setting, world):
+    """exact_auc, group_auc_key, the calibration tables and the calibration map are single-replica evaluations: the ranks' keys
+    would have to be sorted together (the tables summed).  setting: "exact_auc", "group_auc_key", "calibration" or
+    "calibration map", the prefix of the refusal."""
+    if int(world) > 1:
+        what = "tables would have to be summed" if setting == "calibration" else "keys would have to be sorted"
+        raise RsxError("%s: data-parallel evaluation is not supported (the ranks' %s together); evaluate on one replica"
+                       % (setting, what))
+
+
+def floats_on_device(x, device):
+    """-> B fp32 values, contiguous on the device.  A contiguous float32 device tensor is passed through as it is (evaluate()'s
+    tensors: at batch 256 the host's work per batch is the cost); numpy arrays and other tensors are converted and flattened."""
+    if isinstance(x, torch.Tensor) and x.is_cuda and x.dtype == torch.float32 and x.is_contiguous():
+        return x
+    if not isinstance(x, torch.Tensor):
+        x = torch.from_numpy(np.ascontiguousarray(np.asarray(x, np.float32)))
+    return x.to(device).reshape(-1).to(torch.float32).contiguous()
+
+
+def _group_ids_int32(groups):
+    """Group ids of any integer dtype as int32, an id that int32 cannot hold as -1 (invalid for every group_bits)."""
+    g = np.asarray(groups).reshape(-1)
+    if g.dtype == np.int32:
+        return np.ascontiguousarray(g)
+    g = g.astype(np.int64)
+    return np.where((g < 0) | (g > 0x7FFFFFFF), -1, g).astype(np.int32)
+
+
+def group_column_on_device(g, device):
+    """-> (int32 device tensor, element stride): a 1-D int32 device tensor is taken as it is, strided or not (ids[:, slot])."""
+    if isinstance(g, torch.Tensor):
+        if g.is_cuda and g.dtype == torch.int32 and g.dim() == 1 and (g.numel() <= 1 or g.stride(0) >= 1):
+            return g, max(1, int(g.stride(0)))
+        g = g.reshape(-1)
+        if g.dtype != torch.int32:
+            g = g.to(torch.int64)
+            g = torch.where((g < 0) | (g > 0x7FFFFFFF), torch.full_like(g, -1), g).to(torch.int32)
+    else:
+        g = torch.from_numpy(_group_ids_int32(g))
+    return g.to(device).contiguous(), 1
+
+
+class _KeyBuffer:
+    """What ExactAUC and GroupAUC share: the device key buffer -- capacity (examples) fixed when given (an update past it
+    raises), otherwise grown by doubling from GROW_FROM up to max_keys, with a device copy and no synchronisation --, `count`,
+    the output words and the workspace of result()."""
+    GROW_FROM = 1 << 16
+
+    def __init__(self, device, name, key_dtype, max_keys, capacity, out_words):
+        self.device, self.name = torch.device(device), name
+        self.fixed = capacity is not None
+        self.max_keys = int(max_keys)
+        cap = max(1, int(capacity)) if self.fixed else self.GROW_FROM
+        if cap > self.max_keys:
+            raise RsxError("%s: capacity %d is above the %d keys one sort takes" % (name, cap, self.max_keys))
+        self.keys = torch.empty(cap, dtype=key_dtype, device=self.device)
+        self.count = 0
+        self.out = torch.zeros(out_words, dtype=torch.int64, device=self.device)
+        self.workspace = None
+
+    def _room_for(self, n):
+        """Room for n more keys behind the `count` that are held -> the new count (the caller stores it after its launch)."""
+        need = self.count + n
+        if need > self.keys.numel():
+            if self.fixed or need > self.max_keys:
+                raise RsxError("%s: %d examples do not fit the key buffer of %d"
+                               % (self.name, need, self.keys.numel() if self.fixed else self.max_keys))
+            grown = torch.empty(min(self.max_keys, max(2 * self.keys.numel(), need)), dtype=self.keys.dtype, device=self.device)
+            grown[:self.count].copy_(self.keys[:self.count])
+            self.keys = grown
+        return need
+
+    def _workspace_of(self, need):
+        if self.workspace is None or self.workspace.numel() < need:
+            self.workspace = torch.empty(need, dtype=torch.uint8, device=self.device)
+        return self.workspace
+
+
 # ---- exact, tie-aware ROC AUC (include/rsx.h rsx_auc_exact_*) -----------------------------------------------------------------
 EXACT_AUC_PAD = 0xFFFFFFFF
 
 
 def exact_auc_keys_host(labels, prob):
-    """The 32-bit keys of rsx_auc_exact_append: (bits(p) << 1) | (label > 0.5) for 0 <= p <= 1 (-0.0 as +0.0), else the padding
-    key.  The fp32 pattern is taken as an integer, never passed through arithmetic."""
-    y = np.ascontiguousarray(np.asarray(labels, np.float32).reshape(-1))
-    p = np.ascontiguousarray(np.asarray(prob, np.float32).reshape(-1))
-    if y.size != p.size:
-        raise ValueError("labels and predictions differ in size")
-    u = p.view(np.uint32).copy()
-    u[u == 0x80000000] = 0
-    valid = u <= 0x3F800000
-    pos = (y > np.float32(0.5)).astype(np.uint32)
-    return np.where(valid, (u << np.uint32(1)) | pos, np.uint32(EXACT_AUC_PAD)).astype(np.uint32)
+    """The 32-bit keys of rsx_auc_exact_append: (u << 1) | positive for a valid example (example_bits_host), else the padding
+    key."""
+    pos, u, valid = example_bits_host(labels, prob)
+    return np.where(valid, (u << np.uint32(1)) | pos.astype(np.uint32), np.uint32(EXACT_AUC_PAD)).astype(np.uint32)
+
+
+def sorted_valid_keys_host(labels, prob):
+    """-> (the valid keys of exact_auc_keys_host, sorted; the head of every score group, bool; the number of invalid examples)"""
+    keys = exact_auc_keys_host(labels, prob)
+    ks = np.sort(keys[keys != EXACT_AUC_PAD])
+    head = np.ones(ks.size, bool)
+    head[1:] = (ks[1:] >> 1) != (ks[:-1] >> 1)
+    return ks, head, int(keys.size - ks.size)
 
 
 def exact_auc_from_counts(u2, positives, negatives, invalid):
@@ -123,14 +235,9 @@ def exact_auc_host(labels, prob):
     front of position i, h[i] = c at the head of i's score group; U2 = sum over positives of (c + h) =
     sum over positives of (2 #{negatives with a smaller score} + #{negatives with the same score}).
     -> {"AUC_exact", "u2", "positives", "negatives", "invalid"}"""
-    keys = exact_auc_keys_host(labels, prob)
-    ks = np.sort(keys[keys != EXACT_AUC_PAD])
-    invalid = int(keys.size - ks.size)
+    ks, head, invalid = sorted_valid_keys_host(labels, prob)
     neg = (ks & 1) == 0
     c = np.cumsum(neg, dtype=np.int64) - neg                         # exclusive
-    score = ks >> 1
-    head = np.ones(ks.size, bool)
-    head[1:] = score[1:] != score[:-1]
     h = np.maximum.accumulate(np.where(head, c, 0)) if ks.size else c
     u2 = int(np.sum((c + h)[~neg], dtype=np.int64))
     return exact_auc_from_counts(u2, int((~neg).sum()), int(neg.sum()), invalid)
@@ -142,55 +249,25 @@ def exact_auc_reported(res):
     return float("nan") if res["invalid"] else res["AUC_exact"]
 
 
-def check_exact_auc_world(world):
-    """exact_auc is a single-replica evaluation: the ranks' keys would have to be sorted together."""
-    if int(world) > 1:
-        raise RsxError("exact_auc: data-parallel evaluation is not supported (the ranks' keys would have to be sorted together); "
-                       "evaluate on one replica")
-
-
-class ExactAUC:
+class ExactAUC(_KeyBuffer):
     """Exact ROC AUC of one evaluate() call: one append launch per batch into a device key buffer, one sort + reduction and
-    ONE device->host copy in `result()`.  capacity (examples): fixed when given (an update past it raises); otherwise the buffer
-    grows by doubling, with a device copy and no synchronisation.  Memory: 4 B per key + rsx_auc_exact_workspace_bytes(n) =
-    4 n + 1032 ceil(n / 4096) + 4096 B while result() runs."""
-    GROW_FROM = 1 << 16
+    ONE device->host copy in `result()`.  capacity: _KeyBuffer's rules.  Memory: 4 B per key +
+    rsx_auc_exact_workspace_bytes(n) = 4 n + 1032 ceil(n / 4096) + 4096 B while result() runs."""
 
     def __init__(self, device, capacity=None):
-        self.device = torch.device(device)
-        self.fixed = capacity is not None
-        self.max_keys = int(lib().rsx_auc_exact_max_keys())
-        cap = max(1, int(capacity)) if self.fixed else self.GROW_FROM
-        if cap > self.max_keys:
-            raise RsxError("exact_auc: capacity %d is above the %d keys one sort takes" % (cap, self.max_keys))
-        self.keys = torch.empty(cap, dtype=torch.int32, device=self.device)
-        self.count = 0
-        # [0..3] finalize's {U2, P, N, invalid}; [4] the invalid examples the append launches counted
-        self.out = torch.zeros(5, dtype=torch.int64, device=self.device)
-        self.workspace = None
+        # out: [0..3] finalize's {U2, P, N, invalid}; [4] the invalid examples the append launches counted
+        super().__init__(device, "exact_auc", torch.int32, lib().rsx_auc_exact_max_keys(), capacity, 5)
         self.sorted_valid = None          # V = P + N of the latest result() while the buffer still holds its sorted keys
-
-    def _as_device(self, x):
-        if not isinstance(x, torch.Tensor):
-            x = torch.from_numpy(np.ascontiguousarray(np.asarray(x, np.float32)))
-        return x.to(self.device).reshape(-1).to(torch.float32).contiguous()
 
     def update(self, labels, prob):
         """labels / prob: device tensors or numpy arrays of B elements (any shape).  No host synchronisation."""
-        y, p = self._as_device(labels), self._as_device(prob)
+        y, p = floats_on_device(labels, self.device), floats_on_device(prob, self.device)
         n = int(p.numel())
         if y.numel() != n:
             raise ValueError("labels and predictions differ in size")
         if n == 0:
             return
-        need = self.count + n
-        if need > self.keys.numel():
-            if self.fixed or need > self.max_keys:
-                raise RsxError("exact_auc: %d examples do not fit the key buffer of %d"
-                               % (need, self.keys.numel() if self.fixed else self.max_keys))
-            grown = torch.empty(min(self.max_keys, max(2 * self.keys.numel(), need)), dtype=torch.int32, device=self.device)
-            grown[:self.count].copy_(self.keys[:self.count])
-            self.keys = grown
+        need = self._room_for(n)
         check(lib().rsx_auc_exact_append(C.c_void_p(p.data_ptr()), C.c_void_p(y.data_ptr()), n,
                                          C.c_void_p(self.keys.data_ptr() + 4 * self.count),
                                          C.c_void_p(self.out.data_ptr() + 8 * 4),
@@ -201,11 +278,9 @@ class ExactAUC:
     def result(self):
         """-> {"AUC_exact", "u2", "positives", "negatives", "invalid"}; one finalize, ONE device->host copy.  The key buffer keeps
         its multiset (sorted), so updates may continue afterwards."""
-        need = int(lib().rsx_auc_exact_workspace_bytes(self.count))
-        if self.workspace is None or self.workspace.numel() < need:
-            self.workspace = torch.empty(need, dtype=torch.uint8, device=self.device)
-        check(lib().rsx_auc_exact_finalize(C.c_void_p(self.keys.data_ptr()), self.count, C.c_void_p(self.workspace.data_ptr()),
-                                           int(self.workspace.numel()), C.c_void_p(self.out.data_ptr()),
+        ws = self._workspace_of(int(lib().rsx_auc_exact_workspace_bytes(self.count)))
+        check(lib().rsx_auc_exact_finalize(C.c_void_p(self.keys.data_ptr()), self.count, C.c_void_p(ws.data_ptr()),
+                                           int(ws.numel()), C.c_void_p(self.out.data_ptr()),
                                            C.c_void_p(torch.cuda.current_stream().cuda_stream)), "rsx_auc_exact_finalize")
         s = [int(v) for v in self.out.cpu().numpy()]
         if s[3] != s[4] or s[1] + s[2] + s[3] != self.count:
@@ -218,10 +293,7 @@ class ExactAUC:
         """The equal-mass, tie-aware table of the examples result() has sorted (quantile_table_host's, integer for integer):
         int64 [n_bins, 3] = (count, positives, q_sum).  Call it after result() and before the next update(); ONE launch
         (rsx_calibration_quantile_table, no workspace) and ONE device->host copy of 24 n_bins bytes."""
-        n_bins = int(n_bins)
-        if not CALIBRATION_MIN_BINS <= n_bins <= int(lib().rsx_calibration_max_bins()):
-            raise RsxError("quantile_table: n_bins %d is outside %d..%d"
-                           % (n_bins, CALIBRATION_MIN_BINS, int(lib().rsx_calibration_max_bins())))
+        n_bins = check_bins(n_bins, "quantile_table: n_bins %d is outside %d..%d")
         if self.sorted_valid is None:
             raise RsxError("quantile_table: call result() first (it sorts the keys), and again after any further update()")
         table = torch.empty(3 * n_bins, dtype=torch.int64, device=self.device)
@@ -236,15 +308,6 @@ class ExactAUC:
 GROUP_AUC_PAD = 0xFFFFFFFFFFFFFFFF
 # the 8 words of rsx_auc_group_finalize's header (the last one is zero)
 GROUP_AUC_HEADER = ("valid", "invalid", "groups", "mixed_groups", "skipped_examples", "positives", "negatives")
-
-
-def _group_ids_int32(groups):
-    """Group ids of any integer dtype as int32, an id that int32 cannot hold as -1 (invalid for every group_bits)."""
-    g = np.asarray(groups).reshape(-1)
-    if g.dtype == np.int32:
-        return np.ascontiguousarray(g)
-    g = g.astype(np.int64)
-    return np.where((g < 0) | (g > 0x7FFFFFFF), -1, g).astype(np.int32)
 
 
 def group_auc_keys_host(groups, labels, prob, group_bits=31):
@@ -335,75 +398,32 @@ def group_auc_reported(res):
     return float("nan") if res["invalid"] else res["GAUC"]
 
 
-def check_group_auc_world(world):
-    """group_auc_key is a single-replica evaluation, like exact_auc."""
-    if int(world) > 1:
-        raise RsxError("group_auc_key: data-parallel evaluation is not supported (the ranks' keys would have to be sorted "
-                       "together); evaluate on one replica")
-
-
-class GroupAUC:
+class GroupAUC(_KeyBuffer):
     """GAUC of one evaluate() call: one append launch per batch into a device buffer of 64-bit keys; `result()` does one finalize
-    (sort + segmented reduction), one device->host copy of the header, one records launch and one copy of the records.  capacity
-    (examples): fixed when given (an update past it raises); otherwise the buffer grows by doubling, with a device copy and no
-    synchronisation -- ExactAUC's rules.  group_bits: ids are valid in [0, 2^group_bits).
+    (sort + segmented reduction), one device->host copy of the header, one records launch and one copy of the records.  capacity:
+    _KeyBuffer's rules.  group_bits: ids are valid in [0, 2^group_bits).
     Memory: 8 B per key + rsx_auc_group_workspace_bytes(n, group_bits) = round_up(8 n, 256) + round_up(1044 ceil(n / 4096) + 8192,
     256) + 16 ceil(n / 4096) B of workspace while result() runs + 32 B per mixed group for the records."""
-    GROW_FROM = 1 << 16
 
     def __init__(self, device, group_bits, capacity=None):
-        self.device = torch.device(device)
         self.group_bits = int(group_bits)
         if not 1 <= self.group_bits <= 31:
             raise RsxError("group_auc: group_bits %d is outside 1..31" % self.group_bits)
-        self.fixed = capacity is not None
-        self.max_keys = int(lib().rsx_auc_group_max_keys())
-        cap = max(1, int(capacity)) if self.fixed else self.GROW_FROM
-        if cap > self.max_keys:
-            raise RsxError("group_auc: capacity %d is above the %d keys one sort takes" % (cap, self.max_keys))
-        self.keys = torch.empty(cap, dtype=torch.int64, device=self.device)
-        self.count = 0
-        # [0..7] finalize's header; [8] the invalid examples the append launches counted
-        self.out = torch.zeros(9, dtype=torch.int64, device=self.device)
-        self.workspace = None
+        # out: [0..7] finalize's header; [8] the invalid examples the append launches counted
+        super().__init__(device, "group_auc", torch.int64, lib().rsx_auc_group_max_keys(), capacity, 9)
         self.header = None                # the latest result()'s header, as Python integers
-
-    def _floats(self, x):
-        if not isinstance(x, torch.Tensor):
-            x = torch.from_numpy(np.ascontiguousarray(np.asarray(x, np.float32)))
-        return x.to(self.device).reshape(-1).to(torch.float32).contiguous()
-
-    def _groups(self, g):
-        """-> (int32 device tensor, element stride): a 1-D int32 device tensor is taken as it is, strided or not."""
-        if isinstance(g, torch.Tensor):
-            if g.is_cuda and g.dtype == torch.int32 and g.dim() == 1 and (g.numel() <= 1 or g.stride(0) >= 1):
-                return g, max(1, int(g.stride(0)))
-            g = g.reshape(-1)
-            if g.dtype != torch.int32:
-                g = g.to(torch.int64)
-                g = torch.where((g < 0) | (g > 0x7FFFFFFF), torch.full_like(g, -1), g).to(torch.int32)
-        else:
-            g = torch.from_numpy(_group_ids_int32(g))
-        return g.to(self.device).contiguous(), 1
 
     def update(self, groups, labels, prob):
         """groups / labels / prob: device tensors or numpy arrays of B elements; groups may be a strided column view
         (ids[:, slot]).  No host synchronisation."""
-        y, p = self._floats(labels), self._floats(prob)
-        g, stride = self._groups(groups)
+        y, p = floats_on_device(labels, self.device), floats_on_device(prob, self.device)
+        g, stride = group_column_on_device(groups, self.device)
         n = int(p.numel())
         if y.numel() != n or g.numel() != n:
             raise ValueError("groups, labels and predictions differ in size")
         if n == 0:
             return
-        need = self.count + n
-        if need > self.keys.numel():
-            if self.fixed or need > self.max_keys:
-                raise RsxError("group_auc: %d examples do not fit the key buffer of %d"
-                               % (need, self.keys.numel() if self.fixed else self.max_keys))
-            grown = torch.empty(min(self.max_keys, max(2 * self.keys.numel(), need)), dtype=torch.int64, device=self.device)
-            grown[:self.count].copy_(self.keys[:self.count])
-            self.keys = grown
+        need = self._room_for(n)
         check(lib().rsx_auc_group_append(C.c_void_p(p.data_ptr()), C.c_void_p(y.data_ptr()), C.c_void_p(g.data_ptr()), stride, n,
                                          self.group_bits, C.c_void_p(self.keys.data_ptr() + 8 * self.count),
                                          C.c_void_p(self.out.data_ptr() + 8 * 8),
@@ -414,11 +434,9 @@ class GroupAUC:
         """-> {"GAUC", "groups", "mixed_groups", "skipped_examples", "invalid"}, plus "records" (uint64 [mixed_groups, 4] =
         (g, P_g, N_g, U2_g), ascending g) when per_group.  The key buffer keeps its multiset (sorted), so updates may continue."""
         stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
-        need = int(lib().rsx_auc_group_workspace_bytes(self.count, self.group_bits))
-        if self.workspace is None or self.workspace.numel() < need:
-            self.workspace = torch.empty(need, dtype=torch.uint8, device=self.device)
+        ws = self._workspace_of(int(lib().rsx_auc_group_workspace_bytes(self.count, self.group_bits)))
         check(lib().rsx_auc_group_finalize(C.c_void_p(self.keys.data_ptr()), self.count, self.group_bits,
-                                           C.c_void_p(self.workspace.data_ptr()), int(self.workspace.numel()),
+                                           C.c_void_p(ws.data_ptr()), int(ws.numel()),
                                            C.c_void_p(self.out.data_ptr()), stream), "rsx_auc_group_finalize")
         s = [int(v) for v in self.out.cpu().numpy()]
         if s[1] != s[8] or s[0] + s[1] != self.count or s[5] + s[6] != s[0] or s[3] > s[2]:
@@ -426,7 +444,7 @@ class GroupAUC:
                            "launches counted %d invalid" % (s[5], s[6], s[1], self.count, s[8]))
         rec = torch.zeros((s[3], 4), dtype=torch.int64, device=self.device)
         if s[3]:
-            check(lib().rsx_auc_group_records(C.c_void_p(self.keys.data_ptr()), self.count, C.c_void_p(self.workspace.data_ptr()),
+            check(lib().rsx_auc_group_records(C.c_void_p(self.keys.data_ptr()), self.count, C.c_void_p(ws.data_ptr()),
                                               C.c_void_p(self.out.data_ptr()), C.c_void_p(rec.data_ptr()), s[3], stream),
                   "rsx_auc_group_records")
         rec = rec.cpu().numpy().view(np.uint64)
@@ -438,19 +456,8 @@ class GroupAUC:
 
 
 # ---- calibration: reliability bins, ECE / MCE / PCOC / NE and the same per group (include/rsx.h rsx_calibration_*) -------------
-CALIBRATION_MIN_BINS = 2
 CALIBRATION_Q_ONE = 1 << 32             # the fixed-point 1.0 of q
 _NAN = float("nan")
-
-
-def _calibration_inputs(labels, prob):
-    y = np.ascontiguousarray(np.asarray(labels, np.float32).reshape(-1))
-    p = np.ascontiguousarray(np.asarray(prob, np.float32).reshape(-1))
-    if y.size != p.size:
-        raise ValueError("labels and predictions differ in size")
-    u = p.view(np.uint32).copy()
-    u[u == 0x80000000] = 0              # -0.0 is +0.0
-    return y > np.float32(0.5), u.view(np.float32), u <= 0x3F800000
 
 
 def calibration_bin_host(prob, n_bins):
@@ -476,14 +483,12 @@ def _calibration_rows(index, rows, pos, q):
 
 def calibration_bins_host(labels, prob, n_bins):
     """The documented definition of the bin table, in numpy.  An example is valid when 0 <= p <= 1 (exact_auc_keys_host's bit
-    test, -0.0 as +0.0) and positive when y > 0.5.
+    test, -0.0 as +0.0) and positive when y > 0.5: example_bits_host.
     -> (table int64 [n_bins, 3] = (count, positives, q_sum) per bin, the number of invalid examples).  The q sums are 64-bit
     integers, good for 2^31 examples."""
-    n_bins = int(n_bins)
-    if not CALIBRATION_MIN_BINS <= n_bins <= 1024:
-        raise ValueError("n_bins must be in 2..1024")
-    pos, p, valid = _calibration_inputs(labels, prob)
-    pos, p = pos[valid], p[valid]
+    n_bins = check_bins(n_bins)
+    pos, u, valid = example_bits_host(labels, prob)
+    pos, p = pos[valid], u[valid].view(np.float32)
     return _calibration_rows(calibration_bin_host(p, n_bins), n_bins, pos, calibration_q_host(p)), int(valid.size - valid.sum())
 
 
@@ -494,12 +499,12 @@ def calibration_groups_host(groups, labels, prob, n_groups):
     n_groups = int(n_groups)
     if n_groups < 1:
         raise ValueError("n_groups must be positive")
-    pos, p, valid = _calibration_inputs(labels, prob)
+    pos, u, valid = example_bits_host(labels, prob)
     g = _group_ids_int32(groups).astype(np.int64)
-    if g.size != p.size:
+    if g.size != u.size:
         raise ValueError("groups and predictions differ in size")
     valid = valid & (g >= 0) & (g < n_groups)
-    pos, p, g = pos[valid], p[valid], g[valid]
+    pos, p, g = pos[valid], u[valid].view(np.float32), g[valid]
     return _calibration_rows(g, n_groups, pos, calibration_q_host(p)), int(valid.size - valid.sum())
 
 
@@ -567,13 +572,6 @@ def group_calibration_reported(res):
     return {"GCE": _NAN if res["invalid"] else res["GCE"]}
 
 
-def check_calibration_world(world):
-    """The calibration settings are a single-replica evaluation, like exact_auc."""
-    if int(world) > 1:
-        raise RsxError("calibration: data-parallel evaluation is not supported (the ranks' tables would have to be summed "
-                       "together); evaluate on one replica")
-
-
 class Calibration:
     """The calibration tables of one evaluate() call: one launch per batch (rsx_calibration_update, csrc/calibration.hip) adds
     the batch to a bin table (n_bins in 2..rsx_calibration_max_bins()) and / or a group table (n_groups in
@@ -583,31 +581,21 @@ class Calibration:
 
     def __init__(self, device, n_bins=None, n_groups=None):
         self.device = torch.device(device)
-        self.n_bins = 0 if n_bins is None else int(n_bins)
         self.n_groups = 0 if n_groups is None else int(n_groups)
         if n_bins is None and n_groups is None:
             raise RsxError("calibration: give n_bins, n_groups or both")
-        if n_bins is not None and not CALIBRATION_MIN_BINS <= self.n_bins <= int(lib().rsx_calibration_max_bins()):
-            raise RsxError("calibration: n_bins %d is outside %d..%d"
-                           % (self.n_bins, CALIBRATION_MIN_BINS, int(lib().rsx_calibration_max_bins())))
+        self.n_bins = 0 if n_bins is None else check_bins(n_bins, "calibration: n_bins %d is outside %d..%d")
         if n_groups is not None and not 1 <= self.n_groups <= int(lib().rsx_calibration_max_groups()):
             raise RsxError("calibration: n_groups %d is outside 1..%d (the group table is 24 bytes per group)"
                            % (self.n_groups, int(lib().rsx_calibration_max_groups())))
         # [0] invalid examples; [1 .. 1 + 3 n_bins) the bin table; then the group table
         self.state = torch.zeros(1 + 3 * self.n_bins + 3 * self.n_groups, dtype=torch.int64, device=self.device)
 
-    _groups = GroupAUC._groups
-
-    def _floats(self, x):
-        if isinstance(x, torch.Tensor) and x.is_cuda and x.dtype == torch.float32 and x.is_contiguous():
-            return x                      # evaluate()'s tensors as they are: at batch 256 the host's work per batch is the cost
-        return GroupAUC._floats(self, x)
-
     def update(self, labels, prob, groups=None):
         """labels / prob / groups: device tensors or numpy arrays of B elements (any shape); groups (needed with a group table,
         not read without one) may be a strided column view (ids[:, slot]), which is passed through in place.  No host
         synchronisation."""
-        y, p = self._floats(labels), self._floats(prob)
+        y, p = floats_on_device(labels, self.device), floats_on_device(prob, self.device)
         n = int(p.numel())
         if y.numel() != n:
             raise ValueError("labels and predictions differ in size")
@@ -615,7 +603,7 @@ class Calibration:
         if self.n_groups:
             if groups is None:
                 raise ValueError("calibration: this object has a group table; update() needs the group ids")
-            g, stride = self._groups(groups)
+            g, stride = group_column_on_device(groups, self.device)
             if g.numel() != n:
                 raise ValueError("groups, labels and predictions differ in size")
         if n == 0:
@@ -657,27 +645,17 @@ ISOTONIC_MAX_KNOTS = 1024
 ISOTONIC_FORMAT = "recsys_amd.isotonic_map.v1"
 
 
-def _check_quantile_bins(n_bins):
-    n_bins = int(n_bins)
-    if not CALIBRATION_MIN_BINS <= n_bins <= 1024:
-        raise ValueError("n_bins must be in 2..1024")
-    return n_bins
-
-
 def quantile_table_host(labels, prob, n_bins):
     """The documented definition of the equal-mass, tie-aware table, in numpy.  ks = the sorted valid keys of
     exact_auc_keys_host, V of them; h(i) = the position of the first key with i's score; bin b(i) = (h(i) * M) // V in 64-bit
     integers.  All examples of one score share a bin, bins ascend with the score and may be empty.
     -> table int64 [n_bins, 3] = (count, positives, q_sum), calibration_bins_host's row and q."""
-    M = _check_quantile_bins(n_bins)
-    keys = exact_auc_keys_host(labels, prob)
-    ks = np.sort(keys[keys != EXACT_AUC_PAD])
+    M = check_bins(n_bins)
+    ks, head, _ = sorted_valid_keys_host(labels, prob)
     V = int(ks.size)
     if V == 0:
         return np.zeros((M, 3), np.int64)
     score = ks >> np.uint32(1)
-    head = np.ones(V, bool)
-    head[1:] = score[1:] != score[:-1]
     h = np.maximum.accumulate(np.where(head, np.arange(V, dtype=np.int64), 0))
     b = (h * M) // V
     p = np.ascontiguousarray(score.astype(np.uint32)).view(np.float32)
@@ -737,7 +715,7 @@ def _check_knots(x, y):
 
 def isotonic_apply_host(p, x, y):
     """The documented definition of the map, in numpy fp32 -- bit for bit what rsx_calibrate_apply computes.  A p outside
-    [0, 1] by exact_auc_keys_host's bit test is returned unchanged, bit for bit (-0.0 counts as +0.0); p <= x[0] -> y[0];
+    [0, 1] by example_bits_host's bit test is returned unchanged, bit for bit (-0.0 counts as +0.0); p <= x[0] -> y[0];
     p >= x[K-1] -> y[K-1]; otherwise with j the largest index with x[j] <= p:
     t = (p - x[j]) / (x[j+1] - x[j]); o = y[j] + t * (y[j+1] - y[j]); out = o if o < y[j+1] else y[j+1] -- every operation one
     fp32 operation rounded to nearest.  x must ascend strictly (not checked here).  -> float32, p's shape."""
@@ -748,8 +726,7 @@ def isotonic_apply_host(p, x, y):
     if K < 1 or y.size != K:
         raise ValueError("isotonic map: x and y need the same number of knots, at least one")
     bits = p.reshape(-1).view(np.uint32)
-    u = np.where(bits == 0x80000000, np.uint32(0), bits).astype(np.uint32)
-    valid = u <= 0x3F800000
+    _, u, valid = example_bits_host(None, p)
     v = u[valid].view(np.float32)
     r = np.full(v.shape, y[0], np.float32)
     if K > 1:
@@ -762,13 +739,6 @@ def isotonic_apply_host(p, x, y):
     out = bits.copy()
     out[valid] = r.view(np.uint32)
     return out.view(np.float32).reshape(p.shape)
-
-
-def check_calibration_map_world(world):
-    """calibration_fit / calibration_apply are a single-replica evaluation, like exact_auc."""
-    if int(world) > 1:
-        raise RsxError("calibration map: data-parallel evaluation is not supported (the ranks' keys would have to be sorted "
-                       "together); evaluate on one replica")
 
 
 def _f32_bits(a):

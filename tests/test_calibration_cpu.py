@@ -216,9 +216,9 @@ def test_calibration_flags_on_every_script(script):
 def test_run_config_defaults_and_world_check():
     from recsys_amd.estimator import RunConfig
     assert RunConfig().calibration_bins == 0 and RunConfig().calibration_key is None
-    metrics.check_calibration_world(1)
+    metrics.check_single_replica("calibration", 1)
     with pytest.raises(RsxError, match="data-parallel evaluation is not supported"):
-        metrics.check_calibration_world(2)
+        metrics.check_single_replica("calibration", 2)
     for n_bins in (0, 1, 1025):
         with pytest.raises(ValueError):
             metrics.calibration_bins_host([0.0], [0.5], n_bins)

@@ -389,9 +389,9 @@ def test_calibration_map_flags_on_every_script(script):
 def test_run_config_defaults_and_world_check():
     from recsys_amd.estimator import RunConfig
     assert RunConfig().calibration_fit == 0 and RunConfig().calibration_apply is False
-    metrics.check_calibration_map_world(1)
+    metrics.check_single_replica("calibration map", 1)
     with pytest.raises(RsxError, match="data-parallel evaluation is not supported"):
-        metrics.check_calibration_map_world(2)
+        metrics.check_single_replica("calibration map", 2)
 
 
 def test_symbols_are_exported_and_declared():

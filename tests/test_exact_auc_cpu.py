@@ -121,9 +121,9 @@ def test_exact_auc_flag_on_every_script(script):
 def test_run_config_default_and_world_check():
     from recsys_amd.estimator import RunConfig
     assert RunConfig().exact_auc is False
-    metrics.check_exact_auc_world(1)
+    metrics.check_single_replica("exact_auc", 1)
     with pytest.raises(RsxError, match="data-parallel evaluation is not supported"):
-        metrics.check_exact_auc_world(2)
+        metrics.check_single_replica("exact_auc", 2)
 
 
 def test_cabi_envelope_is_checked_before_any_device_call():

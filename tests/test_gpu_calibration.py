@@ -151,7 +151,7 @@ def test_a_strided_group_column_is_read_in_place(n_groups):
     col = torch.from_numpy(ids).to(dev)[:, slot]
     assert col.stride(0) == F and not col.is_contiguous()
     cal = metrics.Calibration(dev, None, n_groups)
-    tensor, stride = cal._groups(col)
+    tensor, stride = metrics.group_column_on_device(col, dev)
     assert stride == F and tensor.data_ptr() == col.data_ptr()          # the view itself is what the launch reads
     cal.update(torch.from_numpy(y).to(dev), torch.from_numpy(p).to(dev), col)
     res = cal.result(per_group=True)

@@ -78,8 +78,8 @@ def stream(rng, n, ties=None):
     return y, p
 
 
-@pytest.mark.parametrize("n", [1, 2, 63, 64, 65, 4095, 4096, 4097, 65836])
-def test_table_at_every_size_and_bin_count(n):
+@pytest.mark.parametrize("n", [1, 2, 63, 64, 65, 255, 1024, 4095, 4096, 4097, 65836])   # 255 / 1024: the 256-thread block sum,
+def test_table_at_every_size_and_bin_count(n):                                           # partly and exactly 4 keys per thread
     rng = np.random.default_rng(3 * n)
     y, p = stream(rng, n)
     check_tables(y, p)                                         # M = 1024 > n for the small sizes: most bins empty

@@ -223,7 +223,7 @@ def test_numpy_inputs_empty_stream_and_strided_column():
     col = ids_d[:, slot]
     assert col.stride(0) == F and not col.is_contiguous()
     gb = metrics.GroupAUC(dev, 5)
-    tensor, stride = gb._groups(col)
+    tensor, stride = metrics.group_column_on_device(col, dev)
     assert stride == F and tensor.data_ptr() == col.data_ptr()         # the view itself is what the launch reads
     gb.update(col, torch.from_numpy(y).to(dev), torch.from_numpy(p).to(dev))
     res = gb.result(per_group=True)

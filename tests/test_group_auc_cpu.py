@@ -149,9 +149,9 @@ def test_group_auc_key_flag_on_every_script(script):
 def test_run_config_default_and_world_check():
     from recsys_amd.estimator import RunConfig
     assert RunConfig().group_auc_key is None
-    metrics.check_group_auc_world(1)
+    metrics.check_single_replica("group_auc_key", 1)
     with pytest.raises(RsxError, match="data-parallel evaluation is not supported"):
-        metrics.check_group_auc_world(2)
+        metrics.check_single_replica("group_auc_key", 2)
 
 
 def test_cabi_envelope_is_checked_before_any_device_call():
