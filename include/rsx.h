@@ -730,6 +730,39 @@ int rsx_predict_fm_tower_supported(int B, int F, int D, int L, const int32_t* wi
 int rsx_predict_fm_tower(const rsx_predict_model* model_h, const int32_t* ids, float* prob, int B, rsx_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Item ranking of an exported two-field deepfm.py model (deepfm/deepfm.py AS COMMITTED: u_id, i_id) as ONE launch: U users,
+ * C items each -> prob [U, C] (csrc/predict_pair.hip).  prob[u, c] is what deepfm/deepfm.py:85-113 gives in PREDICT mode for
+ * the example whose two table-local ids are (user_id[u], item_id[u, c]) -- the formulas of rsx_predict_fm_tower above with
+ * F = 2, in the oracle's order of operations: y1 = w1[row_0] + w1[row_1] over the slots of w1_field_mask in ascending order,
+ * y2 = 0.5 * sum_d ((e_0 + e_1)^2 - (e_0^2 + e_1^2)), the tower over x_0 = [e_0 | e_1] (K_0 = 2 D), the 1-unit layer, the
+ * 3 -> 1 logits layer, the sigmoid.
+ * The model is rsx_predict_model, unchanged: F must be 2, L >= 1 with wd / bd, W[0] is [2 D, widths[0]] with slot 0's D rows
+ * first.  user_slot in {0, 1} says which slot holds the user field (input_layer sorts by name: in a deepfm.py bundle i_id is
+ * slot 0 and u_id slot 1); the item field is the other one.  Row of slot s: row_off[s] + the id of that slot's field.
+ * item_id: row u at item_id + u * item_ld; item_ld == 0 means ONE list [C] shared by all users, else item_ld >= C and the
+ * padding is never read.  prob [U, C] is contiguous.
+ * A workgroup owns 16 consecutive items of ONE user (grid U * ceil(C / 16)); the user's row and its w1 entry are read from
+ * one address by the 16 pairs, the item rows go straight into the LDS tile [16][2 D + 4]; rows past C in a user's last tile
+ * take the last item's id and store nothing.  No workspace, no atomics, no grid-wide step; only prob [0, U * C) is written.
+ * The user's half of the first layer is not folded.
+ * DETERMINISM CONTRACT: a pair's bits depend on its two table rows and the model only -- not on U or C, on item_ld, on the
+ * pair's position in the tile, on the other users and items of the call, or on whether the launch runs eagerly or is replayed
+ * from a hipGraph.
+ * 16-bit tables as in rsx_predict_fm_tower: rows are widened exactly as they are loaded (the load at the flat float4 index
+ * row * (D / 4) + q), so the result is bit-identical to an fp32 launch over the widened table.
+ * RSX_EINVAL (before any HIP call): a NULL model / user_id / item_id / prob, U or C <= 0, user_slot outside {0, 1}, item_ld
+ * neither 0 nor >= C, F != 2, wd / bd missing, or a model rsx_predict_fm_tower refuses (a NULL required pointer, gamma
+ * without beta, a bad bn_eps or table_dtype, tables not 16-byte aligned).  Envelope (rsx_predict_pair_rank_supported;
+ * RSX_EUNSUPPORTED outside, before any HIP call, where the caller expands the request and serves it through `predict`):
+ * D in {8, 16, 32}, 1 <= L <= 3 with the width rules of rsx_predict_fm_tower (inner widths multiples of 4, the last at most
+ * 256), U, C >= 1, U * C < 2^31, and its LDS plan with 2 D in place of 16 F within 160 KB.
+ * Added behind rsx_version() 107 without a new number (the suite pins 107): a caller that must tell looks the symbol up.
+ * ------------------------------------------------------------------------------------------- */
+int rsx_predict_pair_rank_supported(int U, int C, int D, int L, const int32_t* widths);
+int rsx_predict_pair_rank(const rsx_predict_model* model_h, int user_slot, const int32_t* user_id, const int32_t* item_id,
+                          int item_ld, float* prob, int U, int C, rsx_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Serving forward of an exported dcn.py model as ONE launch: ids [B, F] -> prob [B].
  * Replaces, in PREDICT mode, dcn/dcn.py:123-153: the input_layer lookup x_0 [F * 16]; Lc cross layers
  *   x_{l+1} = (x_l . cross_W[l]) * x_0 + x_l + cross_b[l];

@@ -386,6 +386,8 @@ _SIGS = {
     "rsx_mlp_nobn_reduce_job": (_I, [C.POINTER(MlpStep), C.POINTER(MlpReduceJob)]),
     "rsx_predict_fm_tower_supported": (_I, [_I, _I, _I, _I, _P]),
     "rsx_predict_fm_tower": (_I, [C.POINTER(PredictModel), _P, _P, _I, _P]),
+    "rsx_predict_pair_rank_supported": (_I, [_I, _I, _I, _I, _P]),
+    "rsx_predict_pair_rank": (_I, [C.POINTER(PredictModel), _I, _P, _P, _I, _P, _I, _I, _P]),
     "rsx_predict_dcn_supported": (_I, [_I, _I, _I, _I, _P, _I]),
     "rsx_predict_dcn": (_I, [C.POINTER(PredictDcnModel), _P, _P, _I, _P]),
     "rsx_predict_din_rank_supported": (_I, [_I] * 7 + [_P]),

@@ -37,24 +37,29 @@ int launch_big_lds(const Args& p, const unsigned grid, const unsigned threads, c
   return RSX_OK;
 }
 
-// Elements 4 q .. 4 q + 3 of row `row` of tables [R, 16] stored as TD (RSX_TABLE_*), as fp32.  A 16-bit row is 32 bytes: the
-// thread loads the 8 bytes that hold its four elements and widens them, which is exact for both formats (subnormals, signed
+// Elements 4 q .. 4 q + 3 of row `row` of tables [R, 16] stored as TD (RSX_TABLE_*), as fp32 (`load_row4`); `load_flat4` is the
+// same load at a flat float4 index i = row * (D / 4) + q for the kernels whose rows are not 16 wide (predict_pair.hip).  A 16-bit
+// row of 16 is 32 bytes: the thread loads the 8 bytes that hold its four elements and widens them, which is exact for both formats (subnormals, signed
 // zeros included), so the kernel computes what its fp32 instantiation computes over the widened table, bit for bit.
 // bfloat16 is the upper half of the fp32 pattern: a shift for the even elements, a mask for the odd ones.  float16 takes the
 // hardware convert (v_cvt_f32_f16 keeps fp16 subnormals: the fp16 denormal mode is on in every HIP kernel).
 typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
 template <int TD>
-__device__ __forceinline__ f32x4 load_row4(const void* __restrict__ tables, const int row, const int q) {
+__device__ __forceinline__ f32x4 load_flat4(const void* __restrict__ tables, const size_t i) {
   if constexpr (TD == RSX_TABLE_F32) {
-    return reinterpret_cast<const f32x4*>(tables)[(size_t)row * 4 + q];
+    return reinterpret_cast<const f32x4*>(tables)[i];
   } else if constexpr (TD == RSX_TABLE_BF16) {
-    const uint2 v = reinterpret_cast<const uint2*>(tables)[(size_t)row * 4 + q];
+    const uint2 v = reinterpret_cast<const uint2*>(tables)[i];
     return f32x4{__uint_as_float(v.x << 16), __uint_as_float(v.x & 0xffff0000u), __uint_as_float(v.y << 16),
                  __uint_as_float(v.y & 0xffff0000u)};
   } else {
     static_assert(TD == RSX_TABLE_F16, "unknown table dtype");
-    return __builtin_convertvector(reinterpret_cast<const f16x4*>(tables)[(size_t)row * 4 + q], f32x4);
+    return __builtin_convertvector(reinterpret_cast<const f16x4*>(tables)[i], f32x4);
   }
+}
+template <int TD>
+__device__ __forceinline__ f32x4 load_row4(const void* __restrict__ tables, const int row, const int q) {
+  return load_flat4<TD>(tables, (size_t)row * 4 + q);
 }
 inline bool table_dtype_known(int td) { return td == RSX_TABLE_F32 || td == RSX_TABLE_BF16 || td == RSX_TABLE_F16; }
 
@@ -279,6 +284,14 @@ inline long long predict_lds_floats(int B, int F, int D, int L, const int32_t* w
     p->oY = p->oP + pmax;
   }
   return fl;
+}
+
+// The same plan for the pair ranker (predict_pair.hip): a tile of 16 (user, item) pairs whose gathered row is K0 = 2 D wide,
+// D in {8, 16, 32} -- predict_lds_floats' plan with 2 D in place of 16 F, which is its plan for F = D / 8 fields of 16.
+inline long long pair_lds_floats(int U, int C, int D, int L, const int32_t* widths, TowerArgs* p) {
+  if ((D != 8 && D != 16 && D != 32) || L < 1 || U < 1 || C < 1) return -1;
+  if ((long long)U * C >= (1ll << 31)) return -1;
+  return predict_lds_floats(1, D / 8, 16, L, widths, p);
 }
 
 }  // namespace

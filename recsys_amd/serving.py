@@ -63,6 +63,10 @@ from .serving_din import (  # noqa: F401
     check_rank_request, check_top_k, expand_rank_request, item_neighbours_host, narrow_neighbours_host, ranking_metrics,
     recommend_host, recommend_two_stage_host, retrieve_candidates_host, rows_dot_host, target_ranks_host, topk_rows_host,
     two_stage_metrics, two_stage_ranks_host, unit_rows_host)
+# ... and what uid_iid deepfm.py bundles answer beside it in serving_pairs.py
+from .serving_pairs import (  # noqa: F401
+    PairRanking, check_item_catalogue, check_pair_exclude, check_pair_request, exclusion_positions, expand_pair_request,
+    hash_pair_ids, pair_slots, recommend_items_host)
 
 FORMAT_VERSION = 1                    # float32 tables; 16-bit tables (`table_dtype`, `encoding`) make a bundle version 2
 FORMAT_VERSION_16BIT = 2
@@ -429,11 +433,13 @@ def _build_store(est, script):
 
 
 # ---- Predictor ---------------------------------------------------------------------------------------------------------------
-class Predictor(DinRanking):
+class Predictor(DinRanking, PairRanking):
     """An exported model ready to answer requests.  See the module docstring for the two paths.  `table_dtype` is the
     bundle's ("float32" for a version 1 bundle): on the fused path the device holds the table in that dtype; on the layers
     path a 16-bit table is widened to fp32 on the host (the rounded values, no memory saved, `rank_candidates` unchanged).
-    What din.py bundles answer beside `predict` is inherited from `DinRanking` (serving_din.py; its docstring has those requests)."""
+    What din.py bundles answer beside `predict` is inherited from `DinRanking` (serving_din.py; its docstring has those requests),
+    what uid_iid deepfm.py bundles answer -- `rank_items`, `set_item_catalogue`, `recommend_items` -- from `PairRanking`
+    (serving_pairs.py)."""
 
     MAX_GRAPHS = 32            # request sizes that get a captured graph at most (Estimator.MAX_INFER_GRAPHS' twin)
 
@@ -512,6 +518,11 @@ class Predictor(DinRanking):
         self.neighbours_path = None         # where the latest `build_neighbours` built it
         self.two_stage_path = None          # where the latest `recommend_two_stage` ran
         self.evaluate_two_stage_path = None # where the latest `evaluate_two_stage` ranked
+        self._pair = None                   # PairRanking's model and buffers: made by the first ranking request
+        self._item_cat = None               # `set_item_catalogue`'s ids (uid_iid deepfm.py bundles)
+        self.item_catalogue_size = None
+        self.pair_topk_path = None          # where the latest `rank_items(top_k=k)` selected
+        self.recommend_items_path = None    # where the latest `recommend_items` selected
         if self.script == "din":
             self.rank_path = "fused" if self._rank_supported() else "layers"
             self.topk_path = "device" if self.rank_path == "fused" else "host"
