@@ -1344,6 +1344,17 @@ int rsx_cin_layer_bwd(const float* X0, const float* Xk, const float* W, const fl
 size_t rsx_cin_bwd_workspace_floats(int B, int F, int H, int N);
 /* sweep_h (nullable): a slice of the untouched-row optimizer sweep carried by extra workgroups of the dW launch (the
  * MFMA-bound tiles leave HBM idle), as on the tower entry points.                                                  */
+/* The forms rsx_cin_layer_fwd / rsx_cin_layer_bwd take for a layer of (F, H, N) at D = 16 -- the launchers' own selection,
+ * host arithmetic only (no GPU call), for tests that assert the form of a case.  carries_sweep: a sweep slice rides in the
+ * backward (sweep_h != NULL).  RSX_EINVAL for a size <= 0 (B < 0) or out == NULL; RSX_EUNSUPPORTED where either launcher
+ * answers so (the entries of the launcher that would run are still filled, the other's are -1).
+ *   out[0] HSMAX of cin_fwd_k (12 | 32)
+ *   out[1] data gradients: 1 = cin_bwd_dx2_k<NSMAX, 4, 1> + cin_dx0_reduce_k (h tiles over the grid), 0 = cin_bwd_dx_k<NSMAX>
+ *   out[2] NSMAX (2 | 8)             out[3] FS, the field split (workgroup = 4 waves tiled, else HT * FS)
+ *   out[4] that launch's dynamic LDS bytes      out[5] 1 = above 64 KiB: the launcher opts the kernel in first
+ *   out[6] weight-gradient configuration 0..4: cin_bwd_dw_k<5,2,8> <5,1,4> <3,1,4> <2,2,8> <2,1,4>
+ *   out[7] HT = ceil(H / 16)                                                                                          */
+int rsx_cin_layer_plan(int B, int F, int H, int N, int carries_sweep, int32_t out[8]);
 /* 'cin_net' output head, xdeepfm/xdeepfm.py:180-182 (concat of the L layer maps on axis 1, reduce_sum over d, dense(1, relu)):
  *   y[b] = relu(bout + sum_k sum_n Wout[off_k + n] * sum_d out_k[b,n,d]),  off_k = n_0 + .. + n_{k-1}
  * outs_h: HOST array of L device pointers [B, n_k, 16]; sizes_h: HOST array of the n_k.  L <= 8.  The concat is never

@@ -621,9 +621,14 @@ __global__ __launch_bounds__(64 * NW) void cin_bwd_dw_k(const CinBwdDwArgs p) {
     if (c0) __syncthreads();
 #pragma unroll
     for (int u = 0; u < CH; ++u)
-      if (c0 + u < TT + NT) {
+      if (c0 + u < TT) {
 #pragma unroll
         for (int r = 0; r < 4; ++r) red[wv][u][(kq * 4 + r) * 16 + i] = tl[c0 + u][r];
+      } else if (c0 + u < TT + NT) {
+        // a ones-row tile: only row 0 is read back.  (Storing all four rows also made hipcc pair the stores of rows 0 and 1 of
+        // <5, 1, 4>'s second pass into one ds_write2_b32 whose first offset belongs to another base register: row 0 landed in
+        // the neighbouring tile, dc came out zero and every fifth field's dW tile held 16 wrong entries.)
+        if (kq == 0) red[wv][u][i] = tl[c0 + u][0];
       }
     __syncthreads();
     // tile c0 + u is summed and stored by wave u (u < CH <= NW).  C layout: col = lane & 15 (n), row = 4*kq + r
@@ -656,6 +661,93 @@ __global__ __launch_bounds__(64 * NW) void cin_bwd_dw_k(const CinBwdDwArgs p) {
   }
 }
 
+// ----------------------------------------------------------------------------------------------- the launch plans
+// Which instantiation, workgroup shape and LDS size a layer of (F, H, N) takes: host arithmetic only, shared by the launchers
+// below and by rsx_cin_layer_plan, so that a test can assert the form a shape took instead of restating the rules.
+struct CinFwdPlan {
+  int hsmax;     // cin_fwd_k<HSMAX>: 12 covers H <= 48, 32 covers H <= 128
+  size_t lds;    // dynamic LDS bytes
+};
+static int cin_fwd_plan(int F, int H, CinFwdPlan& pl) {
+  if (H > 128) return RSX_EUNSUPPORTED;
+  pl.hsmax = H <= 48 ? 12 : 32;
+  pl.lds = ((size_t)2 * 16 * (4 * pl.hsmax + 4) + (size_t)4 * F * CIN_D) * sizeof(float);
+  if (pl.lds > 64 * 1024) return RSX_EUNSUPPORTED;
+  return RSX_OK;
+}
+
+struct CinBwdPlan {
+  int HT;        // 16-wide h tiles
+  bool tiled;    // cin_bwd_dx2_k<NSMAX, 4, 1> + cin_dx0_reduce_k, else cin_bwd_dx_k<NSMAX> with HT * FS waves
+  int nsmax;     // 2 covers N <= 32, 8 covers N <= 128
+  int FS;        // field split of the data-gradient workgroup
+  size_t lds;    // dynamic LDS bytes of the data-gradient launch
+  bool optin;    // more than 64 KiB: the kernel must opt in (host-side attribute)
+  int cfg;       // index into CIN_DW_CFGS
+};
+static const int CIN_DW_CFGS[5][3] = {{5, 2, 8}, {5, 1, 4}, {3, 1, 4}, {2, 2, 8}, {2, 1, 4}};   // FT, NT, NW
+static int cin_bwd_plan(int F, int H, int N, bool carries_sweep, CinBwdPlan& pl) {
+  if (H > 128 || N > 128) return RSX_EUNSUPPORTED;
+  const int HT = (H + 15) / 16;
+  pl.HT = HT;
+  pl.nsmax = N <= 32 ? 2 : 8;
+  static const int dx_force = getenv("RSX_CIN_DX") ? atoi(getenv("RSX_CIN_DX")) : -1;
+  // Many h tiles (H > 64): weight slices shared by 4 examples through LDS (measured 131 vs 137 us backward at H = N = 128);
+  // few: one workgroup per example with the rows in registers (66 vs 75 us at H = 39).
+  pl.tiled = (N & 3) == 0 && (dx_force >= 0 ? dx_force != 0 : HT >= 5);
+  if (pl.tiled) {
+    const int EB = 4, FS = 1;
+    const int NP = N + 4;
+    const size_t r0 = (size_t)2 * FS * 16 * NP, r1 = (size_t)EB * N * CIN_D;
+    pl.FS = FS;
+    pl.lds = ((r0 > r1 ? r0 : r1) + (size_t)EB * F * CIN_D + (size_t)EB * 256 + (size_t)FS * EB * 256) * sizeof(float);
+    if (pl.lds > 64 * 1024) return RSX_EUNSUPPORTED;
+    pl.optin = false;
+  } else {
+    const int FS = HT <= 3 ? 4 : HT <= 4 ? 2 : 1;   // waves = HT * FS <= 12, an even load for the 4 SIMDs
+    pl.FS = FS;
+    pl.lds = ((size_t)CIN_BT * (N + F + H) * CIN_D + (size_t)HT * CIN_BT * F * CIN_D + (size_t)FS * HT * CIN_BT * 256) * sizeof(float);
+    if (pl.lds > 160 * 1024) return RSX_EUNSUPPORTED;
+    pl.optin = pl.lds > 64 * 1024;   // gfx950 has 160 KiB of LDS per CU; above 64 KiB the kernel must opt in
+  }
+  // Wave tile = FT fields x 16 h x (NT x 16) n, NW waves split the batch.  The configuration is chosen for BALANCE first
+  // (workgroups are equal-sized: ceil(WGs / 256 CUs) rounds of FT*NT work each), then for the larger tile (fewer operand
+  // bytes per MFMA).
+  static const int force = getenv("RSX_CIN_DW_CFG") ? atoi(getenv("RSX_CIN_DW_CFG")) : -1;
+  int best = 0;
+  double best_cost = 1e30;
+  for (int c = 0; c < 5; ++c) {
+    const int ft = CIN_DW_CFGS[c][0], nt = CIN_DW_CFGS[c][1];
+    const long wgs = (long)((N + 16 * nt - 1) / (16 * nt)) * HT * ((F + ft - 1) / ft);
+    const double cost = (double)((wgs + 255) / 256) * ft * nt * (1.0 + 0.02 * c);   // earlier entries win ties
+    if (cost < best_cost) { best_cost = cost; best = c; }
+  }
+  if (carries_sweep) best = 2;   // carrying sweep workgroups: they inherit the tile kernel's footprint, and the small
+                                 // 4-wave / 104-VGPR configuration co-runs best with them (measured end to end)
+  if (force >= 0 && force < 5) best = force;
+  pl.cfg = best;
+  return RSX_OK;
+}
+
+extern "C" int rsx_cin_layer_plan(int B, int F, int H, int N, int carries_sweep, int32_t out[8]) {
+  if (B < 0 || F <= 0 || H <= 0 || N <= 0 || !out) return RSX_EINVAL;
+  for (int k = 0; k < 8; ++k) out[k] = -1;
+  CinFwdPlan fp{};
+  CinBwdPlan bp{};
+  const int rcf = cin_fwd_plan(F, H, fp), rcb = cin_bwd_plan(F, H, N, carries_sweep != 0, bp);
+  if (rcf == RSX_OK) out[0] = fp.hsmax;
+  if (rcb == RSX_OK) {
+    out[1] = bp.tiled ? 1 : 0;
+    out[2] = bp.nsmax;
+    out[3] = bp.FS;
+    out[4] = (int32_t)bp.lds;
+    out[5] = bp.optin ? 1 : 0;
+    out[6] = bp.cfg;
+    out[7] = bp.HT;
+  }
+  return rcf != RSX_OK ? rcf : rcb;
+}
+
 // ----------------------------------------------------------------------------------------------- C ABI
 extern "C" int rsx_cin_layer_fwd(const float* X0, const float* Xk, const float* W, const float* c, float* out, int B,
                                  int F, int H, int N, int D, const rsx_adam_slice* sweep_h, rsx_stream_t stream) {
@@ -663,16 +755,16 @@ extern "C" int rsx_cin_layer_fwd(const float* X0, const float* Xk, const float* 
   if (B == 0) return RSX_OK;
   if (!X0 || !Xk || !W || !c || !out) return RSX_EINVAL;
   if (D != CIN_D) return RSX_EUNSUPPORTED;
-  if (H > 128) return RSX_EUNSUPPORTED;
-  const int hsmax = H <= 48 ? 12 : 32;
-  const size_t lds = ((size_t)2 * 16 * (4 * hsmax + 4) + (size_t)4 * F * CIN_D) * sizeof(float);
-  if (lds > 64 * 1024) return RSX_EUNSUPPORTED;
+  CinFwdPlan pl{};
+  const int rcp = cin_fwd_plan(F, H, pl);
+  if (rcp != RSX_OK) return rcp;
+  const size_t lds = pl.lds;
   CinFwdArgs p{X0, Xk, W, c, out, B, F, H, N, (B + 3) / 4, {}};
   const int rcs = adam_build_slice(sweep_h, p.sweep);
   if (rcs != RSX_OK) return rcs;
   const unsigned gx = (unsigned)((N + 15) / 16);
   const dim3 grid(gx, p.nby + (p.sweep.n_blk + gx - 1) / gx);
-  if (H <= 48) RSX_LAUNCH(cin_fwd_k<12>, grid, dim3(256), lds, rsx_s(stream), p);
+  if (pl.hsmax == 12) RSX_LAUNCH(cin_fwd_k<12>, grid, dim3(256), lds, rsx_s(stream), p);
   else RSX_LAUNCH(cin_fwd_k<32>, grid, dim3(256), lds, rsx_s(stream), p);
   RSX_CHECK_LAUNCH();
   return RSX_OK;
@@ -691,22 +783,18 @@ extern "C" int rsx_cin_layer_bwd(const float* X0, const float* Xk, const float* 
   if (!X0 || !Xk || !W || !out || !dXk || !dX0 || !dW || !dc || !dpre_ws) return RSX_EINVAL;
   if ((!dout && !gs) || (gs && !wout)) return RSX_EINVAL;
   if (dXk == dX0 && !(Xk == X0 && acc_dx0)) return RSX_EINVAL;   // one buffer only for the first layer, accumulating
-  if (D != CIN_D || H > 128 || N > 128) return RSX_EUNSUPPORTED;
-  const int HT = (H + 15) / 16;
+  if (D != CIN_D) return RSX_EUNSUPPORTED;
+  CinBwdPlan pl{};
+  const int rcp = cin_bwd_plan(F, H, N, sweep_h != nullptr, pl);
+  if (rcp != RSX_OK) return rcp;
+  const int HT = pl.HT;
+  const size_t lds = pl.lds;
   CinBwdDxArgs a{X0, Xk, W, out, dout, gs, wout, dXk, dX0, dpre_ws, acc_dxk, acc_dx0, B, F, H, N, HT};
-  static const int dx_force = getenv("RSX_CIN_DX") ? atoi(getenv("RSX_CIN_DX")) : -1;
-  // Many h tiles (H > 64): weight slices shared by 4 examples through LDS (measured 131 vs 137 us backward at H = N = 128);
-  // few: one workgroup per example with the rows in registers (66 vs 75 us at H = 39).
-  const bool tiled = (N & 3) == 0 && (dx_force >= 0 ? dx_force != 0 : HT >= 5);
-  if (tiled) {
+  if (pl.tiled) {
     const int EB = 4, FS = 1;
-    const int NP = N + 4;
-    const size_t r0 = (size_t)2 * FS * 16 * NP, r1 = (size_t)EB * N * CIN_D;
-    const size_t lds = ((r0 > r1 ? r0 : r1) + (size_t)EB * F * CIN_D + (size_t)EB * 256 + (size_t)FS * EB * 256) * sizeof(float);
-    if (lds > 64 * 1024) return RSX_EUNSUPPORTED;
     float* part_ws = dpre_ws + (size_t)B * N * CIN_D;
     const dim3 grid(HT, (B + EB - 1) / EB), block(64 * EB * FS);
-    if (N <= 32) RSX_LAUNCH((cin_bwd_dx2_k<2, 4, 1>), grid, block, lds, rsx_s(stream), a, part_ws);
+    if (pl.nsmax == 2) RSX_LAUNCH((cin_bwd_dx2_k<2, 4, 1>), grid, block, lds, rsx_s(stream), a, part_ws);
     else RSX_LAUNCH((cin_bwd_dx2_k<8, 4, 1>), grid, block, lds, rsx_s(stream), a, part_ws);
     RSX_CHECK_LAUNCH();
     const long long n4 = (long long)B * F * 4;
@@ -714,38 +802,20 @@ extern "C" int rsx_cin_layer_bwd(const float* X0, const float* Xk, const float* 
                        acc_dx0);
     RSX_CHECK_LAUNCH();
   } else {
-    const int FS = HT <= 3 ? 4 : HT <= 4 ? 2 : 1;   // waves = HT * FS <= 12, an even load for the 4 SIMDs
-    const size_t lds = ((size_t)CIN_BT * (N + F + H) * CIN_D + (size_t)HT * CIN_BT * F * CIN_D + (size_t)FS * HT * CIN_BT * 256) * sizeof(float);
-    if (lds > 160 * 1024) return RSX_EUNSUPPORTED;
-    if (lds > 64 * 1024) {   // gfx950 has 160 KiB of LDS per CU; above 64 KiB the kernel must opt in (host-side attribute)
+    if (pl.optin) {   // host-side attribute, see CinBwdPlan
       if (hipFuncSetAttribute(reinterpret_cast<const void*>(cin_bwd_dx_k<8>), hipFuncAttributeMaxDynamicSharedMemorySize,
                               (int)lds) != hipSuccess ||
           hipFuncSetAttribute(reinterpret_cast<const void*>(cin_bwd_dx_k<2>), hipFuncAttributeMaxDynamicSharedMemorySize,
                               (int)lds) != hipSuccess)
         return RSX_ELAUNCH;
     }
-    const dim3 grid((B + CIN_BT - 1) / CIN_BT), block(64 * HT * FS);
-    if (N <= 32) RSX_LAUNCH(cin_bwd_dx_k<2>, grid, block, lds, rsx_s(stream), a);
+    const dim3 grid((B + CIN_BT - 1) / CIN_BT), block(64 * HT * pl.FS);
+    if (pl.nsmax == 2) RSX_LAUNCH(cin_bwd_dx_k<2>, grid, block, lds, rsx_s(stream), a);
     else RSX_LAUNCH(cin_bwd_dx_k<8>, grid, block, lds, rsx_s(stream), a);
     RSX_CHECK_LAUNCH();
   }
-  // Wave tile = FT fields x 16 h x (NT x 16) n, NW waves split the batch.  The configuration is chosen for BALANCE first
-  // (workgroups are equal-sized: ceil(WGs / 256 CUs) rounds of FT*NT work each), then for the larger tile (fewer operand
-  // bytes per MFMA).
-  static const int force = getenv("RSX_CIN_DW_CFG") ? atoi(getenv("RSX_CIN_DW_CFG")) : -1;
-  static const int cfgs[5][3] = {{5, 2, 8}, {5, 1, 4}, {3, 1, 4}, {2, 2, 8}, {2, 1, 4}};
-  int best = 0;
-  double best_cost = 1e30;
-  for (int c = 0; c < 5; ++c) {
-    const int ft = cfgs[c][0], nt = cfgs[c][1];
-    const long wgs = (long)((N + 16 * nt - 1) / (16 * nt)) * HT * ((F + ft - 1) / ft);
-    const double cost = (double)((wgs + 255) / 256) * ft * nt * (1.0 + 0.02 * c);   // earlier entries win ties
-    if (cost < best_cost) { best_cost = cost; best = c; }
-  }
-  if (sweep_h != nullptr) best = 2;   // carrying sweep workgroups: they inherit the tile kernel's footprint, and the small
-                                      // 4-wave / 104-VGPR configuration co-runs best with them (measured end to end)
-  if (force >= 0 && force < 5) best = force;
-  const int FT = cfgs[best][0], NT = cfgs[best][1], NW = cfgs[best][2];
+  const int best = pl.cfg;
+  const int FT = CIN_DW_CFGS[best][0], NT = CIN_DW_CFGS[best][1], NW = CIN_DW_CFGS[best][2];
   CinBwdDwArgs w{X0, Xk, dpre_ws, dW, dc, B, F, H, N, (F + FT - 1) / FT, {}};
   const int rcs = adam_build_slice(sweep_h, w.sweep);
   if (rcs != RSX_OK) return rcs;

@@ -52,6 +52,39 @@ def test_cin_entry_points_reject_bad_arguments(L):
     assert L.rsx_cin_bwd_workspace_floats(4, 39, 128, 128) == 4 * 128 * 16 + 8 * 4 * 39 * 16
 
 
+def test_cin_layer_plan_answers_as_the_launchers_do(L):
+    """rsx_cin_layer_plan: host arithmetic only.  Its forms for a few known shapes, its error returns, and the same answer as
+    rsx_cin_layer_fwd / rsx_cin_layer_bwd wherever those refuse a shape (which they do before any HIP call)."""
+    def plan(B, F, H, N, sweep=0):
+        out = (C.c_int32 * 8)(*([7] * 8))
+        return L.rsx_cin_layer_plan(B, F, H, N, sweep, out), tuple(out)
+    fwd = lambda F, H, N: L.rsx_cin_layer_fwd(P, P, P, P, P, 4, F, H, N, 16, None, None)
+    bwd = lambda F, H, N: L.rsx_cin_layer_bwd(P, C.c_void_p(0x3000), P, P, P, None, None, P, 0, C.c_void_p(0x2000), 0, P, P, P, 4, F, H, N,
+                                              16, None, None)
+    # HSMAX, tiled, NSMAX, FS, LDS bytes, opt-in, dW configuration, HT
+    assert plan(256, 39, 128, 128) == (OK, (32, 1, 8, 1, (64 * 128 + 4 * 39 * 16 + 2 * 4 * 256) * 4, 0, 0, 8))
+    assert plan(256, 39, 128, 128, 1) == (OK, (32, 1, 8, 1, 50944, 0, 2, 8))                  # a sweep slice riding: configuration 2
+    assert plan(256, 39, 39, 128) == (OK, (12, 0, 8, 4, ((128 + 39 + 39) * 16 + 3 * 39 * 16 + 4 * 3 * 256) * 4, 0, 3, 3))
+    assert plan(4, 39, 64, 32)[1][:4] == (32, 0, 2, 2) and plan(4, 39, 128, 50)[1][:4] == (32, 0, 8, 1)
+    assert plan(4, 7, 48, 16)[1][0] == 12 and plan(4, 7, 49, 16)[1][0] == 32
+    assert plan(5, 100, 128, 126) == (OK, (32, 0, 8, 1, 82048, 1, 1, 8))                      # above 64 KiB: the opt-in
+    assert plan(0, 39, 39, 128)[0] == OK                                                     # B takes no part in the selection
+    # bad arguments
+    assert plan(-1, 39, 39, 128)[0] == EINVAL and plan(4, 0, 39, 128)[0] == EINVAL and plan(4, 39, 0, 128)[0] == EINVAL
+    assert plan(4, 39, 39, 0)[0] == EINVAL and L.rsx_cin_layer_plan(4, 39, 39, 128, 0, None) == EINVAL
+    # refused shapes: the same answer as the launcher that refuses, the other launcher's entries still filled
+    rc, p = plan(4, 39, 200, 16)                                                             # H > 128: both
+    assert rc == EUNSUPPORTED == fwd(39, 200, 16) == bwd(39, 200, 16) and p == (-1,) * 8
+    rc, p = plan(4, 39, 39, 132)                                                             # N > 128: the backward alone
+    assert rc == EUNSUPPORTED == bwd(39, 39, 132) and p == (12,) + (-1,) * 7
+    rc, p = plan(4, 100, 128, 128)                                                           # tiled: 66 560 B, and no opt-in there
+    assert rc == EUNSUPPORTED == bwd(100, 128, 128) and p == (32,) + (-1,) * 7
+    rc, p = plan(4, 300, 128, 126)                                                           # untiled: above 160 KiB; forward: above 64
+    assert rc == EUNSUPPORTED == bwd(300, 128, 126) == fwd(300, 128, 126) and p == (-1,) * 8
+    rc, p = plan(4, 240, 16, 16)                                                             # the forward alone (68 096 B)
+    assert rc == EUNSUPPORTED == fwd(240, 16, 16) and p[0] == -1 and p[1:4] == (0, 2, 4)
+
+
 def test_tower_batch_norm_free_mode_is_all_or_nothing(L):
     u32 = C.c_uint32
     # forward: previous layer present (fstat_prev) with gamma but no beta / bn_prev_out
